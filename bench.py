@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — long-read bases/sec through rare-k-mer recruit + distance (A1-A6) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one full pass of the hot path over the synthetic read set, with the packed reads
 already resident in HBM: A1 presence table -> A2 rare window + sort -> A3 unit clouds ->
@@ -17,7 +17,11 @@ WORLD_SIZE / MASTER_PORT read from the environment; the RCCL unique id travels t
 the launcher's pid), or started plainly as `python bench.py --gpus N`, in which case this process
 — which never touches a GPU — starts the N ranks as child processes itself.
 
-Rank 0 prints ONE JSON line (contract in the task brief) with these extra objects:
+Rank 0 prints ONE JSON line: the headline (metric, value, unit, higher_is_better, dtype, ms_per_step = the
+milliseconds of one of the --steps timed steps) with the step's counters and stage split.  A plain run does
+nothing else: set-up, --warmup steps, the timed steps, the line.  --dump-outputs DIR also writes what the last
+timed step computed as DIR/<name>.npy (float64 / float32; a fixed sample of the rare k-mers, device checksums of
+the rest: dump_outputs), the same from run to run for the same arguments.  --full adds these objects:
   roofline              the dominant kernel (cf_dist_kernel): algorithmic bytes per launch (4 B per pair
                         emission + 4 B per cloud entry + 16 B per stored edge) over its mean launch
                         duration, measured with HIP events on the library's own stream; plus
@@ -360,7 +364,50 @@ def parse_args():
     ap.add_argument("--reads-c", type=int, default=CENX["n_reads"], help="test hook: reads of workload_c"); ap.add_argument("--units-c", type=int, default=CENX["n_units"], help="test hook: array units of workload_c")
     ap.add_argument("--steps-c", type=int, default=5, help="timed steps of workload_c (cenX-shaped reads: BASELINE configs[4]'s regime), N = 1 only; 0 = skip")
     ap.add_argument("--lib", default=None, help="test hook: another build of libcfhip (the CPU suite passes the host-emulated one to check this harness)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also run every leg beyond the headline: roofline, transfers, parity against the committed oracle "
+                                                         "records, placement, read recruitment (--rr), CPU baseline, workload_b, workload_c")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_SAMPLE = 1 << 20       # rare k-mers written by --dump-outputs: all of them up to this many, else a fixed seeded sample
+
+
+def _hi_lo(v):
+    """uint64 values as exact float64 (hi 32 bits, lo 32 bits) pairs."""
+    v = np.asarray(v, np.uint64)
+    return np.stack([(v >> np.uint64(32)).astype(np.float64), (v & np.uint64(0xFFFFFFFF)).astype(np.float64)], -1)
+
+
+def dump_outputs(path, sr, out):
+    """What the last timed step hands a caller (ShardedRecruiter.run + .rare / .unique_mask / the stored edges), as float arrays
+    (28 MB at most).  The edge rows (50 GB at the default size) are stored in the order workgroups finish, so they go out as
+    their order-independent device checksum, summed over ranks; every rank must call this (the sum is a collective)."""
+    E = sr.engine
+    edges = int(E.edges_checksum())
+    parts = sr.allreduce([edges >> 32, edges & 0xFFFFFFFF], "sum")
+    edges = ((int(parts[0]) << 32) + int(parts[1])) % 2 ** 64
+    if sr.rank != 0:
+        return
+    rare, mask = sr.rare, sr.unique_mask
+    idx = np.arange(rare.size)
+    if rare.size > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(rare.size, DUMP_SAMPLE, replace=False))
+    names = ("n_bases", "n_windows", "n_read_kmers", "n_distinct", "n_kept", "n_rare", "n_cloud_entries", "n_emissions", "n_edges", "n_unique")
+    arrays = {
+        "counters": np.array([out[k] for k in names], np.float64),          # (in the order of `names`)
+        "rare_kmer_index": idx.astype(np.float64),                            # positions of the written k-mers in the ascending rare set
+        "rare_kmers": _hi_lo(rare[idx]),                                      # 2-bit codes, (hi, lo) 32-bit halves
+        "unique_mask": mask[idx].astype(np.float32),                          # 1 = selected by some edge
+        # device checksums of every stored edge, the rare set, the cloud CSR and the unique k-mers (include/cfhip.h), (hi, lo) halves
+        "checksums": _hi_lo([edges, E.checksum("kmers")[0], E.checksum("clouds")[0], E.checksum("unique")[0]]),
+    }
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), arr)
 
 
 def launch_ranks(a):
@@ -445,7 +492,7 @@ def main():
     # the same step with the host hand-over inside the timed region: H2D of the packed reads, D2H of the
     # rare set, the unique mask and stored edges (up to --d2h-edge-bytes of them)
     incl = None
-    if a.transfer_steps > 0:
+    if a.full and a.transfer_steps > 0:
         n_back = int(min(stored, a.d2h_edge_bytes // 16))
         sr.barrier()
         t1 = time.perf_counter()
@@ -473,17 +520,11 @@ def main():
                          "complete_d2h_of_all_edges_bytes (about one second at the 55 GB/s this path reaches), which scripts/distance_based_kmer_recruitment.py "
                          "never needs at once: it writes the edge file partition by partition")
 
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, sr, out)
+
     if rank == 0:
-        ms_per_step = elapsed * 1e3 / max(a.steps, 1)
-        mean_k_ms = float(np.mean(kernel_ms)) if kernel_ms else 0.0
-        # algorithmic bytes of ONE launch of the dominant kernel on this rank (SURVEY.md §8d): every cloud entry it
-        # works on staged once, one 4-byte partner index per pair emission, 16 bytes per stored edge
-        alg_bytes = 4 * out["dist_cloud_entries"] + 4 * out["local_emissions"] + 16 * stored
-        achieved = alg_bytes / (mean_k_ms * 1e-3) / 1e9 if mean_k_ms > 0 else 0.0
-        # B_alg of the whole step (SURVEY §8d), all ranks: [N_b + 16 N_rk] + [16 K_dist] + [N_b + 8 N_w + 4 N_ce] + [4 N_ce + 4 E] + [16 edges stored]
-        b_alg = (n_bases + 16 * out["n_read_kmers"]) + 16 * out["n_distinct"] + (n_bases + 8 * out["n_windows"] + 4 * out["n_cloud_entries"]) \
-            + (4 * out["n_cloud_entries"] + 4 * out["n_emissions"]) + 16 * min(out["n_edges"], edge_cap * world)
-        derived, derived_from = pmc_derived()
+        ms_per_step = elapsed * 1e3 / a.steps
         res = {
             "metric": "long-read bases/sec through rare-k-mer recruit+distance",
             "value": n_bases * a.steps / elapsed,
@@ -498,20 +539,6 @@ def main():
                                    f"{stored} of {out['local_edges']} selected edges stored per GPU (BASELINE configs[1]+[2], stage 2)",
                        "reads_per_gpu": a.reads, "k": K, "var_len": VAR_LEN, "edges_stored": int(stored), "edges_selected": int(out["local_edges"]),
                        "parallelism": f"reads sharded x{world}, first k-mers partitioned x{world}"},
-            "value_incl_transfers": incl,
-            # `frac` prices the kernel's ALGORITHMIC bytes against the HBM peak (the contract's definition); `bound` names what the
-            # counters of the committed PMC passes say limits it — for this kernel LDS round-trip latency at 4 waves per SIMD, not HBM
-            # ("the roofline label is formal; say what binds"): `lds`, `l2_hit`, `hbm_side_gbps` are those counters
-            "roofline": {"bound": (derived or {}).get("bound", "hbm"), "bound_by_contract": "hbm", "kernel": "cf_dist_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(a, world, stored, out),
-                         "lds": (derived or {}).get("lds"), "l2_hit": (derived or {}).get("l2_hit"), "hbm_side_gbps": (derived or {}).get("hbm_side_gbps"),
-                         "issue_per_cycle_per_cu": (derived or {}).get("issue_per_cycle_per_cu"), "counters_from": derived_from,
-                         "traffic_note": "HBM-side bytes of ONE launch from the committed rocprofv3 --pmc passes of this configuration (profiles/r0N_pmc_dist_kernel.json, the latest round's: "
-                                         "(2 x FETCH_SIZE + WRITE_SIZE) x 1024, separate passes, tools/profile_round.sh); counters cannot be read inside a timed run; null when the workload differs",
-                         "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": mean_k_ms,
-                         "pair_emissions_per_s": out["local_emissions"] / (mean_k_ms * 1e-3) if mean_k_ms else 0.0,
-                         "whole_step_algorithmic_bytes": b_alg,
-                         "whole_step_frac": b_alg / (ms_per_step * 1e-3) / 1e9 / (HBM_PEAK_GBS * world)},
             "counters": {k: out[k] for k in ("n_bases", "n_windows", "n_read_kmers", "n_distinct", "n_kept", "n_rare", "n_cloud_entries",
                                              "n_emissions", "n_edges", "n_unique", "n_dist_passes")},
             "stage_ms_per_step": stage_ms,
@@ -521,6 +548,30 @@ def main():
             "steps_identical": bool(same),
             "device": E.device_info()["name"].strip(),
         }
+    if rank == 0 and a.full:
+        mean_k_ms = float(np.mean(kernel_ms)) if kernel_ms else 0.0
+        # algorithmic bytes of ONE launch of the dominant kernel on this rank (SURVEY.md §8d): every cloud entry it
+        # works on staged once, one 4-byte partner index per pair emission, 16 bytes per stored edge
+        alg_bytes = 4 * out["dist_cloud_entries"] + 4 * out["local_emissions"] + 16 * stored
+        achieved = alg_bytes / (mean_k_ms * 1e-3) / 1e9 if mean_k_ms > 0 else 0.0
+        # B_alg of the whole step (SURVEY §8d), all ranks: [N_b + 16 N_rk] + [16 K_dist] + [N_b + 8 N_w + 4 N_ce] + [4 N_ce + 4 E] + [16 edges stored]
+        b_alg = (n_bases + 16 * out["n_read_kmers"]) + 16 * out["n_distinct"] + (n_bases + 8 * out["n_windows"] + 4 * out["n_cloud_entries"]) \
+            + (4 * out["n_cloud_entries"] + 4 * out["n_emissions"]) + 16 * min(out["n_edges"], edge_cap * world)
+        derived, derived_from = pmc_derived()
+        res["value_incl_transfers"] = incl
+        # `frac` prices the kernel's ALGORITHMIC bytes against the HBM peak (the contract's definition); `bound` names what the
+        # counters of the committed PMC passes say limits it — for this kernel LDS round-trip latency at 4 waves per SIMD, not HBM
+        # ("the roofline label is formal; say what binds"): `lds`, `l2_hit`, `hbm_side_gbps` are those counters
+        res["roofline"] = {"bound": (derived or {}).get("bound", "hbm"), "bound_by_contract": "hbm", "kernel": "cf_dist_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic(a, world, stored, out),
+                           "lds": (derived or {}).get("lds"), "l2_hit": (derived or {}).get("l2_hit"), "hbm_side_gbps": (derived or {}).get("hbm_side_gbps"),
+                           "issue_per_cycle_per_cu": (derived or {}).get("issue_per_cycle_per_cu"), "counters_from": derived_from,
+                           "traffic_note": "HBM-side bytes of ONE launch from the committed rocprofv3 --pmc passes of this configuration (profiles/r0N_pmc_dist_kernel.json, the latest round's: "
+                                           "(2 x FETCH_SIZE + WRITE_SIZE) x 1024, separate passes, tools/profile_round.sh); counters cannot be read inside a timed run; null when the workload differs",
+                           "algorithmic_bytes_per_launch": alg_bytes, "kernel_ms": mean_k_ms,
+                           "pair_emissions_per_s": out["local_emissions"] / (mean_k_ms * 1e-3) if mean_k_ms else 0.0,
+                           "whole_step_algorithmic_bytes": b_alg,
+                           "whole_step_frac": b_alg / (ms_per_step * 1e-3) / 1e9 / (HBM_PEAK_GBS * world)}
         res["parity_vs_committed_oracle"] = committed_parity(out, E, a, world)
         if world == 1 and not a.no_place:
             # BASELINE configs[2]: cloud_contig extension on the same reads with the k-mers selected above
@@ -548,13 +599,15 @@ def main():
             res["cpu_baseline"] = cpu_baseline(a, pk, E)
         else:
             res["cpu_baseline"] = None
-    wb = workload_b(a, sr, rank, world) if a.steps_b > 0 else None      # (every rank: its steps hold collectives)
-    wc = workload_c(a, sr, rank, world) if (a.steps_c > 0 and world == 1) else None
+    if a.full:
+        wb = workload_b(a, sr, rank, world) if a.steps_b > 0 else None      # (every rank: its steps hold collectives)
+        wc = workload_c(a, sr, rank, world) if (a.steps_c > 0 and world == 1) else None
+        if rank == 0:
+            res["workload_b"] = wb
+            res["workload_c"] = wc
+            if world > 1 and not a.no_cpu_baseline:      # (behind the last collective of the other ranks: they wait in the closing barrier)
+                res["cpu_baseline"] = cpu_baseline_weak(a)
     if rank == 0:
-        res["workload_b"] = wb
-        res["workload_c"] = wc
-        if world > 1 and not a.no_cpu_baseline:      # (behind the last collective of the other ranks: they wait in the closing barrier)
-            res["cpu_baseline"] = cpu_baseline_weak(a)
         print(json.dumps(res), flush=True)
     sr.barrier()
     sr.close()

@@ -3,8 +3,11 @@
 (unit, read, threshold) cases with the distances the REFERENCE's own code returns — vendored edlib compiled from
 /root/reference by oracle/ref/Makefile into oracle/_ref/librr_ref.so (build container only).
 
-    python tests/golden/make_golden_rr.py          # writes rr_vectors.json
+    python tests/golden/make_golden_rr.py          # writes rr_vectors.json and rr_ref_random.json
     python tests/golden/make_golden_rr.py --check
+
+rr_ref_random.json: the reference's distance for each of the seeded random cases of tests/test_read_recruitment.py
+(random_cases), so that the test needs no reference library.
 """
 import json
 import os
@@ -61,15 +64,20 @@ def main():
         rc = rr.revcomp(unit)
         vec.append(dict(unit=unit.decode(), read=read.decode(), threshold=k, fwd=rr.ref_distance(unit, read, k), rc=rr.ref_distance(rc, read, k)))
     assert all(v["fwd"] is not None for v in vec), "oracle/_ref/librr_ref.so is missing: make -C oracle/ref"
-    path = os.path.join(HERE, "rr_vectors.json")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_read_recruitment import random_cases
+    rnd = dict(ref_distance=[rr.ref_distance(unit, read, k) for unit, read, k in random_cases()])
+    path, path_rnd = os.path.join(HERE, "rr_vectors.json"), os.path.join(HERE, "rr_ref_random.json")
     if check:
-        with open(path) as f:
-            same = json.load(f) == vec
+        with open(path) as f, open(path_rnd) as g:
+            same = json.load(f) == vec and json.load(g) == rnd
         print("IDENTICAL" if same else "DIFFERENT")
         sys.exit(0 if same else 1)
     with open(path, "w") as f:
         json.dump(vec, f, indent=0)
-    print(len(vec), "cases;", sum(v["fwd"] != -1 or v["rc"] != -1 for v in vec), "recruited")
+    with open(path_rnd, "w") as f:
+        json.dump(rnd, f)
+    print(len(vec), "cases;", sum(v["fwd"] != -1 or v["rc"] != -1 for v in vec), "recruited;", len(rnd["ref_distance"]), "random cases")
 
 
 if __name__ == "__main__":

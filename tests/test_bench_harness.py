@@ -8,11 +8,14 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EMU = os.path.join(ROOT, "tests", "emu", "libcfhip_emu.so")
-ARGS = ["--lib", EMU, "--reads", "6", "--steps", "1", "--warmup", "0", "--edge-cap", "1000", "--transfer-steps", "1", "--no-cpu-baseline", "--steps-b", "1", "--steps-c", "1", "--reads-c", "3", "--units-c", "24"]
+ARGS = ["--lib", EMU, "--full", "--reads", "6", "--steps", "1", "--warmup", "0", "--edge-cap", "1000", "--transfer-steps", "1", "--no-cpu-baseline", "--steps-b", "1", "--steps-c", "1", "--reads-c", "3", "--units-c", "24"]
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+            "counters", "stage_ms_per_step", "host_section_ms_per_step", "exchange_bytes_per_step", "setup_s", "steps_identical", "device")
 
 
 def _line(stdout):
@@ -99,6 +102,66 @@ def test_under_torch_distributed_run(emu_lib, tmp_path):
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=tmp_path, env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     _check(_line(p.stdout), 2)
+
+
+def test_plain_run_is_the_headline_and_dumps_the_same_outputs_twice(emu_lib, tmp_path):
+    """Without --full the line is the headline alone (no extra legs ran); --dump-outputs writes the last timed step's results as
+    float .npy files, equal between two runs with the same arguments; --steps is the number of timed steps."""
+    args = ["--lib", EMU, "--reads", "40", "--steps", "2", "--warmup", "1"]
+    dumps = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(tmp_path / run)], capture_output=True, text=True,
+                           timeout=600, cwd=tmp_path)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+        res = _line(p.stdout)
+        assert sorted(res) == sorted(HEADLINE), sorted(set(res) ^ set(HEADLINE))
+        assert res["steps"] == 2 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0 and res["steps_identical"]
+        assert abs(res["value"] - res["counters"]["n_bases"] / (res["ms_per_step"] * 1e-3)) <= 1e-6 * res["value"]
+        files = sorted(os.listdir(tmp_path / run))
+        assert files == ["checksums.npy", "counters.npy", "rare_kmer_index.npy", "rare_kmers.npy", "unique_mask.npy"]
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in files})
+        assert all(a.dtype in (np.float32, np.float64) for a in dumps[-1].values())
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 << 20
+    a, b = dumps
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    n_rare, n_unique = int(a["counters"][5]), int(a["counters"][9])
+    assert n_rare > 0 and a["rare_kmers"].shape == (n_rare, 2) and int(a["unique_mask"].sum()) == n_unique
+
+
+def test_dump_of_a_large_rare_set_is_a_fixed_bounded_sample(tmp_path):
+    """A rare set larger than bench.DUMP_SAMPLE goes out as the same seeded sample every time, within 64 MB in all."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class FakeEngine:
+        def edges_checksum(self):
+            return 2 ** 64 - 5
+
+        def checksum(self, what):
+            return 2 ** 63 + 7, 0
+
+    class FakeRecruiter:
+        rank, engine = 0, FakeEngine()
+        rare = np.arange(7_500_000, dtype=np.uint64) * np.uint64(3) + np.uint64(2 ** 62)
+        unique_mask = np.arange(7_500_000) % 3 == 0
+
+        def allreduce(self, values, op="sum"):
+            return np.asarray(values, np.int64)
+
+    out = dict.fromkeys(("n_bases", "n_windows", "n_read_kmers", "n_distinct", "n_kept", "n_rare", "n_cloud_entries", "n_emissions", "n_edges", "n_unique"), 1)
+    got = []
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), FakeRecruiter(), out)
+        files = sorted(os.listdir(tmp_path / run))
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 << 20
+        got.append({f[:-4]: np.load(tmp_path / run / f) for f in files})
+    a, b = got
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    idx = a["rare_kmer_index"].astype(np.int64)
+    assert idx.size == bench.DUMP_SAMPLE and (np.diff(idx) > 0).all()
+    codes = (a["rare_kmers"][:, 0].astype(np.uint64) << np.uint64(32)) + a["rare_kmers"][:, 1].astype(np.uint64)
+    assert np.array_equal(codes, FakeRecruiter.rare[idx]) and np.array_equal(a["unique_mask"], (idx % 3 == 0).astype(np.float32))
+    assert a["checksums"].tolist()[0] == [2 ** 32 - 1, 2 ** 32 - 5] and a["checksums"].tolist()[1] == [2 ** 31, 7]
 
 
 def test_package_and_bench_are_torch_free():

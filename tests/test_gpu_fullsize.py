@@ -7,7 +7,7 @@
     first-k-mer partition (a % 64 == p for two p: dist_cnt[d][a] is a's own dict, so a partition is an independent
     piece of the same result): emission count, edge count, edge checksum (device-side and on the copied rows), the
     unique bits of the partition; the full 64/64 CPU run is committed under profiles/r03_full_parity.json and asserted
-    against a full GPU launch here and by bench.py every run;
+    against a full GPU launch here and by every bench.py --full run;
   * placement (A4 + A8/A9) of 3 000 reads vs the C restatement of the greedy loop: identical lines; and of the 50 000
     reads of configs[2] vs the same C placer (the arg-max scan threaded).
   * BASELINE configs[3] at its own size — 500 000 reads (~10 Gb) resident on one GPU: A1, A2, A3 of all reads and ONE WHOLE rank of 8

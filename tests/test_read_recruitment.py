@@ -1,8 +1,8 @@
 """SURVEY.md §8(f) rank 4 — read recruitment (reference scripts/read_recruitment/rr.cpp:73-90, vendored edlib in mode
-HW).  Golden vectors hold the distances the reference's own code returned (tests/golden/make_golden_rr.py, built from
-/root/reference into oracle/_ref by oracle/ref/Makefile).  CPU: the C oracle against them (and against oracle/_ref when
-that library is present), the kernel source on the host emulator, the FASTA/FASTQ reader.  GPU: the HIP kernel through
-the C ABI and the CLI."""
+HW).  Golden vectors hold the distances the reference's own code returned (tests/golden/make_golden_rr.py, with the
+reference's edlib built into oracle/_ref by oracle/ref/Makefile).  CPU: the C oracle against them (and against oracle/_ref
+when that library is present), the kernel source on the host emulator, the FASTA/FASTQ reader.  GPU: the HIP kernel
+through the C ABI and the CLI."""
 import gzip
 import json
 import os
@@ -47,10 +47,10 @@ def test_oracle_against_reference_vectors():
         assert rr.distance(rr.revcomp(unit), read, v["threshold"]) == v["rc"]
 
 
-def test_oracle_against_the_reference_library_when_present():
-    if rr.ref_distance(b"ACGT", b"ACGT", 1) is None:
-        pytest.skip("oracle/_ref/librr_ref.so not built (needs /root/reference: make -C oracle/ref)")
+def random_cases():
+    """300 seeded (unit, read, threshold) cases; the reference's answers to them are stored in tests/golden/rr_ref_random.json."""
     rng = random.Random(5)
+    out = []
     for _ in range(300):
         m = rng.choice([1, 5, 63, 64, 65, 100, 128, 129, 300, 700])
         unit = bytes(rng.choice(b"ACGT") for _ in range(m))
@@ -58,8 +58,20 @@ def test_oracle_against_the_reference_library_when_present():
         if rng.random() < 0.7:
             cut = rng.randrange(m + 1)
             read += unit[:cut] + bytes(rng.choice(b"ACGT") for _ in range(rng.randint(0, 5))) + unit[cut:]
-        k = rng.choice([-1, 0, 3, m // 10, m // 4, m])
-        assert rr.distance(unit, read, k) == rr.ref_distance(unit, read, k)
+        out.append((unit, read, rng.choice([-1, 0, 3, m // 10, m // 4, m])))
+    return out
+
+
+def test_oracle_against_the_reference_library_when_present():
+    """The reference's own edit distances of the random cases, stored by tests/golden/make_golden_rr.py; the library itself as
+    well when oracle/_ref holds it."""
+    with open(os.path.join(ROOT, "tests", "golden", "rr_ref_random.json")) as f:
+        want = json.load(f)["ref_distance"]
+    cases = random_cases()
+    assert len(want) == len(cases)
+    for (unit, read, k), d in zip(cases, want):
+        assert rr.distance(unit, read, k) == d
+        assert rr.ref_distance(unit, read, k) in (None, d)
 
 
 def test_kernel_source_on_the_host_emulator(emu_lib):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Developer tool: throughput of cf_rr_distances (read recruitment) on synthetic HOR reads plus as
-many random reads (`bench.py --rr` reports the same with the CPU baseline beside it).
+many random reads (`bench.py --full --rr` reports the same with the CPU baseline beside it).
 usage: tools/rr_bench.py <reads>"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
