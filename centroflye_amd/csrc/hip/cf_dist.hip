@@ -1351,7 +1351,11 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
         // Round 6: the list of slots that reach min_cov (one returning LDS add, a wait and a readfirstlane per drain that has one — on
         // cenX-shaped reads every drain has a dozen) is not kept for a first k-mer that would overflow it anyway: its filter scans the count
         // fields, as it did all along once the list was full (12 of 108 ms there)
+#if defined(CF_DIST_DIAG_NOHOT)
+        const bool use_hot = false;      // (diagnostic build: no first k-mer keeps the list — the filter must scan, not read an empty list)
+#else
         const bool use_hot = n_ent_a <= A.hot_entries;
+#endif
         // this wave's item records: one coalesced load, in flight while the sketch is cleared; both sweeps run on them
         const uint32_t per_w = (n_items + nw - 1u) / nw;
         const uint32_t mine = CF_DIST_ITEMS_BLOCKED ? (n_items > wv * per_w ? min(per_w, n_items - wv * per_w) : 0u) : (wv < n_items ? (n_items - wv + nw - 1u) / nw : 0u);
@@ -1501,7 +1505,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
                 uint32_t hcur = 0, hend = 0;      // wave-uniform: this wave's block of the hot list [hcur, hend)
 #define CF_DIST_HOT(SLOT) {                                                                                   \
                     const unsigned long long hm_ = cf_ballot((SLOT) != 0xFFFFFFFFu);                           \
-                    if (hm_) {                                                                                \
+                    if (hm_ && use_hot) {      /* (a first k-mer without the list leaves the cursor at 0: its filter scans from there) */ \
                         const uint32_t hn_ = (uint32_t)__popcll(hm_), room_ = hend - hcur;                    \
                         uint32_t hp_ = hcur + cf_rank_in(hm_);                                                \
                         if (hn_ > room_) {      /* (wave-uniform) the rest goes to a new block of 64: entries the wave never fills stay 0xFFFF */ \

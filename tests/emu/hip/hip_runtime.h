@@ -263,6 +263,7 @@ inline int __ffsll(long long v) { return __builtin_ffsll(v); }
 inline int __clz(int v) { return v ? __builtin_clz((unsigned)v) : 32; }
 inline int __clzll(long long v) { return v ? __builtin_clzll((unsigned long long)v) : 64; }
 inline void __builtin_amdgcn_s_sleep(int) {}
+inline unsigned long long __builtin_amdgcn_s_memtime() { static unsigned long long t = 0; return ++t; }   // (the -DCF_DIST_STAMPS build's clock: a counter here)
 
 
 // atomics (single OS thread: plain RMW)

@@ -13,9 +13,13 @@ def sorted_edges(e):
     return e[np.lexsort((e[:, 2], e[:, 1], e[:, 0]))]
 
 
-def check_stage2(engine, report_path, oracle_tuple, n_parts=1, check_table=True):
-    """A1..A6 of one fixture; oracle_tuple from the oracle_stage2 fixture."""
+def check_stage2(engine, report_path, oracle_tuple, n_parts=1, check_table=True, rel_threshold=0.8):
+    """A1..A6 of one fixture; oracle_tuple from the oracle_stage2 fixture (whose edges are those of the threshold 0.8: another
+    rel_threshold filters the oracle's (a, b, d) histogram again).  Returns the parsed report."""
     records, alns, lens, res, p2 = oracle_tuple
+    want_edges, want_unique = res["edges"], res["unique"]
+    if rel_threshold != 0.8:
+        want_edges, want_unique = recruit.filter_edges(*res["hist"], p2["min_coverage"], rel_threshold)
     pk = _host.parse_report(report_path)
     engine.load(pk, 1)
     engine.count_kmers(p2["k"])
@@ -41,7 +45,7 @@ def check_stage2(engine, report_path, oracle_tuple, n_parts=1, check_table=True)
     E = 0
     for part in range(n_parts):
         ne = engine.dist_edges(p2["min_nreads"], p2["max_nreads"], p2["min_distance"], p2["max_distance"],
-                               p2["min_coverage"], 0.8, part, n_parts, edge_cap=res["edges"].shape[0] + 8)
+                               p2["min_coverage"], rel_threshold, part, n_parts, edge_cap=want_edges.shape[0] + 8)
         parts.append(engine.edges(ne))
         from oracle import cport
         assert engine.edges_checksum() == cport.edge_checksum(parts[-1]), "cf_edges_checksum (device) vs the rows"
@@ -51,9 +55,9 @@ def check_stage2(engine, report_path, oracle_tuple, n_parts=1, check_table=True)
         E += engine.stats()["n_emissions"]
     ed = sorted_edges(np.concatenate(parts))
     assert E == cn["E"], "pair emissions"
-    assert np.array_equal(ed, res["edges"]), "A5+A6 selected edges"
-    assert np.array_equal(np.flatnonzero(engine.unique_mask()), res["unique"]), "A6 unique k-mers"
-    assert engine.stats()["n_unique"] == res["unique"].size
+    assert np.array_equal(ed, want_edges), "A5+A6 selected edges"
+    assert np.array_equal(np.flatnonzero(engine.unique_mask()), want_unique), "A6 unique k-mers"
+    assert engine.stats()["n_unique"] == want_unique.size
     return pk
 
 
@@ -83,10 +87,32 @@ def check_stage3(engine, pk, records, alns, lens, genomic_kmers, p3, expect_line
     return lines
 
 
-def check_synthetic_clouds(engine, n_reads=3, n_units=100, cloud=6, n_kmers=40, seed=0, min_d=1, max_d=150, min_cov=2, kmer_base=0):
+def check_clouds(engine, unit_ptr, cloud_ptr, entries, n_kmers, min_d, max_d, min_cov, rel_threshold=0.8):
+    """A5 + A6 of the device on given clouds (cf_set_clouds; read i has the units unit_ptr[i] .. unit_ptr[i + 1]) against the
+    oracle's histogram and filter (the dominance test as the reference does it: Python's int / int against the threshold).
+    Returns the oracle's edges (d, a, b, cnt), sorted."""
+    n_reads = unit_ptr.size - 1
+    U = int(unit_ptr[-1])
+    a, b, d, cnt, E = recruit.dist_histogram(unit_ptr, cloud_ptr, entries, n_kmers, 0, n_reads, min_d, max_d)
+    edges, uniq = recruit.filter_edges(a, b, d, cnt, min_cov, rel_threshold)
+    zeros = np.zeros(U, np.int64)
+    engine.load_arrays(np.zeros(0, np.uint8), np.zeros(n_reads + 1, np.int64), unit_ptr, zeros, zeros)
+    engine.set_kmers(np.arange(n_kmers, dtype=np.uint64), 19)
+    engine.set_clouds(cloud_ptr, entries)
+    engine.reset_unique()
+    ne = engine.dist_edges(0, n_reads, min_d, max_d, min_cov, rel_threshold, 0, 1, edge_cap=edges.shape[0] + 8)
+    assert engine.stats()["n_emissions"] == E
+    assert np.array_equal(sorted_edges(engine.edges(ne)), edges), f"selected edges at rel_threshold {rel_threshold!r}"
+    assert np.array_equal(np.flatnonzero(engine.unique_mask()), uniq)
+    return edges
+
+
+def check_synthetic_clouds(engine, n_reads=3, n_units=100, cloud=6, n_kmers=40, seed=0, min_d=1, max_d=150, min_cov=2, kmer_base=0, rel_threshold=0.8):
     """Distance stage on hand-made clouds (cf_set_clouds): k-mer 0 sits in EVERY unit, so its posting list
     (n_reads * n_units entries) exceeds the kernel's per-chunk posting capacity and the multi-chunk path runs.
-    kmer_base > 0: the other k-mers get the ranks kmer_base + 1 .. (a set of kmer_base + n_kmers k-mers: ranks beyond 24 bits)."""
+    kmer_base > 0: the other k-mers get the ranks kmer_base + 1 .. (a set of kmer_base + n_kmers k-mers: ranks beyond 24 bits).
+    (Random clouds spread every pair over many distances: at the default threshold hardly a pair is dominant — the sizes
+    above select no edge at all; tie_clouds below are the clouds that do.)  Returns the oracle's edges."""
     rng = np.random.default_rng(seed)
     unit_ptr = np.arange(n_reads + 1, dtype=np.int64) * n_units
     U = n_reads * n_units
@@ -99,17 +125,61 @@ def check_synthetic_clouds(engine, n_reads=3, n_units=100, cloud=6, n_kmers=40, 
     if kmer_base:
         entries = np.where(entries > 0, entries + kmer_base, 0).astype(np.int32)
         n_kmers += kmer_base
-    a, b, d, cnt, E = recruit.dist_histogram(unit_ptr, cloud_ptr, entries, n_kmers, 0, n_reads, min_d, max_d)
-    edges, uniq = recruit.filter_edges(a, b, d, cnt, min_cov)
-    zeros = np.zeros(U, np.int64)
-    engine.load_arrays(np.zeros(0, np.uint8), np.zeros(n_reads + 1, np.int64), unit_ptr, zeros, zeros)
-    engine.set_kmers(np.arange(n_kmers, dtype=np.uint64), 19)
-    engine.set_clouds(cloud_ptr, entries)
-    engine.reset_unique()
-    ne = engine.dist_edges(0, n_reads, min_d, max_d, min_cov, 0.8, 0, 1, edge_cap=edges.shape[0] + 8)
-    assert engine.stats()["n_emissions"] == E
-    assert np.array_equal(sorted_edges(engine.edges(ne)), edges)
-    assert np.array_equal(np.flatnonzero(engine.unique_mask()), uniq)
+    return check_clouds(engine, unit_ptr, cloud_ptr, entries, n_kmers, min_d, max_d, min_cov, rel_threshold)
+
+
+# dominance ties: (cnt, total) of the pair's dominant distance.  cnt / total is EXACTLY the threshold of its row
+# (Python: 3 / 10 == 0.3, 7 / 10 == 0.7 ...); 7 / 10 and 9 / 10 divided in single precision fall below theirs.
+TIE_RATIOS = ((0.5, 3, 6), (0.6, 3, 5), (0.75, 3, 4), (0.3, 3, 10), (1.0, 4, 4), (0.8, 4, 5), (0.7, 7, 10), (0.9, 9, 10))
+TIE_MIN_COV = 2
+TIE_MAX_D = 12
+
+
+def tie_clouds(copies=1):
+    """Clouds whose (a, b) pairs meet the thresholds of TIE_RATIOS exactly — and one count short of it — at distances 1 ..
+    TIE_MAX_D.  A pair (a, b) with counts c_d at the distances d is c_d reads of d + 1 units: a in the first unit's cloud, b in
+    the last one's, the units between empty; the dominant distance holds cnt, the rest of the total lies in counts of 1 (below
+    TIE_MIN_COV) at other distances.  copies > 1 repeats every read (each pair's counts times copies: the same ratios).
+    Returns (unit_ptr, cloud_ptr, entries, n_kmers, pairs): pairs[i] = (a, b, d, cnt, total, thr, tie)."""
+    reads, pairs = [], []
+    nxt = 0
+    for i, (thr, cnt, total) in enumerate(TIE_RATIOS):
+        for tie in (True, False):
+            c = cnt if tie else cnt - 1
+            a, b = nxt, nxt + 1
+            nxt += 2
+            d_dom = 1 + (2 * i + (not tie)) % TIE_MAX_D
+            others = [d for d in range(1, TIE_MAX_D + 1) if d != d_dom][:total - c]
+            assert len(others) == total - c
+            pairs.append((a, b, d_dom, c * copies, total * copies, thr, tie))
+            reads += [(a, b, d_dom)] * (c * copies) + [(a, b, d) for d in others for _ in range(copies)]
+    unit_ptr, cloud_ptr, entries = [0], [0], []
+    for a, b, d in reads:
+        for u in range(d + 1):
+            if u == 0:
+                entries.append(a)
+            elif u == d:
+                entries.append(b)
+            cloud_ptr.append(len(entries))
+        unit_ptr.append(unit_ptr[-1] + d + 1)
+    return (np.array(unit_ptr, np.int64), np.array(cloud_ptr, np.int64), np.array(entries, np.int32), nxt, pairs)
+
+
+def check_tie_clouds(engine, rel_threshold, copies=1):
+    """tie_clouds through the device at one threshold, against the oracle; asserts that the case is not vacuous: a pair whose
+    dominant count meets the threshold exactly is selected (where the threshold is one of TIE_RATIOS), the pair one count short
+    is not, no pair is selected above 1, every count >= TIE_MIN_COV is at or below 0."""
+    unit_ptr, cloud_ptr, entries, n_kmers, pairs = tie_clouds(copies)
+    edges = check_clouds(engine, unit_ptr, cloud_ptr, entries, n_kmers, 1, TIE_MAX_D, TIE_MIN_COV * copies, rel_threshold)
+    got = {(int(a), int(b), int(d)): int(c) for d, a, b, c in edges}
+    for a, b, d, cnt, total, thr, tie in pairs:
+        if thr == rel_threshold:
+            assert got.get((a, b, d)) == (cnt if tie else None), (a, b, d, cnt, total, thr, tie, rel_threshold)
+    if rel_threshold > 1.0:
+        assert not got
+    if rel_threshold <= 0.0:
+        assert len(got) == sum(1 for p in pairs if p[3] >= TIE_MIN_COV * copies) > 0
+    return edges
 
 
 def check_unit_kmers(engine, report_path, golden_entry, k):

@@ -1,0 +1,102 @@
+"""The A/B builds of the distance kernel (cf_dist.hip's compile-time switches, timed against the default by tools/build_variant.sh
+and tools/dist_ab.py) compute what the default build computes — checked on the host emulator, each build in a process of its own
+(a build that writes out of bounds fails its test instead of the suite).  Every build runs the dominance-tie clouds, the random
+clouds of pathcheck.check_synthetic_clouds (a multi-chunk posting list, at a threshold that selects edges) and A1..A6 of the
+lowcov fixture, under knobs that force the rare paths (no hot list, no sketch, a small table) and under the defaults.
+
+Result-preserving builds, by their comments in cf_dist.hip / cf_count2.hip:
+  CF_DIST_HOTBLK=1          hot-list entries through per-wave blocks of 64 (round 5, measured slower and kept off)
+  CF_DIST_PUSH_FLAT=1       the table sweep's pushes without the per-step grouping
+  CF_DIST_SKETCH_BY_B=1     the counting sketch indexed by b alone (round 6, measured and kept off)
+  CF_DIST_PROBE_TWICE=1     a second straight-line probe before an insert is parked (round 6, kept off)
+  CF_DIST_FILLRD=0          the fill level read in front of every drain instead of inside it
+  CF_DIST_DRAIN2=0          drains of 64 queued inserts, one per lane
+  CF_DIST_OLD_DRAIN=1       the drain's probe as nested match / claim branches (rounds 2-3)
+  CF_DIST_ITEMS_BLOCKED=1   wave w sweeps a contiguous run of the item records instead of a round-robin share
+  CF_DIST_PF_A / _PF_B      loads in flight per lane in the sketch / table sweep
+  CF_NARROW_PB=8            8 keys per bucket of the 6-byte-slot layout
+  CF_DIST_STAMPS, CF_C2_STAMPS   per-phase clock sums of the distance / counting kernels (the host's clock is a counter)
+  CF_DIST_DIAG_NOHOT        no first k-mer keeps the hot list (the filter scans; it read an empty list and selected nothing before)
+  CF_DIST_DIAG_COUNT        counters of the parked inserts and drains, printed per launch
+Not here:
+  CF_DIST_ABL=n             removes the kernel's phases from the end (tools/dist_ablation.sh): wrong results by design
+  CF_DIST_DIAG_NOPARK       drops parked inserts (timing only): wrong results by design
+  CF_NO_BUFFER_LOAD         the emulator's own build defines it: every emulator test runs it
+  CF_DIST_LB_THREADS / _LB_BLOCKS   launch bounds (register allocation): the host build's code is the default's
+  CF_PL2_STAMPS / _STAMPS2  placement, not the distance stage (test_emu_kernels.py covers its kernels)"""
+import os
+import pickle
+import subprocess
+import sys
+from concurrent.futures import ThreadPoolExecutor
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+VARIANTS = {
+    "hotblk": ["-DCF_DIST_HOTBLK=1"],
+    "push_flat": ["-DCF_DIST_PUSH_FLAT=1"],
+    "sketch_by_b": ["-DCF_DIST_SKETCH_BY_B=1"],
+    "probe_twice": ["-DCF_DIST_PROBE_TWICE=1"],
+    "fillrd_off": ["-DCF_DIST_FILLRD=0"],
+    "drain2_off": ["-DCF_DIST_DRAIN2=0"],
+    "old_drain": ["-DCF_DIST_OLD_DRAIN=1"],
+    "items_blocked": ["-DCF_DIST_ITEMS_BLOCKED=1"],
+    "pf_a3": ["-DCF_DIST_PF_A=3"],
+    "pf_b2": ["-DCF_DIST_PF_B=2"],
+    "narrow_pb8": ["-DCF_NARROW_PB=8"],
+    "dist_stamps": ["-DCF_DIST_STAMPS"],
+    "c2_stamps": ["-DCF_C2_STAMPS"],
+    "diag_nohot": ["-DCF_DIST_DIAG_NOHOT"],
+    "diag_count": ["-DCF_DIST_DIAG_COUNT"],
+}
+# (knob settings, run the random clouds too)
+SETTINGS = [(dict(dist_hot_entries=0, dist_sketch=0, dist_slots=1024), True),
+            (dict(dist_slots=2048, dist_block=128), False)]
+RESET = dict(dist_hot_entries=32768, dist_sketch=1, dist_slots=0, dist_block=0)
+RUN = r"""
+import pickle, sys
+root, lib_path, report_path, oracle_path, settings, reset = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], eval(sys.argv[5]), eval(sys.argv[6])
+sys.path[:0] = [root, root + "/tests"]
+import pathcheck
+from centroflye_amd import _lib
+from centroflye_amd.engine import Engine
+tup = pickle.load(open(oracle_path, "rb"))
+e = Engine(0, _lib.load(lib_path))
+for knobs, clouds in settings:
+    for k, v in knobs.items():
+        e.set_param(k, v)
+    for thr in (0.8, 0.6, 0.0):
+        pathcheck.check_tie_clouds(e, thr)
+    if clouds:
+        assert pathcheck.check_synthetic_clouds(e, rel_threshold=0.05).shape[0] > 0
+    pathcheck.check_stage2(e, report_path, tup, check_table=False)
+    for k, v in reset.items():
+        e.set_param(k, v)
+print("VARIANT-OK")
+"""
+
+
+@pytest.fixture(scope="module")
+def results(emu_lib, report, oracle_stage2, tmp_path_factory):
+    oracle_path = str(tmp_path_factory.mktemp("variants") / "lowcov_d2.pkl")
+    with open(oracle_path, "wb") as f:
+        pickle.dump(oracle_stage2("lowcov", max_distance=2), f)
+    report_path = report("lowcov")
+
+    def one(name):
+        b = subprocess.run(["bash", os.path.join(ROOT, "tests", "emu", "build_emu.sh"), name] + VARIANTS[name], capture_output=True, text=True, timeout=900)
+        if b.returncode:
+            return "build failed: " + b.stderr[-3000:]
+        lib = os.path.join(ROOT, "tests", "emu", f"libcfhip_emu_{name}.so")
+        r = subprocess.run([sys.executable, "-c", RUN, ROOT, lib, report_path, oracle_path, repr(SETTINGS), repr(RESET)],
+                           capture_output=True, text=True, timeout=900)
+        return "ok" if r.returncode == 0 and "VARIANT-OK" in r.stdout else f"exit {r.returncode}: " + r.stdout[-2000:] + r.stderr[-3000:]
+
+    with ThreadPoolExecutor(max_workers=max(1, min(8, os.cpu_count() or 1))) as pool:
+        return dict(zip(VARIANTS, pool.map(one, VARIANTS)))
+
+
+@pytest.mark.parametrize("name", list(VARIANTS))
+def test_variant_build_computes_what_the_default_computes(results, name):
+    assert results[name] == "ok", f"{name} {VARIANTS[name]}: {results[name]}"

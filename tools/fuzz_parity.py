@@ -21,23 +21,26 @@ def arg(name, default, conv=int):
     return conv(sys.argv[sys.argv.index(name) + 1]) if name in sys.argv else default
 
 
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 100
-seed = arg("--seed", 1)
-budget = arg("--seconds", 10 ** 9, float)
-out = arg("--out", os.path.join(ROOT, "gpurun_out", "fuzz_parity.json"), str)
-only = arg("--only", -1)
-rng = np.random.default_rng(seed)
 BASE = dict(bigparity.P)
 KNOB_DEFAULTS = dict(dist_slots=0, dist_block=0, dist_wgs=0, dist_sketch=1, dist_wide=0, dist_regions=0, dist_region_bytes=0, dist_dbits=0, dist_hot_cap=0,
                      dist_post_atomics=0, dist_fill_pct=70, dist_stage=2048, dist_int_thr=1, count_mode=1, count_bits=0, comm_round_bytes=1 << 28,
-                     dist_hot_entries=32768, lut_shift=-1)
+                     dist_hot_entries=32768, lut_shift=-1, dist_sketch_bits=0, dist_est_pct=80, count_slots=4096, count_tile=16)
+# the values a knob case draws from (each knob with probability 0.18); every name and value here and in KNOB_DEFAULTS is one
+# cf_set_param takes on its own (tests/test_fuzz_generator.py): a refusal of a case is then a combination, never a typo
+KNOB_CHOICES = (("dist_slots", [256, 512, 2048, 4096]), ("dist_block", [64, 128, 256, 512, 1024]), ("dist_wgs", [1, 2, 3, 4]), ("dist_sketch", [0]),
+                ("dist_wide", [1]), ("dist_regions", [1, 2, 4, 8]), ("dist_region_bytes", [1]), ("dist_dbits", [5, 6, 7, 8]), ("dist_hot_cap", [1, 8, 64]),
+                ("dist_post_atomics", [1]), ("dist_fill_pct", [20, 50, 90]), ("dist_stage", [0, 64]), ("dist_int_thr", [0]), ("count_mode", [0]),
+                ("count_bits", [4, 9, 14]), ("dist_hot_entries", [-1, 0, 2000]), ("lut_shift", [0, 1, 3]), ("dist_sketch_bits", [4, 8]),
+                ("dist_est_pct", [5, 100]), ("count_slots", [256, 16384]), ("count_tile", [1, 64]))
 
 
-def draw_case():
+def draw_case(rng):
+    """One case from the generator rng: (synth kwargs, script parameters, partition, n_parts, device knobs)."""
     n_reads = int(rng.choice([int(x) for x in os.environ.get("CF_FUZZ_READS", "300,600,1200,2500,5000").split(",")]))
     unit_len = int(rng.choice([342, 1026, 2055, 3078]))
     sy = dict(seed=int(rng.integers(1, 1 << 30)), n_reads=n_reads, unit_len=unit_len, var_len=int(rng.choice([1, 8])),
-              mean_len=float(rng.choice([8000.0, 20000.0, 50000.0, 100000.0])),      # (round 6: 100 kb = the cenX shape, ~47 units per read) p_sub=float(rng.uniform(0.003, 0.04)), p_del=float(rng.uniform(0.003, 0.03)),
+              mean_len=float(rng.choice([8000.0, 20000.0, 50000.0, 100000.0])),      # (round 6: 100 kb = the cenX shape, ~47 units per read)
+              p_sub=float(rng.uniform(0.003, 0.04)), p_del=float(rng.uniform(0.003, 0.03)),
               p_ins=float(rng.uniform(0.003, 0.03)), unit_div=float(rng.uniform(0.003, 0.03)))
     # (pair emissions grow with the square of the units per read: long reads and short units only on small read sets, so that a case is
     # seconds of oracle time and the run is many cases)
@@ -64,69 +67,77 @@ def draw_case():
     part = int(rng.integers(0, n_parts))
     knobs = {}
     if rng.random() < 0.35:
-        for name, choices in (("dist_slots", [256, 512, 2048, 4096]), ("dist_block", [64, 128, 256, 512, 1024]), ("dist_wgs", [1, 2, 3, 4]), ("dist_sketch", [0]),
-                              ("dist_wide", [1]), ("dist_regions", [1, 2, 4, 8]), ("dist_region_bytes", [1]), ("dist_dbits", [5, 6, 7, 8]), ("dist_hot_cap", [1, 8, 64]),
-                              ("dist_post_atomics", [1]), ("dist_fill_pct", [20, 50, 90]), ("dist_stage", [0, 64]), ("dist_int_thr", [0]), ("count_mode", [0]),
-                              ("count_bits", [4, 9, 14]), ("dist_hot_entries", [-1, 0, 2000]), ("lut_shift", [0, 1, 3])):
+        for name, choices in KNOB_CHOICES:
             if rng.random() < 0.18:
                 knobs[name] = int(rng.choice(choices))
     return sy, p, part, n_parts, knobs
 
 
-recs, t_start = [], time.time()
-lib = None
-if os.environ.get("CF_LIB"):      # (another build of the device library, e.g. the host emulator for a dry run of this script)
-    from centroflye_amd import _lib
-    lib = _lib.load(os.environ["CF_LIB"])
-with Engine(0, lib) as e:
-    for i in range(n_cases):
-        if time.time() - t_start > budget:
-            break
-        sy, p, part, n_parts, knobs = draw_case()
-        exchange = bool(rng.random() < 0.25) and n_parts >= 2
-        rec = dict(case=i, synth=sy, params=p, partition=[part, n_parts], knobs=knobs, exchange=exchange)
-        if only >= 0 and i != only:      # (--only i: the i-th case of this seed alone)
-            continue
-        t0 = time.time()
-        try:
-            pk = _host.synth(**sy)
-            bigparity.P.clear(); bigparity.P.update(BASE); bigparity.P.update(p)
-            for kk, vv in KNOB_DEFAULTS.items():
-                e.set_param(kk, vv)
-            for kk, vv in knobs.items():
-                e.set_param(kk, vv)
-            # (a look at the size first, on the device: a case whose partition has more than 4e9 pair emissions or 2e8 edges is minutes of oracle time
-            # and gigabytes of edge rows — dropped, not run)
-            e.load(pk, 1); e.count_kmers(p["k"]); e.select_rare(p["max_nonuniq"], p["lo"], p["hi"]); e.build_clouds(); e.reset_unique()
-            ne0 = e.dist_edges(0, 2 ** 62, p["min_d"], p["max_d"], p["min_cov"], p["rel_threshold"], part, n_parts, edge_cap=0)
-            if e.stats()["n_emissions"] > 4e9 or ne0 > 2e8:
-                raise DeviceError(f"case too large (-12): {e.stats()['n_emissions']} pair emissions, {ne0} edges")
-            if exchange:
-                # the way ONE rank of n_parts runs its partition: A1 on its read shard, table exchange / rare gather / cloud gather through a one-rank
-                # communicator that sends to itself (bucketing, rounds of comm_round_bytes, merge, gathered view), A5 / A6 over the gathered view
-                e.set_param("comm_round_bytes", int(rng.choice([1 << 12, 1 << 16, 1 << 28])))
-                orec = bigparity.oracle_record(pk, part, n_parts)
-                x = bigparity.check_record(e, pk, orec, through_exchange=True, rendezvous=tempfile.mkdtemp() if lib else None)      # (the emulator's file transport meets in a directory)
-                e.set_param("comm_round_bytes", 1 << 28)
-                r = dict(identical=x["identical"], checks=x["checks"], n_rare=orec["n_rare"], n_emissions_partition=x["got"]["n_emissions_partition"],
-                         n_edges_partition=x["got"]["n_edges_partition"], n_dist_passes=x["got"]["n_dist_passes"], n_bases=orec["n_bases"],
-                         dist_kernel_ms=x["got"]["dist_kernel_ms"], oracle_A1_A3_s=orec["oracle_A1_A3_s"], oracle_partition_s=orec["partition"]["oracle_s"])
-            else:
-                r = bigparity.check(e, pk, part=part, n_parts=n_parts)
-            rec.update(identical=bool(r["identical"]), checks=r["checks"], n_rare=r["n_rare"], n_emissions=r["n_emissions_partition"], n_edges=r["n_edges_partition"],
-                       passes=r["n_dist_passes"], n_bases=r["n_bases"], dist_kernel_ms=r["dist_kernel_ms"], oracle_s=round(r["oracle_A1_A3_s"] + r["oracle_partition_s"], 1),
-                       device_ms={k: round(float(v), 1) for k, v in e.times().items() if k.endswith("_ms") and v})
-        except DeviceError as ex:
-            refused = "(-22)" in str(ex) or "(-12)" in str(ex)      # (a knob combination the library does not take; a case too large for the device)
-            rec.update(identical=None if refused else False, refused=str(ex)[:200])
-        rec["s"] = round(time.time() - t0, 2)
-        recs.append(rec)
-        print(json.dumps({k: rec.get(k) for k in ("case", "identical", "refused", "params", "partition", "exchange", "knobs", "n_rare", "n_emissions", "n_edges", "passes", "dist_kernel_ms", "oracle_s", "s")}), flush=True)
-        if rec["identical"] is False:
-            print("DIFFERENCE:", json.dumps(rec), flush=True)
-bad = [r for r in recs if r["identical"] is False]
-summary = dict(seed=seed, cases=len(recs), identical=sum(1 for r in recs if r["identical"]), refused=sum(1 for r in recs if r["identical"] is None), different=len(bad),
-               with_edges=sum(1 for r in recs if r.get("n_edges")), through_exchange=sum(1 for r in recs if r.get("exchange") and r["identical"]), pair_emissions=int(sum(r.get("n_emissions") or 0 for r in recs)), seconds=round(time.time() - t_start, 1))
-json.dump(dict(summary=summary, cases=recs), open(out, "w"), indent=1)
-print(json.dumps(summary))
-sys.exit(1 if bad else 0)
+def main():
+    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 100
+    seed = arg("--seed", 1)
+    budget = arg("--seconds", 10 ** 9, float)
+    out = arg("--out", os.path.join(ROOT, "gpurun_out", "fuzz_parity.json"), str)
+    only = arg("--only", -1)
+    rng = np.random.default_rng(seed)
+    recs, t_start = [], time.time()
+    lib = None
+    if os.environ.get("CF_LIB"):      # (another build of the device library, e.g. the host emulator for a dry run of this script)
+        from centroflye_amd import _lib
+        lib = _lib.load(os.environ["CF_LIB"])
+    with Engine(0, lib) as e:
+        for i in range(n_cases):
+            if time.time() - t_start > budget:
+                break
+            sy, p, part, n_parts, knobs = draw_case(rng)
+            exchange = bool(rng.random() < 0.25) and n_parts >= 2
+            rec = dict(case=i, synth=sy, params=p, partition=[part, n_parts], knobs=knobs, exchange=exchange)
+            if only >= 0 and i != only:      # (--only i: the i-th case of this seed alone)
+                continue
+            t0 = time.time()
+            try:
+                pk = _host.synth(**sy)
+                bigparity.P.clear(); bigparity.P.update(BASE); bigparity.P.update(p)
+                for kk, vv in KNOB_DEFAULTS.items():
+                    e.set_param(kk, vv)
+                for kk, vv in knobs.items():
+                    e.set_param(kk, vv)
+                # (a look at the size first, on the device: a case whose partition has more than 4e9 pair emissions or 2e8 edges is minutes of oracle time
+                # and gigabytes of edge rows — dropped, not run)
+                e.load(pk, 1); e.count_kmers(p["k"]); e.select_rare(p["max_nonuniq"], p["lo"], p["hi"]); e.build_clouds(); e.reset_unique()
+                ne0 = e.dist_edges(0, 2 ** 62, p["min_d"], p["max_d"], p["min_cov"], p["rel_threshold"], part, n_parts, edge_cap=0)
+                if e.stats()["n_emissions"] > 4e9 or ne0 > 2e8:
+                    raise DeviceError(f"case too large (-12): {e.stats()['n_emissions']} pair emissions, {ne0} edges")
+                if exchange:
+                    # the way ONE rank of n_parts runs its partition: A1 on its read shard, table exchange / rare gather / cloud gather through a one-rank
+                    # communicator that sends to itself (bucketing, rounds of comm_round_bytes, merge, gathered view), A5 / A6 over the gathered view
+                    e.set_param("comm_round_bytes", int(rng.choice([1 << 12, 1 << 16, 1 << 28])))
+                    orec = bigparity.oracle_record(pk, part, n_parts)
+                    x = bigparity.check_record(e, pk, orec, through_exchange=True, rendezvous=tempfile.mkdtemp() if lib else None)      # (the emulator's file transport meets in a directory)
+                    e.set_param("comm_round_bytes", 1 << 28)
+                    r = dict(identical=x["identical"], checks=x["checks"], n_rare=orec["n_rare"], n_emissions_partition=x["got"]["n_emissions_partition"],
+                             n_edges_partition=x["got"]["n_edges_partition"], n_dist_passes=x["got"]["n_dist_passes"], n_bases=orec["n_bases"],
+                             dist_kernel_ms=x["got"]["dist_kernel_ms"], oracle_A1_A3_s=orec["oracle_A1_A3_s"], oracle_partition_s=orec["partition"]["oracle_s"])
+                else:
+                    r = bigparity.check(e, pk, part=part, n_parts=n_parts)
+                rec.update(identical=bool(r["identical"]), checks=r["checks"], n_rare=r["n_rare"], n_emissions=r["n_emissions_partition"], n_edges=r["n_edges_partition"],
+                           passes=r["n_dist_passes"], n_bases=r["n_bases"], dist_kernel_ms=r["dist_kernel_ms"], oracle_s=round(r["oracle_A1_A3_s"] + r["oracle_partition_s"], 1),
+                           device_ms={k: round(float(v), 1) for k, v in e.times().items() if k.endswith("_ms") and v})
+            except DeviceError as ex:
+                refused = "(-22)" in str(ex) or "(-12)" in str(ex)      # (a knob combination the library does not take; a case too large for the device)
+                rec.update(identical=None if refused else False, refused=str(ex)[:200])
+            rec["s"] = round(time.time() - t0, 2)
+            recs.append(rec)
+            print(json.dumps({k: rec.get(k) for k in ("case", "identical", "refused", "params", "partition", "exchange", "knobs", "n_rare", "n_emissions", "n_edges", "passes", "dist_kernel_ms", "oracle_s", "s")}), flush=True)
+            if rec["identical"] is False:
+                print("DIFFERENCE:", json.dumps(rec), flush=True)
+    bad = [r for r in recs if r["identical"] is False]
+    summary = dict(seed=seed, cases=len(recs), identical=sum(1 for r in recs if r["identical"]), refused=sum(1 for r in recs if r["identical"] is None), different=len(bad),
+                   with_edges=sum(1 for r in recs if r.get("n_edges")), through_exchange=sum(1 for r in recs if r.get("exchange") and r["identical"]), pair_emissions=int(sum(r.get("n_emissions") or 0 for r in recs)), seconds=round(time.time() - t_start, 1))
+    json.dump(dict(summary=summary, cases=recs), open(out, "w"), indent=1)
+    print(json.dumps(summary))
+    sys.exit(1 if bad else 0)
+
+
+if __name__ == "__main__":
+    main()
