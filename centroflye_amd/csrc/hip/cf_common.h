@@ -230,7 +230,11 @@ extern "C" int cf_comm_free(cf_ctx* ctx);   // cf_exchange.hip
 // primitives (cf_prims.hip)
 int cf_scan_exclusive_i64(cf_ctx* ctx, const int64_t* d_in, int64_t* d_out, int64_t n, int64_t* total);
 int cf_scan_exclusive_u32_to_i64(cf_ctx* ctx, const uint32_t* d_in, int64_t* d_out, int64_t n, int64_t* total);
-// LSD radix sort of 64-bit keys on `bits` low bits; result lands in d_keys (d_tmp is scratch)
+// exclusive scan, in (digit, tile) order, of a tile-major digit histogram hist[tile * D + digit] (D <= 512) -> offs in the
+// same layout; *d_total = the sum (device; may be null).  d_part, d_base: scratch of cf_tile_digit_chunks(n_tiles) * D entries.
+int cf_tile_digit_chunks(int n_tiles);
+int cf_tile_digit_offsets(cf_ctx* ctx, const uint32_t* d_hist, int n_tiles, int D, int64_t* d_offs, int64_t* d_total, uint32_t* d_part, int64_t* d_base);
+// stable LSD radix sort of 64-bit keys on the whole bytes that hold the `bits` low bits; result lands in d_keys (d_tmp is scratch)
 int cf_radix_sort_u64(cf_ctx* ctx, unsigned long long* d_keys, unsigned long long* d_tmp, int64_t n, int bits);
 int cf_radix_sort_u64_any(cf_ctx* ctx, unsigned long long* d_keys, unsigned long long* d_tmp, int64_t n, int bits, unsigned long long** result);
 int cf_radix_sort_rec16(cf_ctx* ctx, void* d_recs, void* d_tmp, int64_t n, const int* words, const int* bits, int n_fields);

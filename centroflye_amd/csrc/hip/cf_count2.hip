@@ -17,11 +17,11 @@
 // All traffic is streamed: N_b x 2 + 8 N_w x 5 + 16 K_dist bytes (~45 GB per Gbase).  Needs 2k + bits(reads) <= 64 and
 // reads < 2^27; otherwise the table path of cf_count.hip runs.  cf_count_occurrences takes the same passes with records that
 // are the k-mer alone and its own reduce kernel (cf_c2_reduce_occ_kernel below).
-#include "cf_common.h"
+#include "cf_radix.h"
 
 void cf_free_table(cf_ctx* c);
 
-#define C2_THREADS 256
+#define C2_THREADS CF_RX_THREADS
 #define C2_ITEMS 16                         /* windows (pass 1) / records (later passes) per thread and tile */
 #define C2_TILE (C2_THREADS * C2_ITEMS)
 #define C2_MAXBITS 9                        /* radix bits per pass */
@@ -45,20 +45,6 @@ __device__ __forceinline__ uint32_t cf_c2_fold(unsigned long long x) { const uin
 __device__ __forceinline__ uint32_t cf_c2_bucket(unsigned long long kmer, int bits) { uint32_t h = cf_c2_fold(kmer); h ^= h >> 15; h *= 0x9E3779B1u; h ^= h >> 13; h *= 0xC2B2AE35u; return h >> (32 - bits); }
 __device__ __forceinline__ uint32_t cf_c2_hash_set(unsigned long long rec) { uint32_t h = cf_c2_fold(rec); h ^= h >> 16; h *= 0x7FEB352Du; return h ^ (h >> 15); }
 __device__ __forceinline__ uint32_t cf_c2_hash_tab(unsigned long long kmer) { uint32_t h = cf_c2_fold(kmer); h ^= h >> 14; h *= 0x846CA68Bu; return h ^ (h >> 16); }
-
-// ---- stable ranking of one round (one record per thread) by digit, as in cf_radix_scatter (cf_prims.hip)
-struct cf_c2_rank { uint32_t rank, count; };
-template <int NB>
-__device__ __forceinline__ cf_c2_rank cf_c2_wave_rank(uint32_t digit, bool valid, int lane) {
-    unsigned long long peers = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        const int bit = (digit >> b) & 1;
-        const unsigned long long m = __ballot(bit);
-        peers &= bit ? m : ~m;
-    }
-    return cf_c2_rank{(uint32_t)__popcll(peers & ((1ull << lane) - 1ull)), (uint32_t)__popcll(peers)};
-}
 
 // windows of a pass-1 tile -> records, 16 consecutive windows per thread (rolled); calls f(j, record, valid) for j < 16.
 // The tile's bases come in as aligned 32-bit words (`a` = the tile's first base's offset in its word, uniform) and are
@@ -144,54 +130,6 @@ cf_c2_hist1_kernel(const uint8_t* __restrict__ bases, int64_t n_bases, const int
     }
 }
 
-// Stable scatter of one tile.  The tile's order is wave-major: wave w holds the records [w * 64 * C2_ITEMS, ...) of the
-// tile, C2_ITEMS rounds of 64.  A wave ranks its own records by itself — per round a ballot match per digit bit, across
-// rounds a running count per digit in the wave's private LDS row — so the workgroup meets only twice per tile: to turn
-// the rows into exclusive offsets across waves, and before the rows are reused.
-//   rank_[j]  rank of the thread's j-th record among the records of its wave with the same digit (filled by cf_c2_rank_round)
-template <int NB>
-__device__ __forceinline__ uint32_t cf_c2_rank_round(uint32_t digit, bool valid, uint32_t* wrow) {     // wrow: this wave's 1 << NB counters
-    const int lane = threadIdx.x & 63;
-    const cf_c2_rank rk = cf_c2_wave_rank<NB>(digit, valid, lane);
-    uint32_t before = 0;
-    if (valid) before = wrow[digit];                       // records of earlier rounds (only this wave writes the row; LDS ops of a wave are in order)
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (valid && rk.rank == 0) wrow[digit] = before + rk.count;
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    return before + rk.rank;
-}
-// after all rounds: wcount rows -> exclusive prefix over the waves (in place), dstart[d] = first position of digit d in
-// the tile sorted by digit (exclusive scan of the tile's digit counts; 1 << NB <= 2 * C2_THREADS)
-template <int NB, int ROWS = C2_THREADS / 64>
-__device__ __forceinline__ void cf_c2_tile_bases(uint32_t* dstart, uint32_t* wcount, uint32_t* scan_tmp) {
-    __syncthreads();
-    const int t = threadIdx.x;
-    uint32_t tot[2] = {0, 0};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int d = 2 * t + h;
-        if (d < (1 << NB)) {
-            uint32_t s = 0;
-            for (int w = 0; w < ROWS; ++w) { const uint32_t c = wcount[w * (1 << NB) + d]; wcount[w * (1 << NB) + d] = s; s += c; }
-            tot[h] = s;
-        }
-    }
-    // exclusive scan of tot over the threads (2 digits each)
-    const int lane = t & 63, wave = t >> 6;
-    uint32_t inc = tot[0] + tot[1];
-    const uint32_t mine = inc;
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, (unsigned)d); if (lane >= d) inc += o; }
-    if (lane == 63) scan_tmp[wave] = inc;
-    __syncthreads();
-    uint32_t off = inc - mine;
-    for (int w = 0; w < wave; ++w) off += scan_tmp[w];
-    if (2 * t < (1 << NB)) dstart[2 * t] = off;
-    if (2 * t + 1 < (1 << NB)) dstart[2 * t + 1] = off + tot[0];
-    if (t == C2_THREADS - 1) scan_tmp[7] = off + mine;          // records of the tile
-    __syncthreads();
-}
 // records staged in digit order -> global: consecutive threads write consecutive addresses inside a digit's run
 template <int NB>
 __device__ __forceinline__ void cf_c2_copy_out(const unsigned long long* stage_recs, uint32_t n_tile, const uint32_t* dstart, const int64_t* gbase,
@@ -204,7 +142,7 @@ __device__ __forceinline__ void cf_c2_copy_out(const unsigned long long* stage_r
     }
 }
 
-// pass 1, scatter: offs = exclusive scan of hist in (digit, tile) order (cf_c2_col* below).  The windows of a tile belong to ONE read, so their order inside the tile
+// pass 1, scatter: offs = exclusive scan of hist in (digit, tile) order (cf_tile_digit_offsets, cf_prims.hip).  The windows of a tile belong to ONE read, so their order inside the tile
 // is free: a record's rank among the tile's records with its digit is what a returning LDS add hands out (the ballot
 // ranking of the later passes, which keeps the order, costs ~45 instructions per record); the digit is kept next to the
 // staged record for the copy-out.
@@ -233,7 +171,7 @@ cf_c2_scatter1_kernel(const uint8_t* __restrict__ bases, int64_t n_bases, const 
             rec_[j] = rec; ok |= (uint32_t)valid << j;
             rd_[j] = (valid ? atomicAdd(&cnt[d], 1u) : 0u) | (d << 16);
         });
-        cf_c2_tile_bases<NB, 1>(dstart, cnt, scan_tmp);       // (leaves the counters at 0 for the next tile)
+        cf_rx_tile_bases<NB, 1>(dstart, cnt, scan_tmp);       // (leaves the counters at 0 for the next tile)
 #pragma unroll
         for (int j = 0; j < C2_ITEMS; ++j)
             if ((ok >> j) & 1u) { const uint32_t d = rd_[j] >> 16, at = dstart[d] + (rd_[j] & 0xFFFFu); srec[at] = rec_[j]; sdig[at] = (uint16_t)d; }
@@ -267,6 +205,7 @@ cf_c2_hist_kernel(const unsigned long long* __restrict__ in, int64_t n, int n_ti
     }
 }
 
+// stable scatter of one tile: wave-major ranking (cf_radix.h), records staged in LDS in digit order, copied out in runs
 template <int NB>
 __global__ void __launch_bounds__(C2_THREADS)
 cf_c2_scatter_kernel(const unsigned long long* __restrict__ in, int64_t n, int n_tiles, int rb, int bits, int shift, const int64_t* __restrict__ offs,
@@ -291,8 +230,8 @@ cf_c2_scatter_kernel(const unsigned long long* __restrict__ in, int64_t n, int n
         for (int j = 0; j < C2_ITEMS; ++j) { const int64_t i = base + (int64_t)j * 64; rec_[j] = i < n ? in[i] : 0ull; }
 #pragma unroll
         for (int j = 0; j < C2_ITEMS; ++j)
-            rank_[j] = cf_c2_rank_round<NB>((cf_c2_bucket(rec_[j] >> rb, bits) >> shift) & mask, base + (int64_t)j * 64 < n, wcount + wave * D);
-        cf_c2_tile_bases<NB>(dstart, wcount, scan_tmp);
+            rank_[j] = cf_rx_rank_round<NB>((cf_c2_bucket(rec_[j] >> rb, bits) >> shift) & mask, base + (int64_t)j * 64 < n, wcount + wave * D);
+        cf_rx_tile_bases<NB>(dstart, wcount, scan_tmp);
 #pragma unroll
         for (int j = 0; j < C2_ITEMS; ++j)
             if (base + (int64_t)j * 64 < n) { const uint32_t d = (cf_c2_bucket(rec_[j] >> rb, bits) >> shift) & mask; srec[dstart[d] + wcount[wave * D + d] + rank_[j]] = rec_[j]; }
@@ -300,73 +239,7 @@ cf_c2_scatter_kernel(const unsigned long long* __restrict__ in, int64_t n, int n
         __syncthreads();
         cf_c2_copy_out<NB>(srec, n_tile, dstart, gbase, rb, bits, shift, out);
         __syncthreads();
-        for (int d = threadIdx.x; d < (C2_THREADS / 64) * D; d += C2_THREADS) wcount[d] = 0;
-    }
-}
-
-// ---- offsets of a pass: offs[tile][d] = records with a smaller digit + records of digit d in earlier tiles = the exclusive scan
-// of hist in (digit, tile) order, computed on the tile-major arrays by columns: (1) column sums of chunks of C2_SCAN_CHUNK
-// tiles, (2) one workgroup turns them into the chunks' bases (column totals, scan over the digits, running sums down the
-// chunks), (3) every chunk walks its tiles again.  All accesses are runs of D counters; the loads of a walk do not depend on
-// its running sum and are issued eight at a time.
-#define C2_SCAN_CHUNK 512
-#define C2_SCAN_THREADS 512                 /* >= 1 << C2_MAXBITS: a thread per digit */
-__global__ void __launch_bounds__(C2_SCAN_THREADS)
-cf_c2_colsum_kernel(const uint32_t* __restrict__ hist, int n_tiles, int D, uint32_t* __restrict__ part) {
-    const int d = threadIdx.x;
-    if (d >= D) return;
-    const int t0 = blockIdx.x * C2_SCAN_CHUNK, t1 = min(n_tiles, t0 + C2_SCAN_CHUNK);
-    uint32_t acc = 0;
-    for (int t = t0; t < t1; t += 8) {
-        uint32_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = t + u < t1 ? hist[(int64_t)(t + u) * D + d] : 0u;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += v[u];
-    }
-    part[(int64_t)blockIdx.x * D + d] = acc;
-}
-__global__ void __launch_bounds__(C2_SCAN_THREADS)
-cf_c2_colbase_kernel(const uint32_t* __restrict__ part, int n_chunks, int D, int64_t* __restrict__ base, int64_t* __restrict__ total_out) {
-    long long* sh = (long long*)cf_lds;                       // C2_SCAN_THREADS / 64 wave totals
-    const int d = threadIdx.x, lane = d & 63, wave = d >> 6;
-    long long tot = 0;
-    if (d < D)
-        for (int c = 0; c < n_chunks; c += 8) {
-            uint32_t v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = c + u < n_chunks ? part[(int64_t)(c + u) * D + d] : 0u;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) tot += v[u];
-        }
-    long long inc = tot;                                       // inclusive scan over the digits
-    for (int s = 1; s < 64; s <<= 1) { const long long o = __shfl_up(inc, (unsigned)s); if (lane >= s) inc += o; }
-    if (lane == 63) sh[wave] = inc;
-    __syncthreads();
-    long long run = inc - tot;
-    for (int w = 0; w < wave; ++w) run += sh[w];
-    if (d == D - 1) *total_out = run + tot;
-    if (d < D)
-        for (int c = 0; c < n_chunks; c += 8) {
-            uint32_t v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = c + u < n_chunks ? part[(int64_t)(c + u) * D + d] : 0u;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) if (c + u < n_chunks) { base[(int64_t)(c + u) * D + d] = run; run += v[u]; }
-        }
-}
-__global__ void __launch_bounds__(C2_SCAN_THREADS)
-cf_c2_coloffs_kernel(const uint32_t* __restrict__ hist, int n_tiles, int D, const int64_t* __restrict__ base, int64_t* __restrict__ offs) {
-    const int d = threadIdx.x;
-    if (d >= D) return;
-    const int t0 = blockIdx.x * C2_SCAN_CHUNK, t1 = min(n_tiles, t0 + C2_SCAN_CHUNK);
-    long long run = base[(int64_t)blockIdx.x * D + d];
-    for (int t = t0; t < t1; t += 8) {
-        uint32_t v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = t + u < t1 ? hist[(int64_t)(t + u) * D + d] : 0u;
-#pragma unroll
-        for (int u = 0; u < 8; ++u) if (t + u < t1) { offs[(int64_t)(t + u) * D + d] = run; run += v[u]; }
+        for (int d = lane; d < D; d += 64) wcount[wave * D + d] = 0;     // a wave clears its own row: the next tile's ranking reads it with no barrier between
     }
 }
 
@@ -784,16 +657,13 @@ int cf_count_sorted(cf_ctx* ctx, int32_t k, int64_t read_lo, int64_t read_hi, in
         CF_KERNEL_CHECK("cf_c2_hist");
         int64_t n_made = 0;
         {
-            const int D = 1 << nb, n_chunks = (n_tiles + C2_SCAN_CHUNK - 1) / C2_SCAN_CHUNK;
+            const size_t nc = (size_t)cf_tile_digit_chunks(n_tiles) << nb;
             uint32_t* d_part = nullptr;
             int64_t* d_base = nullptr;
-            CF_TRY(pass.get(&d_part, (size_t)n_chunks * D + 1, "count column sums"));
-            CF_TRY(pass.get(&d_base, (size_t)n_chunks * D + 2, "count column bases"));
-            int64_t* d_total = d_base + (size_t)n_chunks * D;
-            hipLaunchKernelGGL(cf_c2_colsum_kernel, dim3((unsigned)n_chunks), dim3(C2_SCAN_THREADS), 0, ctx->stream, (const uint32_t*)d_hist, n_tiles, D, d_part);
-            hipLaunchKernelGGL(cf_c2_colbase_kernel, dim3(1), dim3(C2_SCAN_THREADS), 64, ctx->stream, (const uint32_t*)d_part, n_chunks, D, d_base, d_total);
-            hipLaunchKernelGGL(cf_c2_coloffs_kernel, dim3((unsigned)n_chunks), dim3(C2_SCAN_THREADS), 0, ctx->stream, (const uint32_t*)d_hist, n_tiles, D, (const int64_t*)d_base, d_offs);
-            CF_KERNEL_CHECK("cf_c2_col*");
+            CF_TRY(pass.get(&d_part, nc + 1, "count column sums"));
+            CF_TRY(pass.get(&d_base, nc + 2, "count column bases"));
+            int64_t* d_total = d_base + nc;
+            CF_TRY(cf_tile_digit_offsets(ctx, d_hist, n_tiles, 1 << nb, d_offs, d_total, d_part, d_base));
             CF_HIP(hipMemcpyAsync(&n_made, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
             CF_HIP(hipStreamSynchronize(ctx->stream));
         }

@@ -2,7 +2,7 @@
 // Auxiliary primitives of the pipeline: CSR offsets (clouds, postings) and the ascending
 // order of the rare k-mer set (reference: the k-mer file is written sorted,
 // scripts/distance_based_kmer_recruitment.py:160-164).
-#include "cf_common.h"
+#include "cf_radix.h"
 
 #define SCAN_THREADS 256
 #define SCAN_ITEMS 8
@@ -99,64 +99,166 @@ int cf_scan_exclusive_u32_to_i64(cf_ctx* ctx, const uint32_t* d_in, int64_t* d_o
     return scan_impl<uint32_t>(ctx, d_in, d_out, n, total);
 }
 
-// ------------------------------------------------------------------ radix sort
-#define RS_THREADS 256
-#define RS_ITEMS 8
-#define RS_TILE (RS_THREADS * RS_ITEMS)
-
-__global__ void __launch_bounds__(RS_THREADS)
-cf_radix_hist(const unsigned long long* __restrict__ in, uint32_t* __restrict__ hist, int64_t n, int shift, int ntiles) {
-    uint32_t* h = (uint32_t*)cf_lds;
-    h[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * RS_TILE;
+// ------------------------------------------------------------------ offsets of tile-major digit histograms
+// offs[tile][d] = keys with a smaller digit + keys of digit d in earlier tiles = the exclusive scan of hist in (digit, tile)
+// order, computed on the tile-major arrays by columns: (1) column sums of chunks of `chunk` tiles, (2) one workgroup turns
+// them into the chunks' bases (column totals, scan over the digits, running sums down the chunks), (3) every chunk walks its
+// tiles again.  All accesses are runs of D counters (digit-major counters made every counter its own 64-byte sector on the
+// way out and on the way back in: 20 GB of A1's 91 GB of HBM traffic).  A walk is latency-bound — its loads
+// are issued CF_COL_UNROLL at a time, and the stores of a walk wait for their acknowledgement before the next loads — so
+// the chunk is about sqrt(tiles): the walks of (1) and (3) and the one of (2) are equally long.
+#define CF_COL_THREADS 512                  /* >= D: a thread per digit */
+#define CF_COL_UNROLL 16
+__global__ void __launch_bounds__(CF_COL_THREADS)
+cf_col_sum_kernel(const uint32_t* __restrict__ hist, int n_tiles, int D, int chunk, uint32_t* __restrict__ part) {
+    const int d = threadIdx.x;
+    if (d >= D) return;
+    const int t0 = blockIdx.x * chunk, t1 = min(n_tiles, t0 + chunk);
+    uint32_t acc = 0;
+    for (int t = t0; t < t1; t += CF_COL_UNROLL) {
+        uint32_t v[CF_COL_UNROLL];
 #pragma unroll
-    for (int i = 0; i < RS_ITEMS; ++i) {
-        const int64_t idx = base + (int64_t)i * RS_THREADS + threadIdx.x;
-        if (idx < n) atomicAdd(&h[(uint32_t)(in[idx] >> shift) & 255u], 1u);
+        for (int u = 0; u < CF_COL_UNROLL; ++u) v[u] = t + u < t1 ? hist[(int64_t)(t + u) * D + d] : 0u;
+#pragma unroll
+        for (int u = 0; u < CF_COL_UNROLL; ++u) acc += v[u];
     }
+    part[(int64_t)blockIdx.x * D + d] = acc;
+}
+__global__ void __launch_bounds__(CF_COL_THREADS)
+cf_col_base_kernel(const uint32_t* __restrict__ part, int n_chunks, int D, int64_t* __restrict__ base, int64_t* __restrict__ total_out) {
+    long long* sh = (long long*)cf_lds;                       // CF_COL_THREADS / 64 wave totals
+    const int d = threadIdx.x, lane = d & 63, wave = d >> 6;
+    long long tot = 0;
+    if (d < D)
+        for (int c = 0; c < n_chunks; c += CF_COL_UNROLL) {
+            uint32_t v[CF_COL_UNROLL];
+#pragma unroll
+            for (int u = 0; u < CF_COL_UNROLL; ++u) v[u] = c + u < n_chunks ? part[(int64_t)(c + u) * D + d] : 0u;
+#pragma unroll
+            for (int u = 0; u < CF_COL_UNROLL; ++u) tot += v[u];
+        }
+    long long inc = tot;                                       // inclusive scan over the digits
+    for (int s = 1; s < 64; s <<= 1) { const long long o = __shfl_up(inc, (unsigned)s); if (lane >= s) inc += o; }
+    if (lane == 63) sh[wave] = inc;
     __syncthreads();
-    hist[(int64_t)threadIdx.x * ntiles + blockIdx.x] = h[threadIdx.x];
+    long long run = inc - tot;
+    for (int w = 0; w < wave; ++w) run += sh[w];
+    if (total_out && d == D - 1) *total_out = run + tot;
+    if (d < D)
+        for (int c = 0; c < n_chunks; c += CF_COL_UNROLL) {
+            uint32_t v[CF_COL_UNROLL];
+#pragma unroll
+            for (int u = 0; u < CF_COL_UNROLL; ++u) v[u] = c + u < n_chunks ? part[(int64_t)(c + u) * D + d] : 0u;
+#pragma unroll
+            for (int u = 0; u < CF_COL_UNROLL; ++u) if (c + u < n_chunks) { base[(int64_t)(c + u) * D + d] = run; run += v[u]; }
+        }
+}
+__global__ void __launch_bounds__(CF_COL_THREADS)
+cf_col_offs_kernel(const uint32_t* __restrict__ hist, int n_tiles, int D, int chunk, const int64_t* __restrict__ base, int64_t* __restrict__ offs) {
+    const int d = threadIdx.x;
+    if (d >= D) return;
+    const int t0 = blockIdx.x * chunk, t1 = min(n_tiles, t0 + chunk);
+    long long run = base[(int64_t)blockIdx.x * D + d];
+    for (int t = t0; t < t1; t += CF_COL_UNROLL) {
+        uint32_t v[CF_COL_UNROLL];
+#pragma unroll
+        for (int u = 0; u < CF_COL_UNROLL; ++u) v[u] = t + u < t1 ? hist[(int64_t)(t + u) * D + d] : 0u;
+#pragma unroll
+        for (int u = 0; u < CF_COL_UNROLL; ++u) if (t + u < t1) { offs[(int64_t)(t + u) * D + d] = run; run += v[u]; }
+    }
 }
 
-__global__ void __launch_bounds__(RS_THREADS)
+static int col_chunk(int n_tiles) {       // ~sqrt(n_tiles), a multiple of CF_COL_UNROLL
+    int c = CF_COL_UNROLL;
+    while ((int64_t)c * c < n_tiles) c += CF_COL_UNROLL;
+    return c;
+}
+int cf_tile_digit_chunks(int n_tiles) { const int c = col_chunk(n_tiles); return (n_tiles + c - 1) / c; }
+
+int cf_tile_digit_offsets(cf_ctx* ctx, const uint32_t* d_hist, int n_tiles, int D, int64_t* d_offs, int64_t* d_total, uint32_t* d_part, int64_t* d_base) {
+    if (D < 1 || D > CF_COL_THREADS) return cf_fail(ctx, -22, "cf_tile_digit_offsets: bad digit count");
+    const int chunk = col_chunk(n_tiles), n_chunks = cf_tile_digit_chunks(n_tiles);
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(cf_col_sum_kernel, dim3((unsigned)n_chunks), dim3(CF_COL_THREADS), 0, ctx->stream, d_hist, n_tiles, D, chunk, d_part);
+    hipLaunchKernelGGL(cf_col_base_kernel, dim3(1), dim3(CF_COL_THREADS), 64, ctx->stream, (const uint32_t*)d_part, n_chunks, D, d_base, d_total);
+    hipLaunchKernelGGL(cf_col_offs_kernel, dim3((unsigned)n_chunks), dim3(CF_COL_THREADS), 0, ctx->stream, d_hist, n_tiles, D, chunk, (const int64_t*)d_base, d_offs);
+    CF_KERNEL_CHECK("cf_col*");
+    return 0;
+}
+
+// ------------------------------------------------------------------ radix sort of 64-bit keys
+// LSD passes of 8-bit digits over tiles of RX_TILE keys.  Per pass: cf_radix_hist writes every tile's digit counts
+// (tile-major), cf_tile_digit_offsets turns them into the tile's global offsets, cf_radix_scatter ranks the tile stably in
+// LDS (cf_radix.h) and writes every digit's run of the tile as one contiguous piece.  No host synchronisation between passes.
+#define RX_ITEMS 16
+#define RX_TILE (CF_RX_THREADS * RX_ITEMS)
+#define RX_D 256
+struct __attribute__((aligned(16))) cf_u64x2 { unsigned long long a, b; };
+
+__global__ void __launch_bounds__(CF_RX_THREADS)
+cf_radix_hist(const unsigned long long* __restrict__ in, uint32_t* __restrict__ hist, int64_t n, int shift, int ntiles) {
+    uint32_t* h = (uint32_t*)cf_lds;
+    const int t = threadIdx.x;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        h[t] = 0;
+        __syncthreads();
+        const int64_t base = (int64_t)tile * RX_TILE;
+        if (base + RX_TILE <= n) {          // whole tile: 16-byte loads (a tile begins on a multiple of RX_TILE keys)
+            const cf_u64x2* v = (const cf_u64x2*)(in + base);
+#pragma unroll
+            for (int j = 0; j < RX_ITEMS / 2; ++j) {
+                const cf_u64x2 x = v[j * CF_RX_THREADS + t];
+                atomicAdd(&h[(uint32_t)(x.a >> shift) & (RX_D - 1)], 1u);
+                atomicAdd(&h[(uint32_t)(x.b >> shift) & (RX_D - 1)], 1u);
+            }
+        } else {
+            for (int j = 0; j < RX_ITEMS; ++j) {
+                const int64_t i = base + (int64_t)j * CF_RX_THREADS + t;
+                if (i < n) atomicAdd(&h[(uint32_t)(in[i] >> shift) & (RX_D - 1)], 1u);
+            }
+        }
+        __syncthreads();
+        hist[(int64_t)tile * RX_D + t] = h[t];
+        __syncthreads();
+    }
+}
+
+// LDS: gbase int64[D] | wcount u32[4][D] | dstart u32[D] | scan_tmp u32[8] | staged keys u64[RX_TILE]
+#define RX_SCATTER_LDS (RX_D * 8 + (CF_RX_THREADS / 64) * RX_D * 4 + RX_D * 4 + 32 + 16 + RX_TILE * 8)
+__global__ void __launch_bounds__(CF_RX_THREADS)
 cf_radix_scatter(const unsigned long long* __restrict__ in, unsigned long long* __restrict__ out,
                  const int64_t* __restrict__ offs, int64_t n, int shift, int ntiles) {
-    int64_t* run = (int64_t*)cf_lds;                       // 256 running offsets, one per digit
-    uint32_t* wcount = (uint32_t*)(cf_lds + 256 * 8);      // [4][256] per-wave digit counts
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    run[t] = offs[(int64_t)t * ntiles + blockIdx.x];
-    for (int w = 0; w < 4; ++w) wcount[w * 256 + t] = 0;
-    __syncthreads();
-    const int64_t base = (int64_t)blockIdx.x * RS_TILE;
-    for (int round = 0; round < RS_ITEMS; ++round) {
-        const int64_t idx = base + (int64_t)round * RS_THREADS + t;
-        const bool valid = idx < n;
-        const unsigned long long key = valid ? in[idx] : 0ull;
-        const uint32_t digit = (uint32_t)(key >> shift) & 255u;
-        unsigned long long peers = __ballot(valid);
+    int64_t* gbase = (int64_t*)cf_lds;
+    uint32_t* wcount = (uint32_t*)(gbase + RX_D);
+    uint32_t* dstart = wcount + (CF_RX_THREADS / 64) * RX_D;
+    uint32_t* scan_tmp = dstart + RX_D;
+    unsigned long long* srec = (unsigned long long*)(((uintptr_t)(scan_tmp + 8) + 15) & ~(uintptr_t)15);
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    uint32_t* wrow = wcount + wave * RX_D;
+    for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        gbase[t] = offs[(int64_t)tile * RX_D + t];
+        for (int d = lane; d < RX_D; d += 64) wrow[d] = 0;      // (a wave clears its own row: its LDS ops are in order)
+        // wave w takes the keys [w * 64 * RX_ITEMS, ...) of the tile in rounds of 64: array order = (wave, round, lane)
+        const int64_t base = (int64_t)tile * RX_TILE + (int64_t)wave * 64 * RX_ITEMS + lane;
+        unsigned long long key[RX_ITEMS];
+        uint32_t rank[RX_ITEMS];
 #pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const int bit = (digit >> b) & 1;
-            const unsigned long long m = __ballot(bit);
-            peers &= bit ? m : ~m;
-        }
-        const uint32_t rank = (uint32_t)__popcll(peers & ((1ull << lane) - 1ull));
-        if (valid && rank == 0) wcount[wave * 256 + digit] = (uint32_t)__popcll(peers);
+        for (int j = 0; j < RX_ITEMS; ++j) { const int64_t i = base + (int64_t)j * 64; key[j] = i < n ? in[i] : 0ull; }
+#pragma unroll
+        for (int j = 0; j < RX_ITEMS; ++j)
+            rank[j] = cf_rx_rank_round<8>((uint32_t)(key[j] >> shift) & (RX_D - 1), base + (int64_t)j * 64 < n, wrow);
+        cf_rx_tile_bases<8>(dstart, wcount, scan_tmp);
+#pragma unroll
+        for (int j = 0; j < RX_ITEMS; ++j)
+            if (base + (int64_t)j * 64 < n) { const uint32_t d = (uint32_t)(key[j] >> shift) & (RX_D - 1); srec[dstart[d] + wrow[d] + rank[j]] = key[j]; }
+        const uint32_t n_tile = (uint32_t)min((int64_t)RX_TILE, n - (int64_t)tile * RX_TILE);
         __syncthreads();
-        int64_t pos = 0;
-        if (valid) {
-            pos = run[digit] + rank;
-            for (int w = 0; w < wave; ++w) pos += wcount[w * 256 + digit];
-        }
-        __syncthreads();
-        {
-            uint32_t s = 0;
-            for (int w = 0; w < 4; ++w) { s += wcount[w * 256 + t]; wcount[w * 256 + t] = 0; }
-            run[t] += s;
+        for (uint32_t i = t; i < n_tile; i += CF_RX_THREADS) {      // consecutive threads write consecutive addresses inside a digit's run
+            const unsigned long long k = srec[i];
+            const uint32_t d = (uint32_t)(k >> shift) & (RX_D - 1);
+            out[gbase[d] + (int64_t)(i - dstart[d])] = k;
         }
         __syncthreads();
-        if (valid) out[pos] = key;
     }
 }
 
@@ -169,19 +271,26 @@ int cf_radix_sort_u64(cf_ctx* ctx, unsigned long long* d_keys, unsigned long lon
 int cf_radix_sort_u64_any(cf_ctx* ctx, unsigned long long* d_keys, unsigned long long* d_tmp, int64_t n, int bits, unsigned long long** result) {
     if (result) *result = d_keys;
     if (n <= 1) return 0;
-    const int ntiles = (int)((n + RS_TILE - 1) / RS_TILE);
-    const int64_t nh = (int64_t)ntiles * 256;
+    if ((n + RX_TILE - 1) / RX_TILE >= ((int64_t)1 << 31)) return cf_fail(ctx, -22, "radix sort: too many keys");
+    const int ntiles = (int)((n + RX_TILE - 1) / RX_TILE);
+    const int64_t nh = (int64_t)ntiles * RX_D, nc = (int64_t)cf_tile_digit_chunks(ntiles) * RX_D;
+    const int grid = std::min(ntiles, std::max(1, ctx->n_cu) * 8);
     uint32_t* d_hist = nullptr;
     int64_t* d_offs = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_hist, (size_t)nh, "radix histogram"));
-    int rc = cf_alloc_t(ctx, &d_offs, (size_t)nh, "radix offsets");
+    uint32_t* d_part = nullptr;
+    int64_t* d_base = nullptr;
+    int rc = cf_alloc_t(ctx, &d_hist, (size_t)nh, "radix histogram");
+    if (rc == 0) rc = cf_alloc_t(ctx, &d_offs, (size_t)nh, "radix offsets");
+    if (rc == 0) rc = cf_alloc_t(ctx, &d_part, (size_t)nc, "radix column sums");
+    if (rc == 0) rc = cf_alloc_t(ctx, &d_base, (size_t)nc, "radix column bases");
     unsigned long long* src = d_keys;
     unsigned long long* dst = d_tmp;
     for (int shift = 0; rc == 0 && shift < bits; shift += 8) {
-        hipLaunchKernelGGL(cf_radix_hist, dim3((unsigned)ntiles), dim3(RS_THREADS), 256 * 4, ctx->stream, src, d_hist, n, shift, ntiles);
-        rc = cf_scan_exclusive_u32_to_i64(ctx, d_hist, d_offs, nh, nullptr);
+        hipLaunchKernelGGL(cf_radix_hist, dim3((unsigned)grid), dim3(CF_RX_THREADS), RX_D * 4, ctx->stream, (const unsigned long long*)src, d_hist, n, shift, ntiles);
+        rc = cf_tile_digit_offsets(ctx, d_hist, ntiles, RX_D, d_offs, nullptr, d_part, d_base);
         if (rc) break;
-        hipLaunchKernelGGL(cf_radix_scatter, dim3((unsigned)ntiles), dim3(RS_THREADS), 256 * 8 + 4 * 256 * 4, ctx->stream, src, dst, d_offs, n, shift, ntiles);
+        hipLaunchKernelGGL(cf_radix_scatter, dim3((unsigned)grid), dim3(CF_RX_THREADS), RX_SCATTER_LDS, ctx->stream, (const unsigned long long*)src, dst,
+                           (const int64_t*)d_offs, n, shift, ntiles);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("radix launch: ") + hipGetErrorString(e)); break; }
         std::swap(src, dst);
@@ -191,18 +300,24 @@ int cf_radix_sort_u64_any(cf_ctx* ctx, unsigned long long* d_keys, unsigned long
         hipError_t e = hipMemcpyAsync(d_keys, src, (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream);
         if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("radix copy back: ") + hipGetErrorString(e));
     }
-    if (rc == 0) {
+    {
         hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("radix sync: ") + hipGetErrorString(e));
+        if (e != hipSuccess && rc == 0) rc = cf_fail(ctx, -5, std::string("radix sync: ") + hipGetErrorString(e));
     }
+    if (d_base) cf_release_t(ctx, d_base, (size_t)nc);
+    if (d_part) cf_release_t(ctx, d_part, (size_t)nc);
     if (d_offs) cf_release_t(ctx, d_offs, (size_t)nh);
-    cf_release_t(ctx, d_hist, (size_t)nh);
+    if (d_hist) cf_release_t(ctx, d_hist, (size_t)nh);
     return rc;
 }
 
 // ------------------------------------------------------------------ radix sort of 16-byte records by 32-bit fields
-// LSD passes of 8 bits over the fields the caller lists (least significant first): the same histogram / scan / stable
-// ballot-ranked scatter as above, with a record = four 32-bit words and the digit taken from word `word`.
+// LSD passes of 8 bits over the fields the caller lists (least significant first): per pass a digit-major histogram of
+// tiles of RS_TILE records, its exclusive scan, and a stable ballot-ranked scatter, with a record = four 32-bit words and
+// the digit taken from word `word`.
+#define RS_THREADS 256
+#define RS_ITEMS 8
+#define RS_TILE (RS_THREADS * RS_ITEMS)
 struct __attribute__((aligned(16))) cf_rec16 { uint32_t w[4]; };
 
 __global__ void __launch_bounds__(RS_THREADS)
