@@ -60,6 +60,10 @@ def lib():
     L.cfh_exotic_list.restype = i64
     L.cfh_exotic_list.argtypes = [P, i32, i64, i64, C.c_void_p, i64]
     L.cfh_exotic_kept.restype = i64
+    L.cfh_exotic_occurrences.restype = i64
+    L.cfh_exotic_occurrences.argtypes = [P, i32, i64, C.c_void_p, C.c_void_p, i64]
+    L.cfh_unit_star.argtypes = [i32, C.c_char_p, C.c_void_p, i64, C.c_char_p, i64, C.c_void_p, i64, pi64, C.c_void_p, C.c_char_p, C.c_int]
+    L.cfh_hw_locate.argtypes = [C.c_char_p, i64, C.c_char_p, i64, C.POINTER(C.c_int32)]
     L.cfh_exotic_kept.argtypes = [P, i32, i32, C.c_void_p, C.c_void_p, i64]
     L.cfh_exotic_rare.restype = i64
     L.cfh_exotic_rare.argtypes = [P, i32, i32, C.c_uint32, C.c_uint32, C.c_void_p, i64]
@@ -222,6 +226,19 @@ class PackedReads:
         raw = buf.raw[:n * int(k)].decode("latin-1")
         return [raw[i * k:(i + 1) * k] for i in range(n)]
 
+    def exotic_occurrences(self, k, min_count=1):
+        """[(window text, occurrences)] of the windows with a symbol other than upper-case A, C, G, T counted at least min_count
+        times over all reads (every window of every row: stage 4's count), in ascending text order."""
+        n = lib().cfh_exotic_occurrences(self._h, int(k), int(min_count), None, None, 0)
+        if n < 0:
+            raise HostError(f"cfh_exotic_occurrences failed ({n})")
+        buf = C.create_string_buffer(max(1, n * int(k)))
+        cnt = np.zeros(max(1, n), np.int64)
+        if n and lib().cfh_exotic_occurrences(self._h, int(k), int(min_count), buf, cnt.ctypes.data, n) != n:
+            raise HostError("cfh_exotic_occurrences: the window set changed between two calls")
+        raw = buf.raw[:n * int(k)].decode("latin-1")
+        return [(raw[i * k:(i + 1) * k], int(cnt[i])) for i in range(n)]
+
     def export_read_units(self, rec, pos, outdir, min_pos=0, max_pos=None, n_threads=0):
         """Per-position read-unit FASTA files (reference eltr_polisher.py:53-97).  rec / pos: record indices and
         positions of the placed reads in read_positions.csv order; max_pos None = infinity.  Returns
@@ -296,6 +313,54 @@ def synth(report_path=None, pack=True, keep_rows=False, **kw):
     _check(L.cfh_synth(C.byref(sp), os.fsencode(report_path) if report_path else None,
                        int(keep_rows), C.byref(h) if pack else None, err, 512), err)
     return PackedReads(h) if pack else None
+
+
+UNIT_STAR_STATS = ("nodes_built", "edges_built", "nodes_collapsed", "edges_collapsed", "nodes_tipped", "edges_tipped",
+                   "purify_removed", "nodes_final", "edges_final", "cycle_len", "edit_distance", "align_start", "graph_us", "align_us")
+
+
+class UnitStarError(HostError):
+    """cfh_unit_star refused: where the reference's get_polished_unit raises (code -61 .. -64), or bad arguments."""
+
+    def __init__(self, code, msg, stats):
+        super().__init__(msg)
+        self.code = code
+        self.stats = stats
+
+
+def unit_star(k, kmers, counts, unit):
+    """(unit*, stats dict) of the reference's get_polished_unit on the k-mers in the given order (include/cfhost.h cfh_unit_star)."""
+    k = int(k)
+    kmers = list(kmers)
+    raw = "".join(kmers).encode("latin-1")
+    if len(raw) != len(kmers) * k:
+        raise ValueError(f"every k-mer must have length {k}")
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    if counts.size != len(kmers):
+        raise ValueError("one count per k-mer")
+    u = unit.encode("latin-1") if isinstance(unit, str) else bytes(unit)
+    cap = max(1, len(raw))
+    out = C.create_string_buffer(cap)
+    n_out = C.c_int64()
+    stats = np.zeros(len(UNIT_STAR_STATS), np.int64)
+    err = C.create_string_buffer(512)
+    rc = lib().cfh_unit_star(k, raw, counts.ctypes.data if counts.size else None, len(kmers), u, len(u), out, cap, C.byref(n_out),
+                             stats.ctypes.data, err, 512)
+    st = dict(zip(UNIT_STAR_STATS, (int(x) for x in stats)))
+    if rc != 0:
+        raise UnitStarError(rc, f"cfhost error {rc}: {err.value.decode(errors='replace')}", st)
+    return out.raw[:n_out.value].decode("latin-1"), st
+
+
+def hw_locate(query, target):
+    """(edit distance, start, end) of edlib.align(query, target, mode='HW', task='locations')['locations'][0]."""
+    q = query.encode("latin-1") if isinstance(query, str) else bytes(query)
+    t = target.encode("latin-1") if isinstance(target, str) else bytes(target)
+    out = (C.c_int32 * 3)()
+    rc = lib().cfh_hw_locate(q, len(q), t, len(t), out)
+    if rc != 0:
+        raise HostError(f"cfh_hw_locate failed ({rc})")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 def write_kmers(path, kmers, k):

@@ -580,6 +580,9 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
     } else if (n == "count_tile") {
         if (value < 1 || value > 64) return cf_fail(ctx, -22, "count_tile out of range");
         ctx->count_tile = (int)value;
+    } else if (n == "count_skip_exotic") {
+        if (value < 0 || value > 1) return cf_fail(ctx, -22, "count_skip_exotic must be 0 or 1");
+        ctx->count_skip_exotic = (int)value;
     } else if (n == "comm_round_bytes") {
         if (value < 16 || value > ((int64_t)1 << 30) || value % 16) return cf_fail(ctx, -22, "comm_round_bytes must be a multiple of 16 in [16, 2^30]");
         ctx->comm_round_bytes = value;

@@ -173,6 +173,7 @@ struct cf_ctx {
     int count_bits = 0;          // bucket bits of the sort-and-reduce path; 0 = from the number of windows (tests force small / large values)
     int count_slots = 4096;
     int count_tile = 16;
+    int count_skip_exotic = 0;   // 1: cf_count_occurrences counts reads with other symbols too, skipping their windows (stage 4 adds them on the host)
     int64_t comm_round_bytes = (int64_t)256 << 20;   // bytes per pair and round of the multi-GPU exchanges (tests force small rounds)
     int comm_self_p2p = 0;       // 1: a rank's message to itself goes through ncclSend / ncclRecv too (tests: the p2p path on one GPU)
 };

@@ -379,7 +379,7 @@ static int count_impl(cf_ctx* ctx, int32_t k, int64_t read_lo, int64_t read_hi, 
     if (2 * k < 62 && cap > (2ull << (2 * k))) cap = cf_pow2_ceil(2ull << (2 * k));
     ctx->k = k;
     ctx->stats.n_windows = n_w;
-    if (mode == 1 && ctx->has_exotic)
+    if (mode == 1 && ctx->has_exotic && !ctx->count_skip_exotic)
         return cf_fail(ctx, -22, "cf_count_occurrences: reads with symbols other than upper-case A, C, G, T are not supported");
     if (ctx->count_mode) {      // by sort and reduce; 1 = does not apply here (long k, too many reads, a crowded bucket)
         const int rc2 = cf_count_sorted(ctx, k, read_lo, read_hi, n_w, mode);

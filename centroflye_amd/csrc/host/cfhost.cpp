@@ -1285,6 +1285,39 @@ int64_t cfh_exotic_kept(const cfh_pack* p, int32_t k, int32_t max_nonuniq, char*
         return -5;
     }
 }
+// Total occurrences of those windows (stage 4, scripts/better_consensus_unit_reconstruction.py:129-137 counts every window of
+// the raw de-gapped row, no per-read de-duplication): the ones counted at least min_count times, as text in ascending order.
+int64_t cfh_exotic_occurrences(const cfh_pack* p, int32_t k, int64_t min_count, char* out, int64_t* counts, int64_t cap) {
+    try {
+        if (!p || k < 1 || (cap > 0 && (!out || !counts))) return -22;
+        std::unordered_map<std::string, int64_t> all;
+        const int64_t R = p->n_reads();
+        for (int64_t r = 0; r < R; ++r) {
+            const int64_t b0 = p->read_off[(size_t)r], len = p->read_off[(size_t)r + 1] - b0;
+            int64_t next_w = 0;                  // windows below this start were counted already
+            for (int64_t i = 0; i < len; ++i) {
+                const char c = p->bases[(size_t)(b0 + i)];
+                if (c == 'A' || c == 'C' || c == 'G' || c == 'T') continue;
+                const int64_t w_lo = std::max<int64_t>(next_w, i - k + 1), w_hi = std::min<int64_t>(i, len - k);
+                for (int64_t w = w_lo; w <= w_hi; ++w) ++all[std::string(p->bases.data() + (b0 + w), (size_t)k)];
+                if (w_hi + 1 > next_w) next_w = w_hi + 1;
+            }
+        }
+        std::vector<const std::pair<const std::string, int64_t>*> keep;
+        for (const auto& kv : all)
+            if (kv.second >= min_count) keep.push_back(&kv);
+        std::sort(keep.begin(), keep.end(), [](auto* a, auto* b) { return a->first < b->first; });
+        for (int64_t i = 0; i < (int64_t)keep.size() && i < cap; ++i) {
+            std::memcpy(out + i * k, keep[(size_t)i]->first.data(), (size_t)k);
+            counts[i] = keep[(size_t)i]->second;
+        }
+        return (int64_t)keep.size();
+    } catch (const std::bad_alloc&) {
+        return -12;
+    } catch (...) {
+        return -5;
+    }
+}
 const uint8_t* cfh_bases(const cfh_pack* p) { return (const uint8_t*)p->bases.data(); }
 const int64_t* cfh_read_off(const cfh_pack* p) { return p->read_off.data(); }
 const char* cfh_ids(const cfh_pack* p) { return p->ids.data(); }

@@ -99,6 +99,12 @@ int64_t cfh_exotic_rare_lower(const cfh_pack* p, int32_t k, int32_t max_nonuniq,
  * each, ascending) and the number of reads holding it — the keys of get_kmer_freqs_from_ncrf_report's mapping that have no 2-bit code. */
 int64_t cfh_exotic_kept(const cfh_pack* p, int32_t k, int32_t max_nonuniq, char* out, int64_t* pres, int64_t cap);
 
+/* Total occurrences of the same windows over all reads, every window of every row counted (stage 4's get_kmer_counts_reads,
+ * scripts/better_consensus_unit_reconstruction.py:129-137): the windows counted at least min_count times, as text (k bytes each,
+ * ascending) with their counts; at most cap written; returns their number (or < 0).  The device count (cf_count_occurrences) skips
+ * them; the caller merges them into its top n (centroflye_amd/better_consensus_unit_reconstruction.py). */
+int64_t cfh_exotic_occurrences(const cfh_pack* p, int32_t k, int64_t min_count, char* out, int64_t* counts, int64_t cap);
+
 /* Flat arrays. */
 const uint8_t* cfh_bases(const cfh_pack* p);     /* ASCII, de-gapped oriented r_al, length N_b */
 const int64_t* cfh_read_off(const cfh_pack* p);  /* R+1 offsets into bases */
@@ -149,6 +155,21 @@ int cfh_export_read_units(cfh_pack* p, const int64_t* rec, const int64_t* pos, i
  * if non-NULL (size-query then fill). All k-mers must have length k and be ACGT. */
 int cfh_read_kmers(const char* path, int32_t k, uint64_t* out, int64_t cap, int64_t* n_out,
                    char* err, int errlen);
+
+/* Stage 4 on the host (scripts/better_consensus_unit_reconstruction.py:170-190 get_polished_unit; cfh_unit_star.cpp): the de Bruijn
+ * graph of the n k-mers (k bytes each, inserted in the given order, which fixes the node order the result depends on; counts[i] =
+ * occurrences of k-mer i), collapse, tip removal, purification, the smallest edge tuple minus k - 1 bases, re-phased to `unit` by the
+ * first location of an edlib-compatible HW alignment.  2 <= k; writes the unit* (at most n * k bytes) into out[cap] and its length
+ * into out_len.  stats (CFH_UNIT_STAR_NSTATS, may be NULL): nodes / edges after the build, after the first collapse, after tips and
+ * the second collapse, purification removals, nodes / edges of the final graph, cycle length, edit distance, alignment start,
+ * graph and alignment microseconds.  Returns 0, or < 0 where the reference raises (-61 no first edge, -62 the graph empties,
+ * -63 it falls apart, -64 no edge left) or on bad arguments (-22) and a too small buffer (-34). */
+#define CFH_UNIT_STAR_NSTATS 14
+int cfh_unit_star(int32_t k, const char* kmers, const int64_t* counts, int64_t n, const char* unit, int64_t unit_len,
+                  char* out, int64_t cap, int64_t* out_len, int64_t* stats, char* err, int errlen);
+/* The alignment of cfh_unit_star alone: edlib.align(query, target, mode='HW', task='locations') -> out = {edit distance,
+ * locations[0] start, locations[0] end}. */
+int cfh_hw_locate(const char* query, int64_t qlen, const char* target, int64_t tlen, int32_t out[3]);
 
 #ifdef __cplusplus
 }
