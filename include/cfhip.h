@@ -104,7 +104,9 @@ int cf_set_kmers(cf_ctx* ctx, const uint64_t* kmers, int64_t n, int32_t k);
 int cf_get_kmers(cf_ctx* ctx, uint64_t* out, int64_t cap);
 
 /* A3: per-unit clouds of the current k-mer set as CSR (entries = indices into the set, sorted
- * unique inside each unit). */
+ * unique inside each unit).  A unit may hold at most 6144 distinct set k-mers: clouds of up to 1536 are built with a
+ * 2048-slot LDS set, a larger one makes the call repeat the launch with 8192 slots, and beyond 6144 it returns -34
+ * (no clouds are installed; the context stays usable). */
 int cf_build_clouds(cf_ctx* ctx, int64_t* n_entries);
 /* A4: keep k-mers present in [min_mult, max_mult] clouds overall (max_mult = 0: no upper bound). */
 int cf_filter_clouds(cf_ctx* ctx, uint32_t min_mult, uint32_t max_mult, int64_t* n_entries);
