@@ -5,6 +5,7 @@ Not on the pipeline's path: the live use of the cloud contig (adding reads and u
 exists for interactive use and API parity: the same public names, attributes and return
 values as the reference (cloud_contig.py:8-41 CloudContig, :43-84 scoring helpers, :87-95 update_mapping_scores,
 :98-156 map_reads / map_reads_fast), written on plain dict / Counter containers.
+The device path of ``map_reads_fast`` on a finished contig is ``centroflye_amd/read_mapper.py`` (cf_contig_build, cf_map_reads).
 """
 from collections import Counter, defaultdict
 from itertools import chain

@@ -255,8 +255,10 @@ void cf_free_kmers(cf_ctx* c) {
     c->n_kmers = 0; c->lut_cap = 0; c->lut_pre_words = 0; c->unique_words = 0;
 }
 void cf_free_gview(cf_ctx* c);   // cf_exchange.hip
+void cf_free_contig(cf_ctx* c);  // cf_map.hip
 void cf_free_clouds(cf_ctx* c) {
     cf_free_gview(c);           // the all-gathered view is derived from the local clouds
+    cf_free_contig(c);          // and so is the frozen contig
     cf_release_t(c, c->d_cloud_ptr, (size_t)c->n_units + 1);
     cf_release_t(c, c->d_entries, (size_t)c->n_entries);
     c->n_entries = 0; c->have_clouds = false;
@@ -569,6 +571,9 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
     } else if (n == "place_grid") {
         if (value < 0 || value > 4096) return cf_fail(ctx, -22, "place_grid out of range (0 = auto, 1 .. 4096)");
         ctx->place_grid = (int)value;
+    } else if (n == "map_window") {
+        if (value < 0 || value > 4096) return cf_fail(ctx, -22, "map_window out of range (0 = default, 1 .. 4096: 12 bytes of LDS per slot)");
+        ctx->map_window = (int)value;
     } else if (n == "count_mode") {
         ctx->count_mode = value != 0;
     } else if (n == "count_bits") {

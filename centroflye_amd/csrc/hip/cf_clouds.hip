@@ -13,6 +13,7 @@
 
 void cf_free_kmers(cf_ctx* c);
 void cf_free_clouds(cf_ctx* c);
+void cf_free_contig(cf_ctx* c);   // cf_map.hip
 void cf_free_gview(cf_ctx* c);
 
 #define CL_THREADS 256
@@ -487,6 +488,7 @@ int cf_filter_clouds(cf_ctx* ctx, uint32_t min_mult, uint32_t max_mult, int64_t*
         return rc;
     }
     cf_free_gview(ctx);
+    cf_free_contig(ctx);
     cf_release_t(ctx, ctx->d_cloud_ptr, (size_t)U + 1);
     cf_release_t(ctx, ctx->d_entries, (size_t)N);
     ctx->d_cloud_ptr = d_new_ptr;

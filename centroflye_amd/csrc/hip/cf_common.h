@@ -129,6 +129,16 @@ struct cf_ctx {
     uint32_t* d_unique_bits = nullptr;
     int64_t unique_words = 0;
 
+    // frozen contig of cf_contig_build (cf_map.hip): a CSR by k-mer rank of the positions of every frequent k-mer, and the
+    // coverage of the positions 0 .. max_pos; dropped with the clouds it was built from
+    bool have_contig = false;
+    int64_t* d_contig_ptr = nullptr;   // contig_K + 1
+    int32_t* d_contig_pos = nullptr;   // contig_pairs
+    int32_t* d_contig_cov = nullptr;   // contig_cov_n = max_pos + 1 (0 when nothing is covered)
+    int64_t contig_K = 0, contig_pairs = 0, contig_cov_n = 0;
+    int64_t contig_P = 0, contig_max_pos = 0, contig_n_freq = 0;
+    float contig_build_ms = 0.f, map_ms = 0.f;
+
     // host <-> device copies of the caller's (pageable) buffers go through pinned staging slots, one per copy thread
     // (cf_api.hip: cf_copy_h2d / cf_copy_d2h)
     static constexpr int kCopyThreads = 16;      // slots; CF_COPY_THREADS (1 .. 16, default 16) picks how many are used
@@ -169,7 +179,8 @@ struct cf_ctx {
     int place_slots_per_unit = 0; // cf_place2: score-region slots per unit of a read (0 = 48); doubled-up automatically when a region fills
     int place_l3 = 0;            // cf_place2: third level of the arg-max (best candidate per group of 64-read blocks): 1 = on; 0 / 2 = off (measured: no gain at 500 000 reads)
     int place_l3_shift = 0;      // cf_place2: log2 of the blocks per group (0 = 6: groups of 64 blocks = 4 096 reads; tests use small groups at small read sets)
-    int count_mode = 1;          // 1: sort and reduce (cf_count2.hip) when it applies; 0: the atomic table of round 1 (cf_count.hip)
+    int map_window = 0;          // cf_map: candidate starts (LDS score slots) a wave covers per pass over a read's entries (0 = 2048; tests force small windows)
+    int count_mode = 1;         // 1: sort and reduce (cf_count2.hip) when it applies; 0: the atomic table of round 1 (cf_count.hip)
     int count_bits = 0;          // bucket bits of the sort-and-reduce path; 0 = from the number of windows (tests force small / large values)
     int count_slots = 4096;
     int count_tile = 16;

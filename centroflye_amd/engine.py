@@ -334,6 +334,49 @@ class Engine:
                                              _ptr(out_s1)), "cf_place_reads")
         return out_read, out_pos, out_s0, out_s1
 
+    # ------------------------------------------------------------------ A10: batch mapping onto a frozen contig
+    def contig_build(self, reads, pos, min_cloud_kmer_freq=2):
+        """CloudContig(min_cloud_kmer_freq) + add_read(reads[b], pos[b]) for every backbone read, on the current clouds."""
+        reads = np.ascontiguousarray(reads, np.int64).reshape(-1)
+        pos = np.ascontiguousarray(pos, np.int64).reshape(-1)
+        if reads.size != pos.size:
+            raise ValueError("one position per backbone read")
+        self._check(self._lib.cf_contig_build(self._ctx, _ptr(reads) if reads.size else None, _ptr(pos) if pos.size else None,
+                                              reads.size, int(min_cloud_kmer_freq)), "cf_contig_build")
+
+    def contig_info(self):
+        """n_positions (P, the distinct covered positions), max_pos, n_freq_kmers, n_pairs, build_ms, map_ms."""
+        v = [C.c_int64() for _ in range(4)]
+        b, m = C.c_float(), C.c_float()
+        self._check(self._lib.cf_contig_info(self._ctx, *[C.byref(x) for x in v], C.byref(b), C.byref(m)), "cf_contig_info")
+        return dict(n_positions=v[0].value, max_pos=v[1].value, n_freq_kmers=v[2].value, n_pairs=v[3].value,
+                    build_ms=float(b.value), map_ms=float(m.value))
+
+    def contig_coverage(self):
+        """int32 coverage of the positions 0 .. max_pos (empty for an empty contig)."""
+        info = self.contig_info()
+        n = info["max_pos"] + 1 if info["n_positions"] else 0
+        cov = np.zeros(n, np.int32)
+        self._check(self._lib.cf_contig_coverage(self._ctx, _ptr(cov) if n else None, n), "cf_contig_coverage")
+        return cov
+
+    def map_reads(self, reads=None, threshold=(5, 10)):
+        """map_reads_fast on the contig of contig_build: (pos int64, s0, s1 int32) per query read (default: every read, in
+        order); pos = -1 for a read that does not map."""
+        if reads is None:
+            n, q = self.n_reads, None
+        else:
+            q = np.ascontiguousarray(reads, np.int64).reshape(-1)
+            n = q.size
+        pos = np.full(n, -1, np.int64)
+        s0 = np.zeros(n, np.int32)
+        s1 = np.zeros(n, np.int32)
+        if q is not None and n == 0:      # (a NULL read list means "all reads": an empty one is passed as a list of its own)
+            q = np.zeros(1, np.int64)
+        self._check(self._lib.cf_map_reads(self._ctx, _ptr(q) if q is not None else None, n, int(threshold[0]), int(threshold[1]),
+                                           _ptr(pos) if n else None, _ptr(s0) if n else None, _ptr(s1) if n else None), "cf_map_reads")
+        return pos, s0, s1
+
     # ------------------------------------------------------------------ self tests of primitives
     def selftest_sort(self, keys, bits=64):
         keys = np.ascontiguousarray(keys, np.uint64)

@@ -16,6 +16,8 @@
  *                      :131-149 (A6)
  *   cf_place_reads     scripts/cloud_contig.py:26-41, :87-95 (A8) and
  *                      scripts/read_placer.py:35-94 (A9)
+ *   cf_contig_build    scripts/cloud_contig.py:26-41 (CloudContig.add_read for every backbone read)
+ *   cf_map_reads       scripts/cloud_contig.py:87-95, :117-156 (map_reads_fast on the finished contig; A10)
  *
  * Conventions: plain pointers and sizes only; every function returns 0 or a negative
  * errno-style code and never throws or aborts; cf_last_error() gives the message; the
@@ -154,6 +156,31 @@ int cf_place_reads(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, int3
                    int32_t min_unit, int32_t min_inters, int32_t min_prop,
                    int64_t* out_read, int64_t* out_pos, int32_t* out_s0, int32_t* out_s1);
 
+/* A10: batch mapping onto a frozen contig (cf_map.hip).
+ * cf_contig_build = CloudContig(min_cloud_kmer_freq) followed by add_read(reads[b], pos[b]) for b < n (cloud_contig.py:9-41; the
+ * order plays no part in what is kept): on the current clouds, count[(p, x)] = backbone reads whose unit i holds k-mer x with
+ * pos + i == p; x is frequent when count[(p, x)] >= max(1, min_cloud_kmer_freq) at some p (:35-37); the contig keeps EVERY position
+ * of every frequent k-mer (kmer_positions, :33), the coverage of each position (:30) and max_pos (:20-24).  reads: distinct indices
+ * < R; pos >= 0; pos + units < 2^31; n = 0 gives a valid empty contig.  Errors (-22: duplicate or out-of-range reads, negative or
+ * too large positions, no clouds) leave the previous contig and the context as they were.  cf_build_clouds, cf_filter_clouds,
+ * cf_set_clouds, cf_set_kmers, cf_load_units and cf_load_reads drop the contig.
+ * cf_contig_info: n_positions = P = len(cloud_contig.clouds), the DISTINCT covered positions (a unit with an empty cloud covers its
+ * position, :31; P < max_pos + 1 when the coverage has a gap); max_pos (0 for an empty contig); n_freq_kmers = len(freq_kmers);
+ * n_pairs = the (k-mer, position) pairs map_reads_fast seeds from (:125-128); build_ms / map_ms = device time (HIP events) of the
+ * last cf_contig_build / cf_map_reads (map_ms 0 before the first).  Any pointer may be NULL.
+ * cf_contig_coverage: cov[p] for p <= max_pos (cap >= max_pos + 1; nothing is written for an empty contig).
+ * cf_map_reads = map_reads_fast(cloud_contig, reads, threshold = (t0, t1)) (:117-156) for the n query reads (reads == NULL: all R
+ * reads in order, n is ignored): for every frequent x, every position q of x and every (unit i of the read) holding x with q >= i,
+ * scores[q - i][i] += 1 (:87-95); among the starts s with s + units <= P (:135), s0 = units with a hit >= t0 and s1 = hits >= t1
+ * (:137-139) the maximum of (s0, s1, s) wins (:140-143).  out_pos = -1 (and s0 = s1 = 0) for a read with no such start.  A query
+ * read that is part of the backbone counts its own k-mers, as in the reference.  -22 before a contig exists. */
+int cf_contig_build(cf_ctx* ctx, const int64_t* reads, const int64_t* pos, int64_t n, int32_t min_cloud_kmer_freq);
+int cf_contig_info(cf_ctx* ctx, int64_t* n_positions, int64_t* max_pos, int64_t* n_freq_kmers, int64_t* n_pairs, float* build_ms,
+                   float* map_ms);
+int cf_contig_coverage(cf_ctx* ctx, int32_t* cov, int64_t cap);
+int cf_map_reads(cf_ctx* ctx, const int64_t* reads, int64_t n, int32_t t0, int32_t t1, int64_t* out_pos, int32_t* out_s0,
+                 int32_t* out_s1);
+
 int cf_get_stats(cf_ctx* ctx, cf_stats* out);
 int cf_get_times(cf_ctx* ctx, cf_times* out);
 
@@ -192,7 +219,7 @@ int cf_allreduce_unique(cf_ctx* ctx, int64_t* n_unique);
 /* Tuning knobs (defaults are chosen for gfx950): name in {"dist_block" (threads per workgroup, 0 = auto), "dist_wgs"
  * (workgroups per CU the LDS is split between, 0 = auto: by the pair emissions per first k-mer), "dist_slots" (LDS budget of the (b,d) table in 8-byte units, 0 = all that
  * is left), "dist_sketch" (0: every pair goes to the exact table), "dist_fill_pct", "dist_est_pct", "dist_stage", "dist_edge_chunk" (edge rows a workgroup reserves in the output per global atomic, 0 = 8192; tests use small chunks), "dist_int_thr" (0: the dominance test always divides in doubles; 1, the default: the literal 0.8 is tested as 5 cnt >= 4 total, which is the same predicate),
- * "dist_wide", "dist_post_atomics" (1: postings by a histogram and a fill pass of atomics instead of the sort), "dist_hot_cap" (tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan), "dist_sketch_bits" (bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the counters in the same LDS —, else 8; 8 forces bytes), "lut_shift" (the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1, the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0), "dist_hot_entries" (default 32768: first k-mers with more partner entries than this keep no list of hot slots during their inserts — it would overflow — and their filter scans the count fields; -1: always keep it), "dist_regions" (1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long reads take by themselves), "dist_dbits" (5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks need), "place_mode" (2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4; smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the hash-map path of rounds 1-3, cf_place.hip), "place_grid" / "place_block" (workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024), "place_row_words" (32 or 64 words per posting row, 0 = by the longest posting list), "place_slots_per_unit" (score-region slots per unit of a read, 0 = 48; grown automatically when a region fills), "place_l3" / "place_l3_shift" (1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily — built in round 5, measured neutral at 500 000 reads, off by default), "dist_region_bytes" (1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond 128 units do by themselves), "place_long_rescans" (default 2: a run of the region path whose reads average more than this many rescans of reads with more than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is handed to the hash-map path; -1: at the first look, tests), "place_cmap_bits" (log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 = cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load), "place_chunk", "place_fused" (place_mode 1: cloud entries per wave step; 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list and a third kernel per greedy iteration), "count_mode" (1: A1 by sort and reduce, 0: the atomic table), "count_bits" (bucket bits of the former, 0 = auto), "count_slots", "count_tile", "count_skip_exotic" (1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads), "comm_round_bytes" (bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds), "comm_self_p2p" (1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a one-GPU box runs the whole p2p path)}.  Results never depend on them (tests/test_gpu_parity.py). */
+ * "dist_wide", "dist_post_atomics" (1: postings by a histogram and a fill pass of atomics instead of the sort), "dist_hot_cap" (tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan), "dist_sketch_bits" (bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the counters in the same LDS —, else 8; 8 forces bytes), "lut_shift" (the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1, the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0), "dist_hot_entries" (default 32768: first k-mers with more partner entries than this keep no list of hot slots during their inserts — it would overflow — and their filter scans the count fields; -1: always keep it), "dist_regions" (1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long reads take by themselves), "dist_dbits" (5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks need), "place_mode" (2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4; smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the hash-map path of rounds 1-3, cf_place.hip), "place_grid" / "place_block" (workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024), "place_row_words" (32 or 64 words per posting row, 0 = by the longest posting list), "place_slots_per_unit" (score-region slots per unit of a read, 0 = 48; grown automatically when a region fills), "place_l3" / "place_l3_shift" (1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily — built in round 5, measured neutral at 500 000 reads, off by default), "dist_region_bytes" (1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond 128 units do by themselves), "place_long_rescans" (default 2: a run of the region path whose reads average more than this many rescans of reads with more than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is handed to the hash-map path; -1: at the first look, tests), "place_cmap_bits" (log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 = cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load), "place_chunk", "place_fused" (place_mode 1: cloud entries per wave step; 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list and a third kernel per greedy iteration), "count_mode" (1: A1 by sort and reduce, 0: the atomic table), "count_bits" (bucket bits of the former, 0 = auto), "count_slots", "count_tile", "count_skip_exotic" (1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads), "comm_round_bytes" (bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds), "map_window" (candidate starts — LDS score slots — that cf_map_reads covers per pass over a read's cloud entries, 0 = 2048, at most 4096; a read whose hits span more starts takes several passes, tests force that with tiny windows), "comm_self_p2p" (1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a one-GPU box runs the whole p2p path)}.  Results never depend on them (tests/test_gpu_parity.py). */
 int cf_set_param(cf_ctx* ctx, const char* name, int64_t value);
 
 /* Self-tests of the device primitives against host results (used by tests/ only). */
