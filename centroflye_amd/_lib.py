@@ -70,6 +70,9 @@ PROTOTYPES = {
     "cf_contig_info": (C.c_int, [_P, _PI64, _PI64, _PI64, _PI64, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cf_contig_coverage": (C.c_int, [_P, _P, _I64]),
     "cf_map_reads": (C.c_int, [_P, _P, _I64, _I32, _I32, _P, _P, _P]),
+    "cf_score_reads": (C.c_int, [_P, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P]),
+    "cf_contig_spread": (C.c_int, [_P, _I64, _P, _I64, _PI64]),
+    "cf_contig_exact_info": (C.c_int, [_P, _PI64, C.POINTER(C.c_float)]),
     "cf_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "cf_get_times": (C.c_int, [_P, C.POINTER(Times)]),
     "cf_set_param": (C.c_int, [_P, C.c_char_p, _I64]),

@@ -138,6 +138,12 @@ struct cf_ctx {
     int64_t contig_K = 0, contig_pairs = 0, contig_cov_n = 0;
     int64_t contig_P = 0, contig_max_pos = 0, contig_n_freq = 0;
     float contig_build_ms = 0.f, map_ms = 0.f;
+    // the same contig by rank, but only the positions where the k-mer is frequent (freq_clouds, cloud_contig.py:35-36): what
+    // the exact scorer of cf_score.hip intersects with; built and dropped together with the CSR above
+    int64_t* d_exact_ptr = nullptr;    // contig_K + 1
+    int32_t* d_exact_pos = nullptr;    // exact_pairs
+    int64_t exact_pairs = 0;
+    float score_ms = 0.f;
 
     // host <-> device copies of the caller's (pageable) buffers go through pinned staging slots, one per copy thread
     // (cf_api.hip: cf_copy_h2d / cf_copy_d2h)

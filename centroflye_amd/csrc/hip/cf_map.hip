@@ -10,7 +10,8 @@
 //                     cloud_contig.py:33 / :126-128 — become one CSR row, ascending; rows of other ranks are empty.
 //                     Coverage counts units, so a unit with an empty cloud still covers its position (:31), and
 //                     P = the number of covered positions (len(cloud_contig.clouds)), which is not max_pos + 1 when the
-//                     coverage has a gap.
+//                     coverage has a gap.  From the same sorted records a second CSR keeps only the positions where the rank
+//                     IS frequent (a run of at least f records: freq_clouds, :35-36) for the exact scorer of cf_score.hip.
 //   cf_map_reads      one wave per query read.  The candidate starts s = q - i of the read (q a contig position of a k-mer of
 //                     unit i, q >= i, s + n <= P) are scored in windows of `map_window` LDS slots indexed by s - lo: the units
 //                     are taken one after another, a per-slot stamp (last unit seen, by a returning max) tells whether a hit
@@ -28,6 +29,9 @@ void cf_free_contig(cf_ctx* c) {
     cf_release_t(c, c->d_contig_ptr, (size_t)c->contig_K + 1);
     cf_release_t(c, c->d_contig_pos, (size_t)c->contig_pairs);
     cf_release_t(c, c->d_contig_cov, (size_t)c->contig_cov_n);
+    cf_release_t(c, c->d_exact_ptr, (size_t)c->contig_K + 1);
+    cf_release_t(c, c->d_exact_pos, (size_t)c->exact_pairs);
+    c->exact_pairs = 0;
     c->contig_K = c->contig_pairs = c->contig_cov_n = 0;
     c->contig_P = c->contig_max_pos = c->contig_n_freq = 0;
     c->have_contig = false;
@@ -90,6 +94,17 @@ cf_contig_flag_kernel(const unsigned long long* __restrict__ recs, int64_t n, in
     }
 }
 
+// flag[i] = record i is the first of a run that is at least f long: (rank, position) is an entry of freq_clouds, one entry of
+// the exact CSR (the test of cf_contig_freq_kernel, kept per position instead of per rank)
+__global__ void __launch_bounds__(256)
+cf_contig_exact_flag_kernel(const unsigned long long* __restrict__ recs, int64_t n, int64_t f, uint32_t* __restrict__ flag) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long x = recs[i];
+        const bool head = i == 0 || recs[i - 1] != x;
+        flag[i] = (head && f - 1 < n - i && recs[i + (f - 1)] == x) ? 1u : 0u;
+    }
+}
+
 __global__ void __launch_bounds__(256)
 cf_contig_fill_kernel(const unsigned long long* __restrict__ recs, int64_t n, int pbits, const uint32_t* __restrict__ flag,
                       const int64_t* __restrict__ idx, int32_t* __restrict__ cpos) {
@@ -98,10 +113,11 @@ cf_contig_fill_kernel(const unsigned long long* __restrict__ recs, int64_t n, in
         if (flag[i]) cpos[idx[i]] = (int32_t)(recs[i] & pmask);
 }
 
-// contig_ptr[k] = CSR entries of the ranks below k = idx of the first record with rank >= k (idx counts the flags before it)
+// contig_ptr[k] = CSR entries of the ranks below k = idx of the first record with rank >= k (idx counts the flags before it);
+// first[k] = that record itself, for the second CSR over the same records (cf_contig_ptr_of_first_kernel)
 __global__ void __launch_bounds__(256)
 cf_contig_ptr_kernel(const unsigned long long* __restrict__ recs, int64_t n, int pbits, const int64_t* __restrict__ idx,
-                     int64_t n_pairs, int64_t K, int64_t* __restrict__ cptr) {
+                     int64_t n_pairs, int64_t K, int64_t* __restrict__ cptr, int64_t* __restrict__ first) {
     for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= K; k += (int64_t)gridDim.x * blockDim.x) {
         const unsigned long long key = (unsigned long long)k << pbits;
         int64_t lo = 0, hi = n;      // first record >= key
@@ -110,6 +126,16 @@ cf_contig_ptr_kernel(const unsigned long long* __restrict__ recs, int64_t n, int
             if (recs[mid] < key) lo = mid + 1; else hi = mid;
         }
         cptr[k] = lo < n ? idx[lo] : n_pairs;
+        first[k] = lo;
+    }
+}
+
+// ptr[k]: the first record with rank >= k (found above) -> the offset of another scan at that record: no second search
+__global__ void __launch_bounds__(256)
+cf_contig_ptr_of_first_kernel(int64_t* __restrict__ ptr, int64_t K, int64_t n, const int64_t* __restrict__ idx, int64_t n_pairs) {
+    for (int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; k <= K; k += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t lo = ptr[k];
+        ptr[k] = lo < n ? idx[lo] : n_pairs;
     }
 }
 
@@ -236,7 +262,7 @@ static int contig_build(cf_ctx* ctx, const int64_t* reads, const int64_t* pos, i
     int64_t *d_breads = nullptr, *d_bpos = nullptr, *d_sizes = nullptr, *d_off = nullptr, *d_idx = nullptr;
     unsigned long long *d_recs = nullptr, *d_tmp = nullptr, *d_counts = nullptr, *sorted = nullptr;
     uint32_t *d_freq = nullptr, *d_flag = nullptr;
-    int64_t n_rec = 0, n_pairs = 0;
+    int64_t n_rec = 0, n_pairs = 0, n_exact = 0;
     unsigned long long h_counts[2] = {0, 0};
     int rc = 0;
     ctx->contig_K = K;
@@ -244,10 +270,12 @@ static int contig_build(cf_ctx* ctx, const int64_t* reads, const int64_t* pos, i
     do {
         if ((rc = cf_alloc_t(ctx, &ctx->d_contig_ptr, (size_t)K + 1, "contig_ptr"))) break;
         if ((rc = cf_alloc_t(ctx, &ctx->d_contig_cov, (size_t)ctx->contig_cov_n, "contig coverage"))) break;
+        if ((rc = cf_alloc_t(ctx, &ctx->d_exact_ptr, (size_t)K + 1, "exact contig_ptr"))) break;
         if ((rc = cf_alloc_t(ctx, &d_freq, (size_t)K + 1, "frequent ranks"))) break;
         if ((rc = cf_alloc_t(ctx, &d_counts, 2, "contig counters"))) break;
         hipError_t e = hipMemsetAsync(ctx->d_contig_ptr, 0, (size_t)(K + 1) * 8, ctx->stream);
         if (e == hipSuccess && ctx->contig_cov_n) e = hipMemsetAsync(ctx->d_contig_cov, 0, (size_t)ctx->contig_cov_n * 4, ctx->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(ctx->d_exact_ptr, 0, (size_t)(K + 1) * 8, ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_freq, 0, (size_t)(K + 1) * 4, ctx->stream);
         if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, 16, ctx->stream);
         if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_contig_build memset: ") + hipGetErrorString(e)); break; }
@@ -287,9 +315,21 @@ static int contig_build(cf_ctx* ctx, const int64_t* reads, const int64_t* pos, i
                 hipLaunchKernelGGL(cf_contig_fill_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec,
                                    pbits, (const uint32_t*)d_flag, (const int64_t*)d_idx, ctx->d_contig_pos);
             hipLaunchKernelGGL(cf_contig_ptr_kernel, dim3((unsigned)cf_grid_for(K + 1, 256, max_grid * 4)), dim3(256), 0, ctx->stream,
-                               (const unsigned long long*)sorted, n_rec, pbits, (const int64_t*)d_idx, n_pairs, K, ctx->d_contig_ptr);
+                               (const unsigned long long*)sorted, n_rec, pbits, (const int64_t*)d_idx, n_pairs, K, ctx->d_contig_ptr,
+                               ctx->d_exact_ptr);
             hipLaunchKernelGGL(cf_contig_nonzero_kernel, dim3((unsigned)cf_grid_for(K, 256, max_grid)), dim3(256), 64, ctx->stream,
                                (const uint32_t*)d_freq, K, d_counts + 1);
+            // the exact CSR from the same sorted records; the flags and offsets of the CSR above are done with (stream order)
+            hipLaunchKernelGGL(cf_contig_exact_flag_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted,
+                               n_rec, f, d_flag);
+            if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_flag, d_idx, n_rec, &n_exact))) break;
+            ctx->exact_pairs = n_exact;
+            if ((rc = cf_alloc_t(ctx, &ctx->d_exact_pos, (size_t)n_exact, "exact contig positions"))) break;
+            if (n_exact)
+                hipLaunchKernelGGL(cf_contig_fill_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec,
+                                   pbits, (const uint32_t*)d_flag, (const int64_t*)d_idx, ctx->d_exact_pos);
+            hipLaunchKernelGGL(cf_contig_ptr_of_first_kernel, dim3((unsigned)cf_grid_for(K + 1, 256, max_grid * 4)), dim3(256), 0, ctx->stream,
+                               ctx->d_exact_ptr, K, n_rec, (const int64_t*)d_idx, n_exact);
         }
         if (ctx->contig_cov_n)
             hipLaunchKernelGGL(cf_contig_nonzero_kernel, dim3((unsigned)cf_grid_for(ctx->contig_cov_n, 256, max_grid)), dim3(256), 64, ctx->stream,
@@ -348,7 +388,7 @@ int cf_contig_build(cf_ctx* ctx, const int64_t* reads, const int64_t* pos, int64
     CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     CF_HIP(hipEventSynchronize(ctx->ev1));
     CF_HIP(hipEventElapsedTime(&ctx->contig_build_ms, ctx->ev0, ctx->ev1));
-    ctx->map_ms = 0.f;
+    ctx->map_ms = ctx->score_ms = 0.f;
     return 0;
 }
 

@@ -377,6 +377,49 @@ class Engine:
                                            _ptr(pos) if n else None, _ptr(s0) if n else None, _ptr(s1) if n else None), "cf_map_reads")
         return pos, s0, s1
 
+    def score_reads(self, reads=None, lo=None, hi=None, min_unit=2, min_inters=10):
+        """calc_inters_score(read, lo, hi, min_unit, min_inters) on the contig of contig_build, the EXACT scorer (only k-mers
+        that are frequent at the position count): (pos int64, s0, s1 int32) per query read (default: every read, in order);
+        pos = -1 for None.  lo, hi: one start per query or a scalar; default 0 and max_pos - units + 1 (map_reads' range)."""
+        if reads is None:
+            n, q = self.n_reads, None
+        else:
+            q = np.ascontiguousarray(reads, np.int64).reshape(-1)
+            n = q.size
+
+        def bound(v):
+            if v is None:
+                return None
+            v = np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.int64), (n,)) if np.ndim(v) == 0 else v, np.int64).reshape(-1)
+            if v.size != n:
+                raise ValueError("one first / last start per query read")
+            return v if n else np.zeros(1, np.int64)
+        lo, hi = bound(lo), bound(hi)
+        pos = np.full(n, -1, np.int64)
+        s0 = np.zeros(n, np.int32)
+        s1 = np.zeros(n, np.int32)
+        if q is not None and n == 0:      # (a NULL read list means "all reads": an empty one is passed as a list of its own)
+            q = np.zeros(1, np.int64)
+        self._check(self._lib.cf_score_reads(self._ctx, _ptr(q) if q is not None else None, n, _ptr(lo) if lo is not None else None,
+                                             _ptr(hi) if hi is not None else None, int(min_unit), int(min_inters),
+                                             _ptr(pos) if n else None, _ptr(s0) if n else None, _ptr(s1) if n else None), "cf_score_reads")
+        return pos, s0, s1
+
+    def contig_spread(self, max_npos=5):
+        """get_spread_kmers(max_npos): the ranks (int32, ascending) of the frequent k-mers with more than max_npos positions."""
+        n = C.c_int64()
+        self._check(self._lib.cf_contig_spread(self._ctx, int(max_npos), None, 0, C.byref(n)), "cf_contig_spread")
+        ranks = np.zeros(n.value, np.int32)
+        if n.value:
+            self._check(self._lib.cf_contig_spread(self._ctx, int(max_npos), _ptr(ranks), ranks.size, C.byref(n)), "cf_contig_spread")
+        return ranks
+
+    def contig_exact_info(self):
+        """n_exact_pairs (the (k-mer, position) pairs of freq_clouds), score_ms (device time of the last score_reads)."""
+        v, m = C.c_int64(), C.c_float()
+        self._check(self._lib.cf_contig_exact_info(self._ctx, C.byref(v), C.byref(m)), "cf_contig_exact_info")
+        return dict(n_exact_pairs=v.value, score_ms=float(m.value))
+
     # ------------------------------------------------------------------ self tests of primitives
     def selftest_sort(self, keys, bits=64):
         keys = np.ascontiguousarray(keys, np.uint64)

@@ -18,6 +18,8 @@
  *                      scripts/read_placer.py:35-94 (A9)
  *   cf_contig_build    scripts/cloud_contig.py:26-41 (CloudContig.add_read for every backbone read)
  *   cf_map_reads       scripts/cloud_contig.py:87-95, :117-156 (map_reads_fast on the finished contig; A10)
+ *   cf_score_reads     scripts/cloud_contig.py:46-76 (calc_inters_score), :98-114 (map_reads), :146-155 (debug)
+ *   cf_contig_spread   scripts/cloud_contig.py:78-84 (get_spread_kmers)
  *
  * Conventions: plain pointers and sizes only; every function returns 0 or a negative
  * errno-style code and never throws or aborts; cf_last_error() gives the message; the
@@ -180,6 +182,30 @@ int cf_contig_info(cf_ctx* ctx, int64_t* n_positions, int64_t* max_pos, int64_t*
 int cf_contig_coverage(cf_ctx* ctx, int32_t* cov, int64_t cap);
 int cf_map_reads(cf_ctx* ctx, const int64_t* reads, int64_t n, int32_t t0, int32_t t1, int64_t* out_pos, int32_t* out_s0,
                  int32_t* out_s1);
+
+/* A10, the exact scorer (cf_score.hip).  cf_contig_build also keeps freq_clouds (cloud_contig.py:35-36): F(p) = { x :
+ * count[(p, x)] >= max(1, min_cloud_kmer_freq) }, the k-mers that are frequent AT p — not every position of a frequent k-mer,
+ * which is what cf_map_reads seeds from.
+ * cf_score_reads = calc_inters_score(read, min_position = lo[j], max_position = hi[j], min_unit, min_inters) (:46-76) for the n
+ * query reads (reads == NULL: all R reads in order, n is ignored; lo == NULL: 0; hi == NULL: max_pos - units + 1 per read, the
+ * range of map_reads, :103).  The score of a read of `units` units at start s: for i < min(units, max_pos - s + 1) (:57: a read
+ * that overhangs max_pos is truncated, not refused; the limit is max_pos, never P), h_i = |cloud_i & F(s + i)|, s0 = #{i :
+ * h_i >= 1}, s1 = sum h_i (:60-66).  A start beyond max_pos scores (0, 0).  Among the starts lo <= s <= hi with s0 >= min_unit and
+ * s1 >= min_inters the maximum of (s0, s1, s) wins (:71-75, `>=`: the rightmost of equals).  Starts without a hit take part: with
+ * min_unit <= 0 and min_inters <= 0 a read with no hit, or with no units, gets out_pos = hi and the score (0, 0).  out_pos = -1
+ * (s0 = s1 = 0) stands for None: no start qualifies, or lo > hi.  hi may lie beyond max_pos.  Defined here: lo < 0 is refused.
+ * map_reads (:98-114) is cf_score_reads with lo = hi = NULL and (min_unit, min_inters) = (2, 10), whatever its threshold is,
+ * followed on the host by: keep the read iff out_pos == 0 or (s0, s1) > threshold (a strict tuple compare, :107).
+ * Errors (-22: no contig, a read out of range, lo < 0) leave the context and the contig as they were.
+ * cf_contig_spread = get_spread_kmers(max_npos) (:78-84): the ranks of the frequent k-mers with more than max_npos positions in
+ * kmer_positions (ALL their positions, the pairs cf_map_reads seeds from), ascending.  *n_out = their number; ranks == NULL asks
+ * for the number alone; otherwise cap >= *n_out ranks are written (-22, with *n_out set, when they do not fit).
+ * cf_contig_exact_info: n_exact_pairs = sum over p of |F(p)|; score_ms = device time (HIP events) of the last cf_score_reads (0
+ * before the first).  Either pointer may be NULL. */
+int cf_score_reads(cf_ctx* ctx, const int64_t* reads, int64_t n, const int64_t* lo, const int64_t* hi, int32_t min_unit,
+                   int32_t min_inters, int64_t* out_pos, int32_t* out_s0, int32_t* out_s1);
+int cf_contig_spread(cf_ctx* ctx, int64_t max_npos, int32_t* ranks, int64_t cap, int64_t* n_out);
+int cf_contig_exact_info(cf_ctx* ctx, int64_t* n_exact_pairs, float* score_ms);
 
 int cf_get_stats(cf_ctx* ctx, cf_stats* out);
 int cf_get_times(cf_ctx* ctx, cf_times* out);
