@@ -73,6 +73,9 @@ PROTOTYPES = {
     "cf_score_reads": (C.c_int, [_P, _P, _I64, _P, _P, _I32, _I32, _P, _P, _P]),
     "cf_contig_spread": (C.c_int, [_P, _I64, _P, _I64, _PI64]),
     "cf_contig_exact_info": (C.c_int, [_P, _PI64, C.POINTER(C.c_float)]),
+    "cf_edit_distances": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, C.POINTER(C.c_float)]),
+    "cf_hpc": (C.c_int, [_P, _P, _P, _I64, _P, _P]),
+    "cf_edit_info": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _PI64]),
     "cf_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "cf_get_times": (C.c_int, [_P, C.POINTER(Times)]),
     "cf_set_param": (C.c_int, [_P, C.c_char_p, _I64]),

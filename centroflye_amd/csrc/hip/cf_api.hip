@@ -304,6 +304,7 @@ void cf_destroy(cf_ctx* ctx) {
     { std::lock_guard<std::mutex> g(g_pool_lock); g_contexts.erase(std::remove(g_contexts.begin(), g_contexts.end(), ctx), g_contexts.end()); }
     (void)hipSetDevice(ctx->device);
     (void)cf_comm_free(ctx);
+    cf_edit_free(ctx);
     cf_free_edges(ctx);
     cf_free_clouds(ctx);
     cf_free_kmers(ctx);
@@ -574,6 +575,9 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
     } else if (n == "map_window") {
         if (value < 0 || value > 4096) return cf_fail(ctx, -22, "map_window out of range (0 = default, 1 .. 4096: 12 bytes of LDS per slot)");
         ctx->map_window = (int)value;
+    } else if (n == "edit_lds_diags") {
+        if (value < 0 || value > 16384) return cf_fail(ctx, -22, "edit_lds_diags out of range (0 = default, 1 .. 16384: 8 bytes of LDS per diagonal)");
+        ctx->edit_lds_diags = (int)value;
     } else if (n == "count_mode") {
         ctx->count_mode = value != 0;
     } else if (n == "count_bits") {

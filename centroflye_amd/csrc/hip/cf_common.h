@@ -145,6 +145,12 @@ struct cf_ctx {
     int64_t exact_pairs = 0;
     float score_ms = 0.f;
 
+    // sequences left resident by cf_hpc (cf_edit.hip): the caller's bytes, their homopolymer-compressed form right behind them
+    // and the padding; cf_edit_distances with bytes == NULL compares strings of these edit_len bytes
+    uint8_t* d_edit = nullptr;
+    size_t edit_cap = 0;
+    int64_t edit_len = 0;
+
     // host <-> device copies of the caller's (pageable) buffers go through pinned staging slots, one per copy thread
     // (cf_api.hip: cf_copy_h2d / cf_copy_d2h)
     static constexpr int kCopyThreads = 16;      // slots; CF_COPY_THREADS (1 .. 16, default 16) picks how many are used
@@ -186,6 +192,7 @@ struct cf_ctx {
     int place_l3 = 0;            // cf_place2: third level of the arg-max (best candidate per group of 64-read blocks): 1 = on; 0 / 2 = off (measured: no gain at 500 000 reads)
     int place_l3_shift = 0;      // cf_place2: log2 of the blocks per group (0 = 6: groups of 64 blocks = 4 096 reads; tests use small groups at small read sets)
     int map_window = 0;          // cf_map: candidate starts (LDS score slots) a wave covers per pass over a read's entries (0 = 2048; tests force small windows)
+    int edit_lds_diags = 0;      // cf_edit: diagonals per wavefront array above which a pair's wavefronts live in HBM, not LDS (0 = 16384; tests force small values)
     int count_mode = 1;         // 1: sort and reduce (cf_count2.hip) when it applies; 0: the atomic table of round 1 (cf_count.hip)
     int count_bits = 0;          // bucket bits of the sort-and-reduce path; 0 = from the number of windows (tests force small / large values)
     int count_slots = 4096;
@@ -244,6 +251,7 @@ static inline int cf_grid_for(int64_t items, int per_block, int max_blocks) {
 }
 
 extern "C" int cf_comm_free(cf_ctx* ctx);   // cf_exchange.hip
+void cf_edit_free(cf_ctx* ctx);              // cf_edit.hip: drops the sequences cf_hpc left resident
 
 // primitives (cf_prims.hip)
 int cf_scan_exclusive_i64(cf_ctx* ctx, const int64_t* d_in, int64_t* d_out, int64_t n, int64_t* total);

@@ -1,17 +1,76 @@
-"""Read-unit export for polishing: the consumer of ``read_positions.csv``.
+"""The polisher stage: per-position read-unit export, one Flye run per position, and the assembly
+of the polished units into the final sequence of every iteration with its report.
 
-Mirror of the part of the reference's ``scripts/eltr_polisher.py`` that is pure data movement:
-``read_reported_positions`` (:19-30), ``ELTR_Polisher.__init__`` (:33-51, the ``max_pos`` default), ``map_pos2read``
-(:53-66) and ``export_read_units`` (:68-97).  The grouping and the FASTA writing run in the compiled host library
-(``cfh_export_read_units``: one pass over the packed units, positions written by a thread pool).  What follows in the
-reference — Flye runs per position (:99-113), re-reading Flye's output and edlib comparisons (:115-144) — is outside
-this repository's scope and is not here: the script ends with the exported files.
+Mirror of the reference's ``scripts/eltr_polisher.py``.  The pure data movement — ``read_reported_positions`` (:19-30),
+``ELTR_Polisher.__init__`` (:33-51, the ``max_pos`` default), ``map_pos2read`` (:53-66) and ``export_read_units`` (:68-97) —
+groups and writes in the compiled host library (``cfh_export_read_units``: one pass over the packed units, positions written
+by a thread pool).  ``run_polishing`` (:99-114) starts the same Flye command per position.  ``read_polishing`` (:116-131),
+``compare_polished_sequences`` (:133-146) and ``export_results`` (:148-157) are ``assemble``: the final sequences go to the
+device once, one ``cf_hpc`` call compresses them all and one ``cf_edit_distances`` call gives every distance of ``report.txt``
+(DESIGN §16).
+
+Without ``--num-iters``, ``--polish`` or ``--assemble-only`` the script ends with the exported files, as it always did.
 """
 import argparse
 import math
 import os
+import subprocess
+import sys
+
+import numpy as np
 
 from . import ncrf_parser
+
+DEFAULT_MAX_EDIT_DISTANCE = 32768      # --max-edit-distance (65 536 took 2.5 s to give up on two unrelated 1-Mb strings, this 0.64 s)
+
+
+class PolishingError(RuntimeError):
+    """What makes the reference raise in read_polishing: a polished_i.fasta that is missing or empty, a position without reads."""
+
+
+def read_first_record(fn):
+    """The sequence of the first record of a FASTA file (the reference's read_bio_seq, utils/bio.py:11-13): lines joined."""
+    try:
+        f = open(fn)
+    except OSError as e:
+        raise PolishingError(f"{fn}: {e.strerror or e}") from None
+    with f:
+        lines, inside = [], False
+        for ln in f:
+            if ln[:1] == ">":
+                if inside:
+                    break
+                inside = True
+            elif inside:
+                lines.append(ln.strip())
+    if not inside:
+        raise PolishingError(f"{fn}: no FASTA record")
+    return "".join(lines).replace(" ", "")
+
+
+def alignment_dict(distance, query, target):
+    """What python-edlib 1.2.4 returns for edlib.align(query, target) (mode NW, task distance) and the reference prints."""
+    if distance < 0:
+        return {'editDistance': -1, 'alphabetLength': len(set(query) | set(target)), 'locations': None, 'cigar': None}
+    return {'editDistance': int(distance), 'alphabetLength': len(set(query) | set(target)), 'locations': [(None, len(target) - 1)],
+            'cigar': None}
+
+
+def _write_atomically(files):
+    """{path: text}: every file through path.tmp, renamed only when all are written."""
+    tmp = []
+    try:
+        for fn, text in files.items():
+            with open(fn + ".tmp", "w") as f:
+                f.write(text)
+            tmp.append(fn)
+    except BaseException:
+        for fn in tmp + [fn]:
+            if os.path.exists(fn + ".tmp"):
+                os.remove(fn + ".tmp")
+        raise
+    for fn in tmp:
+        os.replace(fn + ".tmp", fn)
 
 
 def read_reported_positions(read_positions_fn):
@@ -68,8 +127,112 @@ class ELTR_Polisher:
         return {p: (os.path.join(self.params.outdir, f'pos_{p}', 'read_units.fasta'),
                     os.path.join(self.params.outdir, f'pos_{p}', 'median_read_unit.fasta')) for p in positions}
 
+    def unit_filenames(self, pos2read):
+        """{position: (units_fn, median_read_unit_fn)} as export_read_units returns it, without exporting (--assemble-only)."""
+        return {p: (os.path.join(self.params.outdir, f'pos_{p}', 'read_units.fasta'),
+                    os.path.join(self.params.outdir, f'pos_{p}', 'median_read_unit.fasta')) for p in pos2read}
+
+    def run_polishing(self, read_unit_filenames):
+        """One Flye process per position (reference :99-114, the same argument vector)."""
+        p = self.params
+        for pos in range(min(read_unit_filenames), max(read_unit_filenames) + 1):
+            if pos not in read_unit_filenames:
+                raise PolishingError(f"position {pos} has no reads")
+            units_fn, median_read_unit_fn = read_unit_filenames[pos]
+            cmd = [getattr(p, "flye_bin", "flye"), f'--{getattr(p, "error_mode", "nano")}-raw', units_fn, '--polish-target', median_read_unit_fn,
+                   '-i', getattr(p, "num_iters", None) or 4, '-t', getattr(p, "num_threads", 16), '-o', os.path.dirname(units_fn)]
+            cmd = [str(x) for x in cmd]
+            print(' '.join(cmd))
+            subprocess.check_call(cmd)
+
+    def read_polishing(self, read_unit_filenames, num_iters):
+        """{position: [polished sequence of iteration 1 .. num_iters]} (reference :116-126) after the checks that make the
+        reference raise: every position of min .. max has reads, every polished_i.fasta is there."""
+        if not read_unit_filenames:
+            raise PolishingError("no position has reads")
+        for pos in range(min(read_unit_filenames), max(read_unit_filenames) + 1):
+            if pos not in read_unit_filenames:
+                raise PolishingError(f"position {pos} has no reads")
+        return {pos: [read_first_record(os.path.join(os.path.dirname(fns[0]), f'polished_{i}.fasta')) for i in range(1, num_iters + 1)]
+                for pos, fns in sorted(read_unit_filenames.items())}
+
+    def assemble(self, read_unit_filenames, num_iters=None, max_edit_distance=None, position_report=None):
+        """final_sequence_i.fasta, final_sequence_hpc_i.fasta and report.txt (reference :116-157) — and position_changes.csv —
+        from the polished_i.fasta of every position.  Returns the distances [(plain, compressed) for i = 1 .. num_iters - 1],
+        -1 standing for "above the limit"."""
+        from . import session
+        p = self.params
+        num_iters = int(num_iters if num_iters is not None else (getattr(p, "num_iters", None) or 4))
+        limit = int(max_edit_distance if max_edit_distance is not None else getattr(p, "max_edit_distance", DEFAULT_MAX_EDIT_DISTANCE))
+        position_report = getattr(p, "position_report", False) if position_report is None else position_report
+        if num_iters < 1:
+            raise PolishingError("--num-iters must be at least 1")
+        polished = self.read_polishing(read_unit_filenames, num_iters)
+        positions = sorted(polished)
+        finals = ["".join(polished[pos][i] for pos in positions).encode("latin-1") for i in range(num_iters)]
+        e = session.engine()
+        off = np.zeros(num_iters + 1, np.int64)
+        np.cumsum([len(s) for s in finals], out=off[1:])
+        hpc, hpc_off = e.hpc(b"".join(finals), off)
+        hpc = hpc.tobytes()
+        finals_hpc = [hpc[hpc_off[i]:hpc_off[i + 1]] for i in range(num_iters)]
+        dists = []
+        if num_iters > 1:
+            # the strings of either side of a pair list lie back to back, so ONE call takes the pairs (i, i + 1) of the plain
+            # sequences, two pairs that join the runs — (the last plain sequence, nothing) and (nothing, the first compressed
+            # one): an empty string costs no step — and the pairs of the compressed sequences, all on the bytes cf_hpc left
+            # on the device: its input followed by its output
+            h = off[-1] + hpc_off
+            a_off = np.concatenate([off, off[-1:], h[1:num_iters]])
+            b_off = np.concatenate([off[1:], off[-1:], h[1:]])
+            d, self.edit_ms = e.edit_distances(None, a_off, b_off, limit)
+            dists = [(int(d[i]), int(d[num_iters + 1 + i])) for i in range(num_iters - 1)]
+        files = {}
+        lines = []
+        for i in range(1, num_iters):
+            for what, seqs, dist in (("polishing", finals, dists[i - 1][0]), ("homopolymer compressed polishing", finals_hpc, dists[i - 1][1])):
+                lines.append(f'Alignment {what} seq {i} vs {i+1}:')
+                lines.append(str(alignment_dict(dist, seqs[i - 1], seqs[i])))
+                if dist < 0:
+                    print(f"eltr_polisher: the {what} sequences {i} and {i+1} differ in more than {limit} places (--max-edit-distance): "
+                          "reported as -1", file=sys.stderr)
+        files[os.path.join(p.outdir, 'report.txt')] = "".join(ln + "\n" for ln in lines)
+        for i in range(1, num_iters + 1):
+            files[os.path.join(p.outdir, f'final_sequence_{i}.fasta')] = f'>polished_repeat_{i}\n{finals[i - 1].decode("latin-1")}\n'
+            files[os.path.join(p.outdir, f'final_sequence_hpc_{i}.fasta')] = f'>polished_repeat_{i}\n{finals_hpc[i - 1].decode("latin-1")}\n'
+        if position_report:
+            files[os.path.join(p.outdir, 'position_changes.csv')] = self.position_changes(polished, num_iters, limit)
+        _write_atomically(files)
+        return dists
+
+    def position_changes(self, polished, num_iters, limit):
+        """Lines `iteration position distance`: the distance between polished_i and polished_{i+1} of every position, all
+        pairs in one cf_edit_distances call."""
+        from . import session
+        positions = sorted(polished)
+        if num_iters < 2 or not positions:
+            return ""
+        # iteration-major: the strings of iteration i + 1 follow those of iteration i, so a_off = off[:-n], b_off = off[n:]
+        seqs = [polished[pos][i].encode("latin-1") for i in range(num_iters) for pos in positions]
+        n = len(positions)
+        off = np.zeros(len(seqs) + 1, np.int64)
+        np.cumsum([len(s) for s in seqs], out=off[1:])
+        d, _ = session.engine().edit_distances(b"".join(seqs), off[:len(off) - n], off[n:], limit)
+        return "".join(f"{i + 1} {pos} {int(d[i * n + j])}\n" for i in range(num_iters - 1) for j, pos in enumerate(positions))
+
     def run(self, export_only=True):
-        return self.export_read_units(self.map_pos2read())
+        """export_only (the default, and all that a params object without the new attributes asks for): the export alone.
+        Otherwise the reference's run(): export, Flye per position, assemble."""
+        pos2read = self.map_pos2read()
+        if getattr(self.params, "assemble_only", False):
+            return self.assemble(self.unit_filenames(pos2read))
+        files = self.export_read_units(pos2read)
+        if export_only:
+            return files
+        if not files:
+            raise PolishingError("no position has reads")
+        self.run_polishing(files)
+        return self.assemble(files)
 
 
 def main():
@@ -80,9 +243,28 @@ def main():
     parser.add_argument("--ncrf", required=True)
     parser.add_argument("--min-pos", type=int, default=0)
     parser.add_argument("--max-pos", type=int, default=math.inf)
-    parser.add_argument("--export-only", action="store_true", help="accepted for compatibility: exporting is all this script does")
+    parser.add_argument("--flye-bin", default='flye')
+    parser.add_argument("--error-mode", default="nano")
+    parser.add_argument("--num-iters", default=None, type=int, help="Flye polishing iterations (4 when the full stage runs); giving it selects the full stage")
+    parser.add_argument("--num-threads", default=16, type=int)
+    parser.add_argument("--export-only", action="store_true", help="stop after the per-position export (the default without --num-iters / --polish / --assemble-only)")
+    parser.add_argument("--polish", action="store_true", help="the full stage: export, one Flye run per position, assemble")
+    parser.add_argument("--assemble-only", action="store_true", help="skip the export and Flye: assemble the pos_P/polished_i.fasta that are there")
+    parser.add_argument("--max-edit-distance", type=int, default=DEFAULT_MAX_EDIT_DISTANCE,
+                        help="distances above this are reported as -1 (the work grows with its square)")
+    parser.add_argument("--position-report", action="store_true", help="also write position_changes.csv: iteration position distance")
     params = parser.parse_args()
-    ELTR_Polisher(params).run()
+    if params.max_edit_distance < 0:
+        parser.error("--max-edit-distance must not be negative")
+    full = (params.polish or params.num_iters is not None or params.assemble_only) and not params.export_only
+    if params.export_only and (params.polish or params.assemble_only):
+        parser.error("--export-only excludes --polish and --assemble-only")
+    try:
+        ELTR_Polisher(params).run(export_only=not full)
+    except PolishingError as e:
+        sys.exit(f"eltr_polisher: {e}")
+    except subprocess.CalledProcessError as e:
+        sys.exit(f"eltr_polisher: {e}")
 
 
 if __name__ == "__main__":

@@ -420,6 +420,49 @@ class Engine:
         self._check(self._lib.cf_contig_exact_info(self._ctx, C.byref(v), C.byref(m)), "cf_contig_exact_info")
         return dict(n_exact_pairs=v.value, score_ms=float(m.value))
 
+    # ------------------------------------------------------------------ the polisher's comparisons (cf_edit.hip)
+    def edit_distances(self, data, a_off, b_off, k=2 ** 31 - 1):
+        """Global (NW) edit distances of the pairs (data[a_off[p]:a_off[p + 1]], data[b_off[p]:b_off[p + 1]]), -1 above k, in one
+        launch: (int32[n_pairs], device ms).  data: bytes / uint8 array, or None for the bytes hpc() left on the device (its
+        input followed by its output)."""
+        a_off = np.ascontiguousarray(a_off, np.int64).reshape(-1)
+        b_off = np.ascontiguousarray(b_off, np.int64).reshape(-1)
+        if a_off.size != b_off.size or a_off.size < 1:
+            raise ValueError("a_off and b_off have one entry per pair and one more")
+        n = a_off.size - 1
+        if data is not None:
+            data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+            if n and max(int(a_off[-1]), int(b_off[-1])) > data.size:
+                raise ValueError("an offset lies beyond the bytes")
+            if data.size == 0:
+                data = np.zeros(1, np.uint8)
+        dist = np.zeros(n, np.int32)
+        ms = C.c_float()
+        self._check(self._lib.cf_edit_distances(self._ctx, _ptr(data), _ptr(a_off), _ptr(b_off), n, int(k), _ptr(dist) if n else None,
+                                                C.byref(ms)), "cf_edit_distances")
+        return dist, float(ms.value)
+
+    def hpc(self, data, off):
+        """Homopolymer compression of the sequences data[off[s]:off[s + 1]]: (uint8 bytes back to back, int64 offsets).  The
+        input and the output stay on the device for edit_distances(None, ...)."""
+        data = np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, np.uint8)
+        off = np.ascontiguousarray(off, np.int64).reshape(-1)
+        if off.size < 1 or int(off[-1]) > data.size:
+            raise ValueError("off has one entry per sequence and one more, all inside the bytes")
+        out = np.zeros(max(int(off[-1]), 1), np.uint8)
+        out_off = np.zeros(off.size, np.int64)
+        self._check(self._lib.cf_hpc(self._ctx, _ptr(data) if data.size else None, _ptr(off), off.size - 1, _ptr(out), _ptr(out_off)), "cf_hpc")
+        return out[:int(out_off[-1])], out_off
+
+    def edit_info(self):
+        """The shape of the edit-distance kernel: lds_diags (the LDS/HBM switch point of the wavefronts), lane_bytes, turn_bytes,
+        block_small, block_big, resident_bytes."""
+        v = [C.c_int32() for _ in range(5)]
+        r = C.c_int64()
+        self._check(self._lib.cf_edit_info(self._ctx, *[C.byref(x) for x in v], C.byref(r)), "cf_edit_info")
+        names = ("lds_diags", "lane_bytes", "turn_bytes", "block_small", "block_big")
+        return dict({k: x.value for k, x in zip(names, v)}, resident_bytes=r.value)
+
     # ------------------------------------------------------------------ self tests of primitives
     def selftest_sort(self, keys, bits=64):
         keys = np.ascontiguousarray(keys, np.uint64)
