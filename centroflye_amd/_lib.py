@@ -33,6 +33,19 @@ class Times(C.Structure):
         return {n: float(getattr(self, n)) for n, _ in self._fields_}
 
 
+class TandemRead(C.Structure):
+    """Mirror of ``cf_tandem_read``."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "status", "n_windows", "n_rep_kmers", "n_conv", "count", "bin_left", "bin_right", "period", "hook_pos", "hook_index", "n_hook")]
+
+
+class TandemShape(C.Structure):
+    """Mirror of ``cf_tandem_shape``."""
+    _fields_ = [(n, C.c_int64) for n in (
+        "sort_tile", "rec_tile", "scan_tile", "block", "batch_windows", "key_mode", "code_bits", "read_bits", "pos_bits",
+        "pos_shift", "n_batches", "n_key_batches", "n_records", "n_reads")] + [("phase_ms", C.c_float * 6)]
+
+
 # every symbol include/cfhip.h declares: name -> (restype, argtypes)
 _P, _I64, _I32, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
 _PI64 = C.POINTER(C.c_int64)
@@ -76,6 +89,9 @@ PROTOTYPES = {
     "cf_edit_distances": (C.c_int, [_P, _P, _P, _P, _I64, _I32, _P, C.POINTER(C.c_float)]),
     "cf_hpc": (C.c_int, [_P, _P, _P, _I64, _P, _P]),
     "cf_edit_info": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32), _PI64]),
+    "cf_tandem_scan": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P]),
+    "cf_tandem_hook_positions": (C.c_int, [_P, _P, _P, _I64, _PI64]),
+    "cf_tandem_info": (C.c_int, [_P, C.POINTER(TandemShape)]),
     "cf_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "cf_get_times": (C.c_int, [_P, C.POINTER(Times)]),
     "cf_set_param": (C.c_int, [_P, C.c_char_p, _I64]),

@@ -578,6 +578,12 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
     } else if (n == "edit_lds_diags") {
         if (value < 0 || value > 16384) return cf_fail(ctx, -22, "edit_lds_diags out of range (0 = default, 1 .. 16384: 8 bytes of LDS per diagonal)");
         ctx->edit_lds_diags = (int)value;
+    } else if (n == "tandem_key_mode") {
+        if (value < 0 || value > 2) return cf_fail(ctx, -22, "tandem_key_mode out of range (0 = auto, 1 = 64-bit keys, 2 = 16-byte records)");
+        ctx->tandem_key_mode = (int)value;
+    } else if (n == "tandem_batch_windows") {
+        if (value < 0 || value > ((int64_t)1 << 31)) return cf_fail(ctx, -22, "tandem_batch_windows out of range (0 = default, 1 .. 2^31)");
+        ctx->tandem_batch_windows = value;
     } else if (n == "count_mode") {
         ctx->count_mode = value != 0;
     } else if (n == "count_bits") {

@@ -151,6 +151,11 @@ struct cf_ctx {
     size_t edit_cap = 0;
     int64_t edit_len = 0;
 
+    // results of the last cf_tandem_scan (cf_tandem.hip): the hook positions as a CSR over its reads, and its shape and timings
+    std::vector<int64_t> tandem_hook_ptr;
+    std::vector<int32_t> tandem_hook_pos;
+    cf_tandem_shape tandem_last{};
+
     // host <-> device copies of the caller's (pageable) buffers go through pinned staging slots, one per copy thread
     // (cf_api.hip: cf_copy_h2d / cf_copy_d2h)
     static constexpr int kCopyThreads = 16;      // slots; CF_COPY_THREADS (1 .. 16, default 16) picks how many are used
@@ -193,6 +198,8 @@ struct cf_ctx {
     int place_l3_shift = 0;      // cf_place2: log2 of the blocks per group (0 = 6: groups of 64 blocks = 4 096 reads; tests use small groups at small read sets)
     int map_window = 0;          // cf_map: candidate starts (LDS score slots) a wave covers per pass over a read's entries (0 = 2048; tests force small windows)
     int edit_lds_diags = 0;      // cf_edit: diagonals per wavefront array above which a pair's wavefronts live in HBM, not LDS (0 = 16384; tests force small values)
+    int tandem_key_mode = 0;     // cf_tandem: 0 = 64-bit keys where (read in batch, code, position) fit them, 1 = keys or an error, 2 = 16-byte records
+    int64_t tandem_batch_windows = 0;   // cf_tandem: windows per batch of whole reads (0 = 2^26; tests force borders inside small inputs)
     int count_mode = 1;         // 1: sort and reduce (cf_count2.hip) when it applies; 0: the atomic table of round 1 (cf_count.hip)
     int count_bits = 0;          // bucket bits of the sort-and-reduce path; 0 = from the number of windows (tests force small / large values)
     int count_slots = 4096;

@@ -463,6 +463,46 @@ class Engine:
         names = ("lds_diags", "lane_bytes", "turn_bytes", "block_small", "block_big")
         return dict({k: x.value for k, x in zip(names, v)}, resident_bytes=r.value)
 
+    # ------------------------------------------------------------------ period, window and hook of raw reads (cf_tandem.hip)
+    TANDEM_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.TandemRead._fields_])
+    TANDEM_OK, TANDEM_NO_PERIOD, TANDEM_EXOTIC = 0, 1, 2
+
+    def tandem_scan(self, reads, read_off, k=15, bin_size=10):
+        """unit_extractor.py's period, best distance window and hook k-mer of every read reads[read_off[i]:read_off[i + 1]] in one
+        batch: a structured array (TANDEM_DTYPE: status, n_windows, n_rep_kmers, n_conv, count, bin_left, bin_right, period,
+        hook_pos, hook_index, n_hook), one row per read.  A row with status TANDEM_EXOTIC holds nothing else of use: the read has
+        bytes other than upper-case ACGT, which centroflye_amd.unit_extractor redoes on the host."""
+        reads = np.frombuffer(reads, np.uint8) if isinstance(reads, (bytes, bytearray, memoryview)) else np.ascontiguousarray(reads, np.uint8)
+        read_off = np.ascontiguousarray(read_off, np.int64).reshape(-1)
+        if read_off.size < 1:
+            raise ValueError("read_off has one entry per read and one more")
+        if int(read_off.max()) > reads.size:
+            raise ValueError("an offset lies beyond the bytes")
+        n = read_off.size - 1
+        out = np.zeros(n, self.TANDEM_DTYPE)
+        self._check(self._lib.cf_tandem_scan(self._ctx, _ptr(reads) if reads.size else None, _ptr(read_off), n, int(k), int(bin_size),
+                                             _ptr(out) if n else None), "cf_tandem_scan")
+        return out
+
+    def tandem_hook_positions(self):
+        """(ptr int64[n_reads + 1], pos int32): the positions of every read's hook k-mer in the last tandem_scan, ascending."""
+        n = C.c_int64()
+        self._check(self._lib.cf_tandem_hook_positions(self._ctx, None, None, 0, C.byref(n)), "cf_tandem_hook_positions")
+        info = self.tandem_info()
+        ptr = np.zeros(info["n_reads"] + 1, np.int64)
+        pos = np.zeros(max(n.value, 1), np.int32)
+        self._check(self._lib.cf_tandem_hook_positions(self._ctx, _ptr(ptr), _ptr(pos), n.value, C.byref(n)), "cf_tandem_hook_positions")
+        return ptr, pos[:n.value]
+
+    def tandem_info(self):
+        """The shape of cf_tandem.hip (tile sizes, batch size, key layout of the last scan) and the last scan's device
+        milliseconds per phase."""
+        s = _lib.TandemShape()
+        self._check(self._lib.cf_tandem_info(self._ctx, C.byref(s)), "cf_tandem_info")
+        d = {n: int(getattr(s, n)) for n, _ in s._fields_ if n != "phase_ms"}
+        d["phase_ms"] = dict(zip(("records", "sorts", "runs", "windows", "hook", "total"), (float(x) for x in s.phase_ms)))
+        return d
+
     # ------------------------------------------------------------------ self tests of primitives
     def selftest_sort(self, keys, bits=64):
         keys = np.ascontiguousarray(keys, np.uint64)

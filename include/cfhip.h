@@ -22,6 +22,7 @@
  *   cf_contig_spread   scripts/cloud_contig.py:78-84 (get_spread_kmers)
  *   cf_edit_distances  scripts/eltr_polisher.py:133-146 (compare_polished_sequences: edlib.align in mode NW)
  *   cf_hpc             scripts/utils/bio.py:60-61 (compress_homopolymer), used by eltr_polisher.py:142-143, :151
+ *   cf_tandem_scan     scripts/unit_extractor.py:23-89 (get_repetitive_kmers, get_convolution, get_period_info, get_hook_kmer)
  *
  * Conventions: plain pointers and sizes only; every function returns 0 or a negative
  * errno-style code and never throws or aborts; cf_last_error() gives the message; the
@@ -234,6 +235,48 @@ int cf_hpc(cf_ctx* ctx, const uint8_t* bytes, const int64_t* off, int64_t n_seqs
 int cf_edit_info(cf_ctx* ctx, int32_t* lds_diags, int32_t* lane_bytes, int32_t* turn_bytes, int32_t* block_small, int32_t* block_big,
                  int64_t* resident_bytes);
 
+/* The HOR period and unit of raw reads (cf_tandem.hip; scripts/unit_extractor.py:23-97), every read of the call in one batch.
+ * cf_tandem_scan: reads = n_reads byte strings back to back, read_off[n_reads + 1] non-decreasing and >= 0 (the layout of
+ * cf_rr_distances).  1 <= k <= 31, bin_size >= 0, a read holds fewer than 2^31 bases; distances and counts are int32.  Per read,
+ * with the repetitive k-mers = the k-mers with two or more start positions, conv = the differences of consecutive positions of
+ * every such k-mer sorted ascending (n_conv of them), r(l) = the first index whose distance exceeds conv[l] + 2 bin_size:
+ *   n_windows     window starts l = 0, 1, .. the reference's loop visits: up to the first l with r(l) = n_conv
+ *   count         C = the largest r(l) - l among them; bin_left = conv[l*], bin_right = conv[r(l*) - 1] for the FIRST l* with count C
+ *   period        periods[0] of get_period_info: the median (conv[mid] for an odd count, the floored mean of the two middle
+ *                 distances for an even one) of the LAST visited window with count C
+ *   hook_index    the largest number of one k-mer's distances inside [bin_left, bin_right] (closed); hook_pos = the first position
+ *                 of that k-mer, ties to the k-mer that occurs first; n_hook = its positions (cf_tandem_hook_positions has them)
+ * status: CF_TANDEM_OK; CF_TANDEM_NO_PERIOD = no k-mer repeats (shorter than k included): every other field but n_rep_kmers and
+ * n_conv (both 0) is 0 and hook_pos -1; CF_TANDEM_EXOTIC = some window holds a byte that is not upper-case A, C, G, T: the device
+ * skipped those windows and the other fields must not be used (the reference compares raw strings: centroflye_amd/unit_extractor.py
+ * redoes such reads on the host).  n_reads = 0 is allowed.  Device time goes to cf_tandem_info, nothing is added to cf_times or
+ * cf_stats.  Errors (-22: a negative count, decreasing offsets, k < 1, k > 31, bin_size < 0, null pointers, a read of 2^31 bases,
+ * keys forced where one read alone does not fit them) leave the context and the results of the call before as they were.
+ * cf_tandem_hook_positions: the hook's positions of every read of the last cf_tandem_scan as a CSR: ptr[n_reads + 1], pos[ptr[n_reads]]
+ * ascending inside a read.  *n_out = the number of positions; ptr == pos == NULL asks for it alone; otherwise cap >= *n_out.
+ * cf_tandem_info: the shape the tests straddle and the last scan's figures.  Records are sorted on (read, code) only; a stable
+ * sort keeps the positions of a (read, code) run ascending.  key_mode 1: 64-bit keys [position | invalid | read in batch | code]
+ * with the position starting at bit pos_shift (a multiple of 8: the sort works on whole bytes); key_mode 2: 16-byte records
+ * {code low, code high, read, position}.  A batch is a range of whole reads of at most batch_windows windows (knob
+ * "tandem_batch_windows", 0 = 2^26) and, unless records are forced, of few enough reads for the keys; knob "tandem_key_mode": 0
+ * = keys where they fit, 1 = keys or -22, 2 = records.  phase_ms: records, sorts, runs and distances, windows, hook, and the whole
+ * call with its copies, by HIP events, summed over the batches of the last scan. */
+enum { CF_TANDEM_OK = 0, CF_TANDEM_NO_PERIOD = 1, CF_TANDEM_EXOTIC = 2 };
+typedef struct cf_tandem_read {
+    int32_t status, n_windows, n_rep_kmers, n_conv, count, bin_left, bin_right, period, hook_pos, hook_index, n_hook;
+} cf_tandem_read;
+typedef struct cf_tandem_shape {
+    int64_t sort_tile, rec_tile, scan_tile, block; /* keys / records / scan entries per tile, threads per workgroup */
+    int64_t batch_windows;                         /* windows per batch in force                                   */
+    int64_t key_mode, code_bits, read_bits, pos_bits, pos_shift; /* layout of the last batch of the last scan      */
+    int64_t n_batches, n_key_batches, n_records, n_reads; /* of the last scan                                   */
+    float phase_ms[6];
+} cf_tandem_shape;
+int cf_tandem_scan(cf_ctx* ctx, const uint8_t* reads, const int64_t* read_off, int64_t n_reads, int32_t k, int32_t bin_size,
+                   cf_tandem_read* out);
+int cf_tandem_hook_positions(cf_ctx* ctx, int64_t* ptr, int32_t* pos, int64_t cap, int64_t* n_out);
+int cf_tandem_info(cf_ctx* ctx, cf_tandem_shape* out);
+
 int cf_get_stats(cf_ctx* ctx, cf_stats* out);
 int cf_get_times(cf_ctx* ctx, cf_times* out);
 
@@ -272,7 +315,7 @@ int cf_allreduce_unique(cf_ctx* ctx, int64_t* n_unique);
 /* Tuning knobs (defaults are chosen for gfx950): name in {"dist_block" (threads per workgroup, 0 = auto), "dist_wgs"
  * (workgroups per CU the LDS is split between, 0 = auto: by the pair emissions per first k-mer), "dist_slots" (LDS budget of the (b,d) table in 8-byte units, 0 = all that
  * is left), "dist_sketch" (0: every pair goes to the exact table), "dist_fill_pct", "dist_est_pct", "dist_stage", "dist_edge_chunk" (edge rows a workgroup reserves in the output per global atomic, 0 = 8192; tests use small chunks), "dist_int_thr" (0: the dominance test always divides in doubles; 1, the default: the literal 0.8 is tested as 5 cnt >= 4 total, which is the same predicate),
- * "dist_wide", "dist_post_atomics" (1: postings by a histogram and a fill pass of atomics instead of the sort), "dist_hot_cap" (tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan), "dist_sketch_bits" (bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the counters in the same LDS —, else 8; 8 forces bytes), "lut_shift" (the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1, the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0), "dist_hot_entries" (default 32768: first k-mers with more partner entries than this keep no list of hot slots during their inserts — it would overflow — and their filter scans the count fields; -1: always keep it), "dist_regions" (1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long reads take by themselves), "dist_dbits" (5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks need), "place_mode" (2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4; smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the hash-map path of rounds 1-3, cf_place.hip), "place_grid" / "place_block" (workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024), "place_row_words" (32 or 64 words per posting row, 0 = by the longest posting list), "place_slots_per_unit" (score-region slots per unit of a read, 0 = 48; grown automatically when a region fills), "place_l3" / "place_l3_shift" (1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily — built in round 5, measured neutral at 500 000 reads, off by default), "dist_region_bytes" (1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond 128 units do by themselves), "place_long_rescans" (default 2: a run of the region path whose reads average more than this many rescans of reads with more than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is handed to the hash-map path; -1: at the first look, tests), "place_cmap_bits" (log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 = cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load), "place_chunk", "place_fused" (place_mode 1: cloud entries per wave step; 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list and a third kernel per greedy iteration), "count_mode" (1: A1 by sort and reduce, 0: the atomic table), "count_bits" (bucket bits of the former, 0 = auto), "count_slots", "count_tile", "count_skip_exotic" (1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads), "comm_round_bytes" (bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds), "map_window" (candidate starts — LDS score slots — that cf_map_reads covers per pass over a read's cloud entries, 0 = 2048, at most 4096; a read whose hits span more starts takes several passes, tests force that with tiny windows), "edit_lds_diags" (cf_edit_distances: diagonals per wavefront array up to which a pair's wavefronts stay in LDS, 0 = 16384, at most 16384; tests force the HBM path with small values), "comm_self_p2p" (1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a one-GPU box runs the whole p2p path)}.  Results never depend on them (tests/test_gpu_parity.py). */
+ * "dist_wide", "dist_post_atomics" (1: postings by a histogram and a fill pass of atomics instead of the sort), "dist_hot_cap" (tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan), "dist_sketch_bits" (bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the counters in the same LDS —, else 8; 8 forces bytes), "lut_shift" (the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1, the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0), "dist_hot_entries" (default 32768: first k-mers with more partner entries than this keep no list of hot slots during their inserts — it would overflow — and their filter scans the count fields; -1: always keep it), "dist_regions" (1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long reads take by themselves), "dist_dbits" (5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks need), "place_mode" (2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4; smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the hash-map path of rounds 1-3, cf_place.hip), "place_grid" / "place_block" (workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024), "place_row_words" (32 or 64 words per posting row, 0 = by the longest posting list), "place_slots_per_unit" (score-region slots per unit of a read, 0 = 48; grown automatically when a region fills), "place_l3" / "place_l3_shift" (1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily — built in round 5, measured neutral at 500 000 reads, off by default), "dist_region_bytes" (1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond 128 units do by themselves), "place_long_rescans" (default 2: a run of the region path whose reads average more than this many rescans of reads with more than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is handed to the hash-map path; -1: at the first look, tests), "place_cmap_bits" (log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 = cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load), "place_chunk", "place_fused" (place_mode 1: cloud entries per wave step; 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list and a third kernel per greedy iteration), "count_mode" (1: A1 by sort and reduce, 0: the atomic table), "count_bits" (bucket bits of the former, 0 = auto), "count_slots", "count_tile", "count_skip_exotic" (1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads), "comm_round_bytes" (bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds), "map_window" (candidate starts — LDS score slots — that cf_map_reads covers per pass over a read's cloud entries, 0 = 2048, at most 4096; a read whose hits span more starts takes several passes, tests force that with tiny windows), "edit_lds_diags" (cf_edit_distances: diagonals per wavefront array up to which a pair's wavefronts stay in LDS, 0 = 16384, at most 16384; tests force the HBM path with small values), "comm_self_p2p" (1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a one-GPU box runs the whole p2p path), "tandem_key_mode" and "tandem_batch_windows" (cf_tandem_scan: see there)}.  Results never depend on them (tests/test_gpu_parity.py). */
 int cf_set_param(cf_ctx* ctx, const char* name, int64_t value);
 
 /* Self-tests of the device primitives against host results (used by tests/ only). */
