@@ -218,18 +218,15 @@ cf_alphabet_kernel(const uint8_t* __restrict__ bases, int64_t n, unsigned int* _
 static int cf_check_alphabet(cf_ctx* ctx, const uint8_t* d_bases, int64_t n, bool* exotic) {
     *exotic = false;
     if (n <= 0) return 0;
+    cf_scratch tmp(ctx);
     unsigned int* d_flag = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_flag, 4, "alphabet flag"));
+    CF_TRY(tmp.get(&d_flag, 4, "alphabet flag"));
     unsigned int h = 0;
-    hipError_t e = hipMemsetAsync(d_flag, 0, 16, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(cf_alphabet_kernel, dim3((unsigned)cf_grid_for((n >> 4) + 1, 256, std::max(1, ctx->n_cu) * 16)), dim3(256), 0, ctx->stream, d_bases, n, d_flag);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    cf_release_t(ctx, d_flag, 4);
-    if (e != hipSuccess) return cf_fail(ctx, -5, std::string("alphabet check: ") + hipGetErrorString(e));
+    CF_HIP(hipMemsetAsync(d_flag, 0, 16, ctx->stream));
+    hipLaunchKernelGGL(cf_alphabet_kernel, dim3((unsigned)cf_grid_for((n >> 4) + 1, 256, std::max(1, ctx->n_cu) * 16)), dim3(256), 0, ctx->stream, d_bases, n, d_flag);
+    CF_KERNEL_CHECK("cf_alphabet_kernel");
+    CF_HIP(hipMemcpyAsync(&h, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
     *exotic = h != 0;
     return 0;
 }
@@ -392,9 +389,9 @@ int cf_load_reads(cf_ctx* ctx, const uint8_t* bases, const int64_t* read_off, in
     ctx->n_bases = nb;
     ctx->h_read_off.assign(read_off, read_off + n_reads + 1);
     CF_TRY(cf_alloc_t(ctx, &ctx->d_bases, (size_t)nb + 64, "bases"));
-    CF_TRY(cf_alloc_t(ctx, &ctx->d_read_off, (size_t)n_reads + 1, "read_off"));
     // note: d_bases was allocated with +64 slack; account it under n_bases for release
     ctx->live -= 64;
+    CF_TRY(cf_alloc_t(ctx, &ctx->d_read_off, (size_t)n_reads + 1, "read_off"));
     ctx->has_exotic = false;
     CF_TRY(cf_copy_h2d(ctx, ctx->d_bases, bases, (size_t)nb));      // (host or device memory: cf_copy_staged tells them apart)
     CF_TRY(cf_check_alphabet(ctx, ctx->d_bases, nb, &exotic));
@@ -462,14 +459,13 @@ int cf_sort_edges(cf_ctx* ctx) {
     if (!ctx) return -22;
     const int64_t n = ctx->n_edges_stored;
     if (n <= 1) return 0;
+    cf_scratch tmp(ctx);
     uint32_t* d_tmp = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_tmp, (size_t)n * 4, "edge sort scratch"));
+    CF_TRY(tmp.get(&d_tmp, (size_t)n * 4, "edge sort scratch"));
     int kbits = 1;
     while (kbits < 32 && ((int64_t)1 << kbits) < std::max<int64_t>(ctx->n_kmers, 2)) ++kbits;
     const int words[3] = {2, 1, 0}, bits[3] = {kbits, kbits, 16};      // b, then a, then d (<= 65535)
-    const int rc = cf_radix_sort_rec16(ctx, ctx->d_edges, d_tmp, n, words, bits, 3);
-    cf_release_t(ctx, d_tmp, (size_t)n * 4);
-    return rc;
+    return cf_radix_sort_rec16(ctx, ctx->d_edges, d_tmp, n, words, bits, 3);
 }
 
 int cf_get_stats(cf_ctx* ctx, cf_stats* out) {
@@ -612,39 +608,29 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
 int cf_selftest_sort(cf_ctx* ctx, const uint64_t* keys, int64_t n, int32_t bits, uint64_t* out) {
     if (!ctx) return -22;
     CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
     unsigned long long *a = nullptr, *b = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &a, (size_t)n, "selftest keys"));
-    int rc = cf_alloc_t(ctx, &b, (size_t)n, "selftest tmp");
-    if (rc == 0 && n) {
-        if (hipMemcpy(a, keys, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) rc = cf_fail(ctx, -5, "selftest copy");
-    }
-    if (rc == 0) rc = cf_radix_sort_u64(ctx, a, b, n, bits);
-    if (rc == 0 && n) {
-        if (hipMemcpy(out, a, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = cf_fail(ctx, -5, "selftest copy back");
-    }
-    if (b) cf_release_t(ctx, b, (size_t)n);
-    cf_release_t(ctx, a, (size_t)n);
-    return rc;
+    CF_TRY(tmp.get(&a, (size_t)n, "selftest keys"));
+    CF_TRY(tmp.get(&b, (size_t)n, "selftest tmp"));
+    if (n && hipMemcpy(a, keys, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) return cf_fail(ctx, -5, "selftest copy");
+    CF_TRY(cf_radix_sort_u64(ctx, a, b, n, bits));
+    if (n && hipMemcpy(out, a, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return cf_fail(ctx, -5, "selftest copy back");
+    return 0;
 }
 
 int cf_selftest_scan(cf_ctx* ctx, const int64_t* in, int64_t n, int64_t* out) {
     if (!ctx) return -22;
     CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
     int64_t *a = nullptr, *b = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &a, (size_t)n + 1, "selftest in"));
-    int rc = cf_alloc_t(ctx, &b, (size_t)n + 1, "selftest out");
+    CF_TRY(tmp.get(&a, (size_t)n + 1, "selftest in"));
+    CF_TRY(tmp.get(&b, (size_t)n + 1, "selftest out"));
     int64_t total = 0;
-    if (rc == 0 && n) {
-        if (hipMemcpy(a, in, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) rc = cf_fail(ctx, -5, "selftest copy");
-    }
-    if (rc == 0) rc = cf_scan_exclusive_i64(ctx, a, b, n, &total);
-    if (rc == 0 && n) {
-        if (hipMemcpy(out, b, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) rc = cf_fail(ctx, -5, "selftest copy back");
-    }
-    if (rc == 0) out[n] = total;
-    if (b) cf_release_t(ctx, b, (size_t)n + 1);
-    cf_release_t(ctx, a, (size_t)n + 1);
-    return rc;
+    if (n && hipMemcpy(a, in, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) return cf_fail(ctx, -5, "selftest copy");
+    CF_TRY(cf_scan_exclusive_i64(ctx, a, b, n, &total));
+    if (n && hipMemcpy(out, b, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return cf_fail(ctx, -5, "selftest copy back");
+    out[n] = total;
+    return 0;
 }
 
 }  // extern "C"

@@ -63,34 +63,31 @@ extern "C" int cf_checksum(cf_ctx* ctx, int32_t what, uint64_t* sum, int64_t* n_
     *sum = 0;
     if (n_items) *n_items = 0;
     CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
     unsigned long long* d_out = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_out, 2, "checksum"));
-    int rc = 0;
+    CF_TRY(tmp.get(&d_out, 2, "checksum"));
     unsigned long long h[2] = {0, 0};
     const int grid_max = std::max(1, ctx->n_cu) * 16;
-    do {
-        if (hipMemsetAsync(d_out, 0, 16, ctx->stream) != hipSuccess) { rc = cf_fail(ctx, -5, "cf_checksum: memset"); break; }
-        if (what == CF_CHECKSUM_TABLE) {
-            if (!ctx->d_table) { rc = cf_fail(ctx, -22, "cf_checksum: no table (call cf_count_kmers first)"); break; }
-            hipLaunchKernelGGL(cf_cs_table_kernel, dim3((unsigned)cf_grid_for((int64_t)ctx->table_cap, 256, grid_max)), dim3(256), 0, ctx->stream,
-                               (const cf_slot*)ctx->d_table, (uint64_t)ctx->table_cap, d_out);
-        } else if (what == CF_CHECKSUM_KMERS || what == CF_CHECKSUM_UNIQUE) {
-            if (what == CF_CHECKSUM_UNIQUE && !ctx->d_unique_bits) { rc = cf_fail(ctx, -22, "cf_checksum: no k-mer set"); break; }
-            if (ctx->n_kmers > 0)
-                hipLaunchKernelGGL(cf_cs_kmers_kernel, dim3((unsigned)cf_grid_for(ctx->n_kmers, 256, grid_max)), dim3(256), 0, ctx->stream,
-                                   (const unsigned long long*)ctx->d_kmers, ctx->n_kmers,
-                                   what == CF_CHECKSUM_UNIQUE ? (const uint32_t*)ctx->d_unique_bits : (const uint32_t*)nullptr, d_out);
-        } else if (what == CF_CHECKSUM_CLOUDS) {
-            if (!ctx->have_clouds) { rc = cf_fail(ctx, -22, "cf_checksum: no clouds built"); break; }
-            if (ctx->n_units > 0)
-                hipLaunchKernelGGL(cf_cs_clouds_kernel, dim3((unsigned)cf_grid_for(ctx->n_units, 4, grid_max)), dim3(256), 0, ctx->stream,
-                                   (const int64_t*)ctx->d_cloud_ptr, (const int32_t*)ctx->d_entries, ctx->n_units, d_out);
-        } else { rc = cf_fail(ctx, -22, "cf_checksum: unknown selector"); break; }
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(h, d_out, 16, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) rc = cf_fail(ctx, -5, "cf_checksum: kernel");
-    } while (0);
-    cf_release_t(ctx, d_out, 2);
-    if (rc) return rc;
+    CF_HIP(hipMemsetAsync(d_out, 0, 16, ctx->stream));
+    if (what == CF_CHECKSUM_TABLE) {
+        if (!ctx->d_table) return cf_fail(ctx, -22, "cf_checksum: no table (call cf_count_kmers first)");
+        hipLaunchKernelGGL(cf_cs_table_kernel, dim3((unsigned)cf_grid_for((int64_t)ctx->table_cap, 256, grid_max)), dim3(256), 0, ctx->stream,
+                           (const cf_slot*)ctx->d_table, (uint64_t)ctx->table_cap, d_out);
+    } else if (what == CF_CHECKSUM_KMERS || what == CF_CHECKSUM_UNIQUE) {
+        if (what == CF_CHECKSUM_UNIQUE && !ctx->d_unique_bits) return cf_fail(ctx, -22, "cf_checksum: no k-mer set");
+        if (ctx->n_kmers > 0)
+            hipLaunchKernelGGL(cf_cs_kmers_kernel, dim3((unsigned)cf_grid_for(ctx->n_kmers, 256, grid_max)), dim3(256), 0, ctx->stream,
+                               (const unsigned long long*)ctx->d_kmers, ctx->n_kmers,
+                               what == CF_CHECKSUM_UNIQUE ? (const uint32_t*)ctx->d_unique_bits : (const uint32_t*)nullptr, d_out);
+    } else if (what == CF_CHECKSUM_CLOUDS) {
+        if (!ctx->have_clouds) return cf_fail(ctx, -22, "cf_checksum: no clouds built");
+        if (ctx->n_units > 0)
+            hipLaunchKernelGGL(cf_cs_clouds_kernel, dim3((unsigned)cf_grid_for(ctx->n_units, 4, grid_max)), dim3(256), 0, ctx->stream,
+                               (const int64_t*)ctx->d_cloud_ptr, (const int32_t*)ctx->d_entries, ctx->n_units, d_out);
+    } else return cf_fail(ctx, -22, "cf_checksum: unknown selector");
+    CF_KERNEL_CHECK("the cf_checksum kernel");
+    CF_HIP(hipMemcpyAsync(h, d_out, 16, hipMemcpyDeviceToHost, ctx->stream));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
     *sum = (uint64_t)h[0];
     if (n_items) *n_items = (int64_t)h[1];
     return 0;

@@ -298,22 +298,19 @@ int cf_install_kmers(cf_ctx* ctx, int32_t k) {
     CF_HIP(hipMemsetAsync(ctx->d_lut, 0, (size_t)ctx->lut_cap * sizeof(cf_slot), ctx->stream));
     CF_HIP(hipMemsetAsync(ctx->d_unique_bits, 0, (size_t)ctx->unique_words * 4, ctx->stream));
     ctx->stats.n_unique = 0;
+    cf_scratch tmp(ctx);
     unsigned int* d_flags = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_flags, 4, "lut flags"));      // (the last early return: everything below releases it)
+    CF_TRY(tmp.get(&d_flags, 4, "lut flags"));
     unsigned int flags = 0;
-    int rc = 0;
-    hipError_t e = hipMemsetAsync(d_flags, 0, 16, ctx->stream);
-    if (e == hipSuccess && n) {
+    CF_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
+    if (n) {
         const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
         hipLaunchKernelGGL(cf_lut_build_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)ctx->d_kmers,
                            n, ctx->d_lut, (uint64_t)(ctx->lut_cap - 1), ctx->d_lut_pre, (uint64_t)(ctx->lut_pre_words - 1), d_flags);
-        e = hipGetLastError();
+        CF_KERNEL_CHECK("cf_lut_build_kernel");
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&flags, d_flags, 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("k-mer lookup build: ") + hipGetErrorString(e));
-    cf_release_t(ctx, d_flags, 4);
-    if (rc) return rc;
+    CF_HIP(hipMemcpyAsync(&flags, d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
     if (flags & 1u) return cf_fail(ctx, -34, "k-mer lookup table overflow");
     if (flags & 6u) return cf_fail(ctx, -22, "k-mer set must be sorted ascending and unique");
     cf_free_clouds(ctx);
@@ -323,17 +320,14 @@ int cf_install_kmers(cf_ctx* ctx, int32_t k) {
 // popcount of the unique bitmap -> stats.n_unique
 int cf_refresh_unique_count(cf_ctx* ctx) {
     if (!ctx->d_unique_bits) { ctx->stats.n_unique = 0; return 0; }
+    cf_scratch tmp(ctx);
     unsigned long long* d_u = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_u, 2, "unique count"));
+    CF_TRY(tmp.get(&d_u, 2, "unique count"));
     unsigned long long hu = 0;
-    hipError_t e = hipMemsetAsync(d_u, 0, 16, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(cf_bits_count_kernel, dim3((unsigned)cf_grid_for(ctx->unique_words, 256, std::max(1, ctx->n_cu) * 8)), dim3(256), 0,
-                           ctx->stream, (const uint32_t*)ctx->d_unique_bits, ctx->unique_words, d_u);
-        e = hipMemcpy(&hu, d_u, 8, hipMemcpyDeviceToHost);
-    }
-    cf_release_t(ctx, d_u, 2);
-    if (e != hipSuccess) return cf_fail(ctx, -5, std::string("unique count: ") + hipGetErrorString(e));
+    CF_HIP(hipMemsetAsync(d_u, 0, 16, ctx->stream));
+    hipLaunchKernelGGL(cf_bits_count_kernel, dim3((unsigned)cf_grid_for(ctx->unique_words, 256, std::max(1, ctx->n_cu) * 8)), dim3(256), 0,
+                       ctx->stream, (const uint32_t*)ctx->d_unique_bits, ctx->unique_words, d_u);
+    CF_HIP(hipMemcpy(&hu, d_u, 8, hipMemcpyDeviceToHost));
     ctx->stats.n_unique = (int64_t)hu;
     return 0;
 }
@@ -368,58 +362,57 @@ cf_cloud_compact_kernel(const int32_t* __restrict__ rows, int64_t row_stride, co
 
 extern "C" {
 
-// One attempt with an LDS set of set_slots entries per unit; returns 1 when some unit's cloud did not fit.
-static int build_clouds_attempt(cf_ctx* ctx, int set_slots, int64_t* n_entries) {
-    cf_free_clouds(ctx);
+// Fills ctx->d_cloud_ptr / d_entries with an LDS set of set_slots entries per unit; returns 1 when some unit's cloud did not fit.
+static int fill_clouds(cf_ctx* ctx, int set_slots, int64_t* n_total) {
     const int64_t U = ctx->n_units;
+    cf_scratch tmp(ctx);
     uint32_t* d_sizes = nullptr;
     int32_t* d_rows = nullptr;
     unsigned int* d_flags = nullptr;
     CF_TRY(cf_alloc_t(ctx, &ctx->d_cloud_ptr, (size_t)U + 1, "cloud_ptr"));
-    CF_TRY(cf_alloc_t(ctx, &d_sizes, (size_t)U + 1, "cloud sizes"));
-    int rc = cf_alloc_t(ctx, &d_flags, 4, "cloud flags");
+    CF_TRY(tmp.get(&d_sizes, (size_t)U + 1, "cloud sizes"));
+    CF_TRY(tmp.get(&d_flags, 4, "cloud flags"));
     const size_t lds = (size_t)set_slots * 8 + CL_THREADS * CL_TILE_W + 64 + 16;
     const int grid = (int)std::min<int64_t>(std::max<int64_t>(U, 1), (int64_t)std::max(1, ctx->n_cu) * 32);
-    int64_t total = 0, row_stride = 0;
+    int64_t total = 0;
     unsigned int flags = 0;
-    do {
-        if (rc) break;
-        hipError_t e = hipMemsetAsync(d_flags, 0, 16, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_sizes, 0, (size_t)(U + 1) * 4, ctx->stream);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)cf_cloud_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_build_clouds setup: ") + hipGetErrorString(e)); break; }
-        // one pass: every unit's sorted cloud goes to a fixed-stride row of a scratch buffer (a cloud that fits the LDS set
-        // has at most 3/4 of its slots), sizes are scanned, rows are compacted into the CSR
-        // (nor more entries than the longest unit has windows: the retry with the 64 KiB set does not quadruple the scratch)
-        row_stride = std::min<int64_t>((int64_t)set_slots * 3 / 4, std::max<int64_t>(1, ctx->max_unit_len - ctx->set_k + 1));
-        if ((rc = cf_alloc_t(ctx, &d_rows, (size_t)(U * row_stride + 1), "cloud rows scratch"))) break;
-        if (U) {
-            hipLaunchKernelGGL(cf_cloud_kernel, dim3((unsigned)grid), dim3(CL_THREADS), lds, ctx->stream, (const uint8_t*)ctx->d_bases,
-                               (const int64_t*)ctx->d_unit_start, (const int64_t*)ctx->d_unit_end, U, ctx->set_k, set_slots,
-                               (const cf_slot*)ctx->d_lut, (uint64_t)(ctx->lut_cap - 1), (const uint32_t*)ctx->d_lut_pre, (uint64_t)(ctx->lut_pre_words - 1),
-                               2, row_stride, d_sizes, (const int64_t*)nullptr, d_rows, d_flags);
-            e = hipGetLastError();
-            if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_cloud_kernel: ") + hipGetErrorString(e)); break; }
-        }
-        if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_sizes, ctx->d_cloud_ptr, U + 1, &total))) break;
-        if (hipMemcpy(&flags, d_flags, 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = cf_fail(ctx, -5, "cloud flags copy"); break; }
-        if (flags & 1u) { rc = 1; break; }
-        ctx->n_entries = total;
-        if ((rc = cf_alloc_t(ctx, &ctx->d_entries, (size_t)total, "cloud entries"))) break;
-        if (U && total) {
-            hipLaunchKernelGGL(cf_cloud_compact_kernel, dim3((unsigned)cf_grid_for(U * 64, 256, std::max(1, ctx->n_cu) * 8)), dim3(256), 0, ctx->stream,
-                               (const int32_t*)d_rows, row_stride, (const int64_t*)ctx->d_cloud_ptr, U, ctx->d_entries);
-            e = hipGetLastError();
-            if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_cloud_compact_kernel: ") + hipGetErrorString(e)); break; }
-        }
-        e = hipEventRecord(ctx->ev1, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev1);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_build_clouds sync: ") + hipGetErrorString(e)); break; }
-        (void)hipEventElapsedTime(&ctx->times.clouds_ms, ctx->ev0, ctx->ev1);
-    } while (0);
-    if (d_flags) cf_release_t(ctx, d_flags, 4);
-    if (d_rows) cf_release_t(ctx, d_rows, (size_t)(U * row_stride + 1));
-    cf_release_t(ctx, d_sizes, (size_t)U + 1);
+    CF_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_sizes, 0, (size_t)(U + 1) * 4, ctx->stream));
+    CF_HIP(hipFuncSetAttribute((const void*)cf_cloud_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // one pass: every unit's sorted cloud goes to a fixed-stride row of a scratch buffer (a cloud that fits the LDS set
+    // has at most 3/4 of its slots), sizes are scanned, rows are compacted into the CSR
+    // (nor more entries than the longest unit has windows: the retry with the 64 KiB set does not quadruple the scratch)
+    const int64_t row_stride = std::min<int64_t>((int64_t)set_slots * 3 / 4, std::max<int64_t>(1, ctx->max_unit_len - ctx->set_k + 1));
+    CF_TRY(tmp.get(&d_rows, (size_t)(U * row_stride + 1), "cloud rows scratch"));
+    if (U) {
+        hipLaunchKernelGGL(cf_cloud_kernel, dim3((unsigned)grid), dim3(CL_THREADS), lds, ctx->stream, (const uint8_t*)ctx->d_bases,
+                           (const int64_t*)ctx->d_unit_start, (const int64_t*)ctx->d_unit_end, U, ctx->set_k, set_slots,
+                           (const cf_slot*)ctx->d_lut, (uint64_t)(ctx->lut_cap - 1), (const uint32_t*)ctx->d_lut_pre, (uint64_t)(ctx->lut_pre_words - 1),
+                           2, row_stride, d_sizes, (const int64_t*)nullptr, d_rows, d_flags);
+        CF_KERNEL_CHECK("cf_cloud_kernel");
+    }
+    CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_sizes, ctx->d_cloud_ptr, U + 1, &total));
+    CF_HIP(hipMemcpy(&flags, d_flags, 4, hipMemcpyDeviceToHost));
+    if (flags & 1u) return 1;
+    ctx->n_entries = total;
+    CF_TRY(cf_alloc_t(ctx, &ctx->d_entries, (size_t)total, "cloud entries"));
+    if (U && total) {
+        hipLaunchKernelGGL(cf_cloud_compact_kernel, dim3((unsigned)cf_grid_for(U * 64, 256, std::max(1, ctx->n_cu) * 8)), dim3(256), 0, ctx->stream,
+                           (const int32_t*)d_rows, row_stride, (const int64_t*)ctx->d_cloud_ptr, U, ctx->d_entries);
+        CF_KERNEL_CHECK("cf_cloud_compact_kernel");
+    }
+    CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    CF_HIP(hipEventSynchronize(ctx->ev1));
+    (void)hipEventElapsedTime(&ctx->times.clouds_ms, ctx->ev0, ctx->ev1);
+    *n_total = total;
+    return 0;
+}
+
+// One attempt: the clouds are in the context afterwards, or none are
+static int build_clouds_attempt(cf_ctx* ctx, int set_slots, int64_t* n_entries) {
+    cf_free_clouds(ctx);
+    int64_t total = 0;
+    const int rc = fill_clouds(ctx, set_slots, &total);
     if (rc) { cf_free_clouds(ctx); return rc; }
     ctx->have_clouds = true;
     ctx->stats.n_cloud_entries = total;
@@ -454,43 +447,34 @@ int cf_filter_clouds(cf_ctx* ctx, uint32_t min_mult, uint32_t max_mult, int64_t*
     int64_t* d_new_ptr = nullptr;
     int32_t* d_new_entries = nullptr;
     int64_t total = 0;
-    int rc = 0;
     const int grid_e = cf_grid_for(N, 256, std::max(1, ctx->n_cu) * 8);
     const int grid_u = cf_grid_for(U * 64, 256, std::max(1, ctx->n_cu) * 8);
-    do {
-        if ((rc = cf_alloc_t(ctx, &d_mult, (size_t)K + 1, "k-mer multiplicities"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_sizes, (size_t)U + 1, "filtered sizes"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_new_ptr, (size_t)U + 1, "filtered cloud_ptr"))) break;
-        hipError_t e = hipMemsetAsync(d_mult, 0, (size_t)(K + 1) * 4, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_sizes, 0, (size_t)(U + 1) * 4, ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, "cf_filter_clouds memset"); break; }
-        if (N) hipLaunchKernelGGL(cf_mult_hist_kernel, dim3((unsigned)grid_e), dim3(256), 0, ctx->stream, (const int32_t*)ctx->d_entries, N, d_mult);
-        if (U) hipLaunchKernelGGL(cf_mult_filter_kernel, dim3((unsigned)grid_u), dim3(256), 0, ctx->stream, (const int64_t*)ctx->d_cloud_ptr,
-                                  (const int32_t*)ctx->d_entries, U, (const uint32_t*)d_mult, min_mult, max_mult, 0, d_sizes,
-                                  (const int64_t*)nullptr, (int32_t*)nullptr);
-        if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_sizes, d_new_ptr, U + 1, &total))) break;
-        if ((rc = cf_alloc_t(ctx, &d_new_entries, (size_t)total, "filtered entries"))) break;
-        if (U && total)
-            hipLaunchKernelGGL(cf_mult_filter_kernel, dim3((unsigned)grid_u), dim3(256), 0, ctx->stream, (const int64_t*)ctx->d_cloud_ptr,
-                               (const int32_t*)ctx->d_entries, U, (const uint32_t*)d_mult, min_mult, max_mult, 1, d_sizes,
-                               (const int64_t*)d_new_ptr, d_new_entries);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev1);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_filter_clouds: ") + hipGetErrorString(e)); break; }
-        (void)hipEventElapsedTime(&ctx->times.filter_ms, ctx->ev0, ctx->ev1);
-    } while (0);
-    if (d_sizes) cf_release_t(ctx, d_sizes, (size_t)U + 1);
-    if (d_mult) cf_release_t(ctx, d_mult, (size_t)K + 1);
-    if (rc) {
-        if (d_new_entries) cf_release_t(ctx, d_new_entries, (size_t)total);
-        if (d_new_ptr) cf_release_t(ctx, d_new_ptr, (size_t)U + 1);
-        return rc;
-    }
+    cf_scratch tmp(ctx);
+    CF_TRY(tmp.get(&d_mult, (size_t)K + 1, "k-mer multiplicities"));
+    CF_TRY(tmp.get(&d_sizes, (size_t)U + 1, "filtered sizes"));
+    CF_TRY(tmp.get(&d_new_ptr, (size_t)U + 1, "filtered cloud_ptr"));
+    CF_HIP(hipMemsetAsync(d_mult, 0, (size_t)(K + 1) * 4, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_sizes, 0, (size_t)(U + 1) * 4, ctx->stream));
+    if (N) hipLaunchKernelGGL(cf_mult_hist_kernel, dim3((unsigned)grid_e), dim3(256), 0, ctx->stream, (const int32_t*)ctx->d_entries, N, d_mult);
+    if (U) hipLaunchKernelGGL(cf_mult_filter_kernel, dim3((unsigned)grid_u), dim3(256), 0, ctx->stream, (const int64_t*)ctx->d_cloud_ptr,
+                              (const int32_t*)ctx->d_entries, U, (const uint32_t*)d_mult, min_mult, max_mult, 0, d_sizes,
+                              (const int64_t*)nullptr, (int32_t*)nullptr);
+    CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_sizes, d_new_ptr, U + 1, &total));
+    CF_TRY(tmp.get(&d_new_entries, (size_t)total, "filtered entries"));
+    if (U && total)
+        hipLaunchKernelGGL(cf_mult_filter_kernel, dim3((unsigned)grid_u), dim3(256), 0, ctx->stream, (const int64_t*)ctx->d_cloud_ptr,
+                           (const int32_t*)ctx->d_entries, U, (const uint32_t*)d_mult, min_mult, max_mult, 1, d_sizes,
+                           (const int64_t*)d_new_ptr, d_new_entries);
+    CF_KERNEL_CHECK("cf_mult_filter_kernel");
+    CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    CF_HIP(hipEventSynchronize(ctx->ev1));
+    (void)hipEventElapsedTime(&ctx->times.filter_ms, ctx->ev0, ctx->ev1);
     cf_free_gview(ctx);
     cf_free_contig(ctx);
     cf_release_t(ctx, ctx->d_cloud_ptr, (size_t)U + 1);
     cf_release_t(ctx, ctx->d_entries, (size_t)N);
+    tmp.keep(d_new_ptr);
+    tmp.keep(d_new_entries);
     ctx->d_cloud_ptr = d_new_ptr;
     ctx->d_entries = d_new_entries;
     ctx->n_entries = total;
@@ -505,14 +489,13 @@ int cf_get_unique_mask(cf_ctx* ctx, uint8_t* mask) {
     const int64_t n = ctx->n_kmers;
     if (!n) return 0;
     CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
     uint8_t* d_tmp = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_tmp, (size_t)n, "unique mask bytes"));
+    CF_TRY(tmp.get(&d_tmp, (size_t)n, "unique mask bytes"));
     const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
     hipLaunchKernelGGL(cf_bits_expand_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_unique_bits, n, d_tmp);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(mask, d_tmp, (size_t)n, hipMemcpyDefault);
-    cf_release_t(ctx, d_tmp, (size_t)n);
-    if (e != hipSuccess) return cf_fail(ctx, -5, std::string("cf_get_unique_mask: ") + hipGetErrorString(e));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    CF_HIP(hipMemcpy(mask, d_tmp, (size_t)n, hipMemcpyDefault));
     return 0;
 }
 
@@ -522,27 +505,21 @@ int cf_or_unique_mask(cf_ctx* ctx, const uint8_t* mask) {
     const int64_t n = ctx->n_kmers;
     if (!n) return 0;
     CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
     uint8_t* d_tmp = nullptr;
     unsigned long long* d_cnt = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_tmp, (size_t)n, "unique mask bytes"));
-    int rc = cf_alloc_t(ctx, &d_cnt, 2, "unique count");
+    CF_TRY(tmp.get(&d_tmp, (size_t)n, "unique mask bytes"));
+    CF_TRY(tmp.get(&d_cnt, 2, "unique count"));
     unsigned long long h = 0;
-    if (rc == 0) {
-        hipError_t e = hipMemcpy(d_tmp, mask, (size_t)n, hipMemcpyDefault);
-        if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, 16, ctx->stream);
-        if (e == hipSuccess) {
-            const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
-            hipLaunchKernelGGL(cf_bits_or_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, ctx->d_unique_bits, n, (const uint8_t*)d_tmp);
-            hipLaunchKernelGGL(cf_bits_count_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_unique_bits,
-                               ctx->unique_words, d_cnt);
-            e = hipMemcpy(&h, d_cnt, 8, hipMemcpyDeviceToHost);
-        }
-        if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("cf_or_unique_mask: ") + hipGetErrorString(e));
-        else ctx->stats.n_unique = (int64_t)h;
-    }
-    if (d_cnt) cf_release_t(ctx, d_cnt, 2);
-    cf_release_t(ctx, d_tmp, (size_t)n);
-    return rc;
+    CF_HIP(hipMemcpy(d_tmp, mask, (size_t)n, hipMemcpyDefault));
+    CF_HIP(hipMemsetAsync(d_cnt, 0, 16, ctx->stream));
+    const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
+    hipLaunchKernelGGL(cf_bits_or_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, ctx->d_unique_bits, n, (const uint8_t*)d_tmp);
+    hipLaunchKernelGGL(cf_bits_count_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_unique_bits,
+                       ctx->unique_words, d_cnt);
+    CF_HIP(hipMemcpy(&h, d_cnt, 8, hipMemcpyDeviceToHost));
+    ctx->stats.n_unique = (int64_t)h;
+    return 0;
 }
 
 int cf_reset_unique(cf_ctx* ctx) {

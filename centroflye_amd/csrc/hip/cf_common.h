@@ -227,6 +227,38 @@ inline void cf_release_t(cf_ctx* ctx, T*& p, size_t n) {
     p = nullptr;
 }
 
+// Scratch buffers of one host function: every exit releases what the guard still holds, last taken first, with the size
+// it was taken with.  keep() hands a buffer on (to the context or the caller), drop() releases one before the end.
+struct cf_scratch {
+    explicit cf_scratch(cf_ctx* c) : ctx(c) {}
+    cf_scratch(const cf_scratch&) = delete;
+    cf_scratch& operator=(const cf_scratch&) = delete;
+    ~cf_scratch() { release_all(); }
+    template <class T> int get(T** p, size_t n, const char* what) {
+        const int rc = cf_alloc_t(ctx, p, n, what);
+        if (rc == 0) held.emplace_back((void*)*p, n * sizeof(T));
+        return rc;
+    }
+    void keep(void* p) { const auto it = find(p); if (it != held.end()) held.erase(it); }
+    void drop(void* p) {
+        const auto it = find(p);
+        if (it == held.end()) return;
+        cf_release(ctx, it->first, it->second);
+        held.erase(it);
+    }
+    void release_all() {
+        for (auto it = held.rbegin(); it != held.rend(); ++it) cf_release(ctx, it->first, it->second);
+        held.clear();
+    }
+
+private:
+    std::vector<std::pair<void*, size_t>>::iterator find(void* p) {
+        return p ? std::find_if(held.begin(), held.end(), [p](const std::pair<void*, size_t>& e) { return e.first == p; }) : held.end();
+    }
+    cf_ctx* ctx;
+    std::vector<std::pair<void*, size_t>> held;
+};
+
 #define CF_HIP(expr)                                                                          \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \

@@ -319,30 +319,26 @@ static int table_compact(cf_ctx* ctx, uint32_t max_nonuniq, uint32_t lo, uint32_
                          unsigned long long** d_keys, uint32_t** d_pres, uint32_t** d_multi, int pred = 0,
                          unsigned long long t_val = 0, unsigned long long t_key = 0) {
     const int grid = std::max(1, ctx->n_cu) * 8;
+    cf_scratch tmp(ctx);
     unsigned long long* d_cnt = nullptr;
     int64_t* d_blk = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_cnt, 4, "select counters"));
-    int rc = cf_alloc_t(ctx, &d_blk, (size_t)grid + 1, "select block counts");
+    CF_TRY(tmp.get(&d_cnt, 4, "select counters"));
+    CF_TRY(tmp.get(&d_blk, (size_t)grid + 1, "select block counts"));
     unsigned long long h[4] = {0, 0, 0, 0};
-    do {
-        if (rc) break;
-        if (hipMemsetAsync(d_cnt, 0, 32, ctx->stream) != hipSuccess || hipMemsetAsync(d_blk, 0, (size_t)(grid + 1) * 8, ctx->stream) != hipSuccess) { rc = cf_fail(ctx, -5, "select memset"); break; }
-        hipLaunchKernelGGL(cf_select_kernel, dim3((unsigned)grid), dim3(256), 16, ctx->stream, (const cf_slot*)ctx->d_table, (uint64_t)ctx->table_cap,
-                           max_nonuniq, lo, hi, 0, d_cnt, d_blk, (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, pred, t_val, t_key);
-        if (hipMemcpy(h, d_cnt, 32, hipMemcpyDeviceToHost) != hipSuccess) { rc = cf_fail(ctx, -5, "select count"); break; }
-        counts_out[0] = h[0]; counts_out[1] = h[1]; counts_out[2] = h[2];
-        if ((rc = alloc((int64_t)h[2]))) break;
-        if (h[2] == 0 || !*d_keys) break;
-        if ((rc = cf_scan_exclusive_i64(ctx, d_blk, d_blk, grid + 1, nullptr))) break;
-        hipLaunchKernelGGL(cf_select_kernel, dim3((unsigned)grid), dim3(256), 16, ctx->stream, (const cf_slot*)ctx->d_table, (uint64_t)ctx->table_cap,
-                           max_nonuniq, lo, hi, 1, d_cnt, d_blk, *d_keys, d_pres ? *d_pres : (uint32_t*)nullptr, d_multi ? *d_multi : (uint32_t*)nullptr, pred, t_val, t_key);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_select_kernel: ") + hipGetErrorString(e)); break; }
-    } while (0);
-    if (d_blk) cf_release_t(ctx, d_blk, (size_t)grid + 1);
-    cf_release_t(ctx, d_cnt, 4);
-    return rc;
+    CF_HIP(hipMemsetAsync(d_cnt, 0, 32, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_blk, 0, (size_t)(grid + 1) * 8, ctx->stream));
+    hipLaunchKernelGGL(cf_select_kernel, dim3((unsigned)grid), dim3(256), 16, ctx->stream, (const cf_slot*)ctx->d_table, (uint64_t)ctx->table_cap,
+                       max_nonuniq, lo, hi, 0, d_cnt, d_blk, (unsigned long long*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, pred, t_val, t_key);
+    CF_HIP(hipMemcpy(h, d_cnt, 32, hipMemcpyDeviceToHost));
+    counts_out[0] = h[0]; counts_out[1] = h[1]; counts_out[2] = h[2];
+    CF_TRY(alloc((int64_t)h[2]));
+    if (h[2] == 0 || !*d_keys) return 0;
+    CF_TRY(cf_scan_exclusive_i64(ctx, d_blk, d_blk, grid + 1, nullptr));
+    hipLaunchKernelGGL(cf_select_kernel, dim3((unsigned)grid), dim3(256), 16, ctx->stream, (const cf_slot*)ctx->d_table, (uint64_t)ctx->table_cap,
+                       max_nonuniq, lo, hi, 1, d_cnt, d_blk, *d_keys, d_pres ? *d_pres : (uint32_t*)nullptr, d_multi ? *d_multi : (uint32_t*)nullptr, pred, t_val, t_key);
+    CF_KERNEL_CHECK("cf_select_kernel");
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 int cf_count_sorted(cf_ctx* ctx, int32_t k, int64_t read_lo, int64_t read_hi, int64_t n_w, int occ);   // cf_count2.hip
@@ -403,45 +399,37 @@ static int count_impl(cf_ctx* ctx, int32_t k, int64_t read_lo, int64_t read_hi, 
         }
         CF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
         CF_HIP(hipMemsetAsync(ctx->d_table, 0, (size_t)cap * sizeof(cf_slot), ctx->stream));
+        cf_scratch tmp(ctx);      // of this attempt
         cf_count_item* d_items = nullptr;
         unsigned long long* d_cnt = nullptr;
-        CF_TRY(cf_alloc_t(ctx, &d_items, items.size(), "count items"));
-        int rc = cf_alloc_t(ctx, &d_cnt, 2, "count counters");
+        CF_TRY(tmp.get(&d_items, items.size(), "count items"));
+        CF_TRY(tmp.get(&d_cnt, 2, "count counters"));
         unsigned long long h_cnt[2] = {0, 0};
-        if (rc == 0) {
-            hipError_t e = hipMemsetAsync(d_cnt, 0, 16, ctx->stream);
-            if (e == hipSuccess && !items.empty())
-                e = hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(cf_count_item), hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess && !items.empty()) {
-                const int tile_w = ctx->count_tile;
-                const size_t lds = (size_t)slots * (mode == 1 ? 12 : 8) + (size_t)((CNT_THREADS * tile_w + 64 + 15) & ~15) + 16;
-                const int grid = (int)std::min<int64_t>((int64_t)items.size(), (int64_t)std::max(1, ctx->n_cu) * 8);
-                if (lds > 64 * 1024)
-                    e = mode == 1 ? hipFuncSetAttribute((const void*)cf_occ_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-                                  : hipFuncSetAttribute((const void*)cf_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (e == hipSuccess) {
-                    (void)hipEventRecord(ctx->ev2, ctx->stream);
-                    if (mode == 1)
-                        hipLaunchKernelGGL(cf_occ_kernel, dim3((unsigned)grid), dim3(CNT_THREADS), lds, ctx->stream,
-                                           (const uint8_t*)ctx->d_bases, (const int64_t*)ctx->d_read_off, (const cf_count_item*)d_items,
-                                           (int)items.size(), (int)k, slots, tile_w, ctx->d_table, (uint64_t)(cap - 1), (unsigned int*)(d_cnt + 1));
-                    else
-                        hipLaunchKernelGGL(cf_count_kernel, dim3((unsigned)grid), dim3(CNT_THREADS), lds, ctx->stream,
-                                           (const uint8_t*)ctx->d_bases, (const int64_t*)ctx->d_read_off, (const cf_count_item*)d_items,
-                                           (int)items.size(), (int)k, slots, tile_w, ctx->d_table, (uint64_t)(cap - 1), d_cnt,
-                                           (unsigned int*)(d_cnt + 1));
-                    e = hipGetLastError();
-                    (void)hipEventRecord(ctx->ev3, ctx->stream);
-                }
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 16, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-            if (e == hipSuccess) e = hipEventSynchronize(ctx->ev1);
-            if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("cf_count_kmers: ") + hipGetErrorString(e));
+        CF_HIP(hipMemsetAsync(d_cnt, 0, 16, ctx->stream));
+        if (!items.empty()) {
+            CF_HIP(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(cf_count_item), hipMemcpyHostToDevice, ctx->stream));
+            const int tile_w = ctx->count_tile;
+            const size_t lds = (size_t)slots * (mode == 1 ? 12 : 8) + (size_t)((CNT_THREADS * tile_w + 64 + 15) & ~15) + 16;
+            const int grid = (int)std::min<int64_t>((int64_t)items.size(), (int64_t)std::max(1, ctx->n_cu) * 8);
+            if (lds > 64 * 1024)
+                CF_HIP(mode == 1 ? hipFuncSetAttribute((const void*)cf_occ_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
+                                 : hipFuncSetAttribute((const void*)cf_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            (void)hipEventRecord(ctx->ev2, ctx->stream);
+            if (mode == 1)
+                hipLaunchKernelGGL(cf_occ_kernel, dim3((unsigned)grid), dim3(CNT_THREADS), lds, ctx->stream,
+                                   (const uint8_t*)ctx->d_bases, (const int64_t*)ctx->d_read_off, (const cf_count_item*)d_items,
+                                   (int)items.size(), (int)k, slots, tile_w, ctx->d_table, (uint64_t)(cap - 1), (unsigned int*)(d_cnt + 1));
+            else
+                hipLaunchKernelGGL(cf_count_kernel, dim3((unsigned)grid), dim3(CNT_THREADS), lds, ctx->stream,
+                                   (const uint8_t*)ctx->d_bases, (const int64_t*)ctx->d_read_off, (const cf_count_item*)d_items,
+                                   (int)items.size(), (int)k, slots, tile_w, ctx->d_table, (uint64_t)(cap - 1), d_cnt,
+                                   (unsigned int*)(d_cnt + 1));
+            CF_KERNEL_CHECK((mode == 1 ? "cf_occ_kernel" : "cf_count_kernel"));
+            (void)hipEventRecord(ctx->ev3, ctx->stream);
         }
-        if (d_cnt) cf_release_t(ctx, d_cnt, 2);
-        cf_release_t(ctx, d_items, items.size());
-        if (rc) return rc;
+        CF_HIP(hipMemcpyAsync(h_cnt, d_cnt, 16, hipMemcpyDeviceToHost, ctx->stream));
+        CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+        CF_HIP(hipEventSynchronize(ctx->ev1));
         const unsigned int flags = (unsigned int)h_cnt[1];
         if (flags & 1u) { cap *= 2; continue; }            // HBM table full: retry larger
         if (flags & 2u) { ++shrink; continue; }            // an LDS set overflowed: more classes per read
@@ -486,16 +474,15 @@ static int top_exact(cf_ctx* ctx, int64_t n, uint64_t* keys_out, uint64_t* count
 // small dense table, and the threshold searches run on that (255 -> ~20 ms for the top 6 165 of 1.7e8 k-mers).
 static int top_impl(cf_ctx* ctx, int64_t n, uint64_t* keys_out, uint64_t* counts_out, int64_t* n_out) {
     if (n <= 0 || !keys_out || ctx->table_cap < 4096) return top_exact(ctx, n, keys_out, counts_out, n_out);
-    unsigned long long* d_hist = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_hist, 64, "count magnitude histogram"));
     unsigned long long hist[64];
-    hipError_t e = hipMemsetAsync(d_hist, 0, 64 * 8, ctx->stream);
-    if (e == hipSuccess) {
+    {
+        cf_scratch tmp(ctx);
+        unsigned long long* d_hist = nullptr;
+        CF_TRY(tmp.get(&d_hist, 64, "count magnitude histogram"));
+        CF_HIP(hipMemsetAsync(d_hist, 0, 64 * 8, ctx->stream));
         hipLaunchKernelGGL(cf_val_log2_hist_kernel, dim3((unsigned)(std::max(1, ctx->n_cu) * 8)), dim3(256), 256, ctx->stream, (const cf_slot*)ctx->d_table, (uint64_t)ctx->table_cap, d_hist);
-        e = hipMemcpy(hist, d_hist, 64 * 8, hipMemcpyDeviceToHost);
+        CF_HIP(hipMemcpy(hist, d_hist, 64 * 8, hipMemcpyDeviceToHost));
     }
-    cf_release_t(ctx, d_hist, 64);
-    if (e != hipSuccess) return cf_fail(ctx, -5, std::string("cf_top_kmers histogram: ") + hipGetErrorString(e));
     int b = 63;
     unsigned long long above = 0, total = 0;
     for (int i = 0; i < 64; ++i) total += hist[i];
@@ -504,33 +491,29 @@ static int top_impl(cf_ctx* ctx, int64_t n, uint64_t* keys_out, uint64_t* counts
     if (b == 0 || n_cand > total / 4 || n_cand < (unsigned long long)std::min<int64_t>(n, (int64_t)total)) return top_exact(ctx, n, keys_out, counts_out, n_out);      // no real reduction: search the table itself
     // compact count >= 2^b into a small dense table and search there
     unsigned long long c[3] = {0, 0, 0};
+    cf_scratch tmp(ctx);
     unsigned long long* d_keys = nullptr; uint32_t *d_lo = nullptr, *d_hi = nullptr;
     int64_t m_sel = 0;
     auto alloc = [&](int64_t m) -> int {
         m_sel = m;
-        CF_TRY(cf_alloc_t(ctx, &d_keys, (size_t)m, "top candidates keys"));
-        CF_TRY(cf_alloc_t(ctx, &d_lo, (size_t)m, "top candidates lo"));
-        return cf_alloc_t(ctx, &d_hi, (size_t)m, "top candidates hi");
+        CF_TRY(tmp.get(&d_keys, (size_t)m, "top candidates keys"));
+        CF_TRY(tmp.get(&d_lo, (size_t)m, "top candidates lo"));
+        return tmp.get(&d_hi, (size_t)m, "top candidates hi");
     };
-    int rc = table_compact(ctx, 0, 0, 0, c, alloc, &d_keys, &d_lo, &d_hi, 1, (1ull << b) - 1ull, ~0ull);
+    CF_TRY(table_compact(ctx, 0, 0, 0, c, alloc, &d_keys, &d_lo, &d_hi, 1, (1ull << b) - 1ull, ~0ull));
     cf_slot* d_small = nullptr;
-    if (rc == 0 && (unsigned long long)m_sel != n_cand) rc = cf_fail(ctx, -5, "cf_top_kmers: internal error, candidate count mismatch");
-    if (rc == 0) rc = cf_alloc_t(ctx, &d_small, (size_t)m_sel, "top candidates");
-    if (rc == 0) {
-        hipLaunchKernelGGL(cf_pack_slots_kernel, dim3((unsigned)cf_grid_for(m_sel, 256, std::max(1, ctx->n_cu) * 8)), dim3(256), 0, ctx->stream,
-                           (const unsigned long long*)d_keys, (const uint32_t*)d_lo, (const uint32_t*)d_hi, m_sel, d_small);
-        if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = cf_fail(ctx, -5, "cf_top_kmers: candidate pack");
-    }
-    if (d_hi) cf_release_t(ctx, d_hi, (size_t)m_sel);
-    if (d_lo) cf_release_t(ctx, d_lo, (size_t)m_sel);
-    if (d_keys) cf_release_t(ctx, d_keys, (size_t)m_sel);
-    if (rc == 0) {
-        cf_slot* const big = ctx->d_table; const uint64_t big_cap = ctx->table_cap;
-        ctx->d_table = d_small; ctx->table_cap = (uint64_t)m_sel;
-        rc = top_exact(ctx, n, keys_out, counts_out, n_out);
-        ctx->d_table = big; ctx->table_cap = big_cap;
-    }
-    if (d_small) cf_release_t(ctx, d_small, (size_t)m_sel);
+    if ((unsigned long long)m_sel != n_cand) return cf_fail(ctx, -5, "cf_top_kmers: internal error, candidate count mismatch");
+    CF_TRY(tmp.get(&d_small, (size_t)m_sel, "top candidates"));
+    hipLaunchKernelGGL(cf_pack_slots_kernel, dim3((unsigned)cf_grid_for(m_sel, 256, std::max(1, ctx->n_cu) * 8)), dim3(256), 0, ctx->stream,
+                       (const unsigned long long*)d_keys, (const uint32_t*)d_lo, (const uint32_t*)d_hi, m_sel, d_small);
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    tmp.drop(d_hi);
+    tmp.drop(d_lo);
+    tmp.drop(d_keys);
+    cf_slot* const big = ctx->d_table; const uint64_t big_cap = ctx->table_cap;
+    ctx->d_table = d_small; ctx->table_cap = (uint64_t)m_sel;
+    const int rc = top_exact(ctx, n, keys_out, counts_out, n_out);
+    ctx->d_table = big; ctx->table_cap = big_cap;
     return rc;
 }
 
@@ -566,28 +549,23 @@ static int top_exact(cf_ctx* ctx, int64_t n, uint64_t* keys_out, uint64_t* count
         CF_TRY(count_ge(T, mid, &cnt, nullptr));
         if ((int64_t)cnt - (int64_t)above >= need) klo = mid; else khi = mid - 1;
     }
+    cf_scratch tmp(ctx);
     unsigned long long* d_keys = nullptr; uint32_t *d_lo = nullptr, *d_hi = nullptr;
     int64_t n_sel = 0;
     auto alloc = [&](int64_t m) -> int {
         n_sel = m;
-        CF_TRY(cf_alloc_t(ctx, &d_keys, (size_t)m, "top keys"));
-        CF_TRY(cf_alloc_t(ctx, &d_lo, (size_t)m, "top counts lo"));
-        return cf_alloc_t(ctx, &d_hi, (size_t)m, "top counts hi");
+        CF_TRY(tmp.get(&d_keys, (size_t)m, "top keys"));
+        CF_TRY(tmp.get(&d_lo, (size_t)m, "top counts lo"));
+        return tmp.get(&d_hi, (size_t)m, "top counts hi");
     };
-    int rc = table_compact(ctx, 0, 0, 0, c, alloc, &d_keys, &d_lo, &d_hi, 1, T, klo);
+    CF_TRY(table_compact(ctx, 0, 0, 0, c, alloc, &d_keys, &d_lo, &d_hi, 1, T, klo));
     std::vector<unsigned long long> hk((size_t)n_sel);
     std::vector<uint32_t> hl((size_t)n_sel), hh((size_t)n_sel);
-    if (rc == 0 && n_sel != n) rc = cf_fail(ctx, -5, "cf_top_kmers: internal error, selection size mismatch");
-    if (rc == 0) {
-        hipError_t e = hipMemcpy(hk.data(), d_keys, (size_t)n_sel * 8, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(hl.data(), d_lo, (size_t)n_sel * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(hh.data(), d_hi, (size_t)n_sel * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("cf_top_kmers copy: ") + hipGetErrorString(e));
-    }
-    if (d_hi) cf_release_t(ctx, d_hi, (size_t)n_sel);
-    if (d_lo) cf_release_t(ctx, d_lo, (size_t)n_sel);
-    if (d_keys) cf_release_t(ctx, d_keys, (size_t)n_sel);
-    if (rc) return rc;
+    if (n_sel != n) return cf_fail(ctx, -5, "cf_top_kmers: internal error, selection size mismatch");
+    CF_HIP(hipMemcpy(hk.data(), d_keys, (size_t)n_sel * 8, hipMemcpyDeviceToHost));
+    CF_HIP(hipMemcpy(hl.data(), d_lo, (size_t)n_sel * 4, hipMemcpyDeviceToHost));
+    CF_HIP(hipMemcpy(hh.data(), d_hi, (size_t)n_sel * 4, hipMemcpyDeviceToHost));
+    tmp.release_all();
     std::vector<int64_t> idx((size_t)n);
     for (int64_t i = 0; i < n; ++i) idx[(size_t)i] = i;
     auto val = [&](int64_t i) { return (unsigned long long)hl[(size_t)i] | ((unsigned long long)hh[(size_t)i] << 32); };
@@ -626,6 +604,7 @@ int cf_get_table(cf_ctx* ctx, uint64_t* keys, uint32_t* pres, uint32_t* multi, i
     if (!ctx || !n_out) return -22;
     if (!ctx->d_table) return cf_fail(ctx, -22, "cf_get_table: no table");
     CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
     unsigned long long *d_keys = nullptr;
     uint32_t *d_pres = nullptr, *d_multi = nullptr;
     unsigned long long counts[3] = {0, 0, 0};
@@ -635,21 +614,17 @@ int cf_get_table(cf_ctx* ctx, uint64_t* keys, uint32_t* pres, uint32_t* multi, i
         if (!keys) return 0;   // size query
         if (n > cap) return cf_fail(ctx, -22, "cf_get_table: buffer too small");
         n_alloc = n;
-        CF_TRY(cf_alloc_t(ctx, &d_keys, (size_t)n, "dump keys"));
-        CF_TRY(cf_alloc_t(ctx, &d_pres, (size_t)n, "dump pres"));
-        return cf_alloc_t(ctx, &d_multi, (size_t)n, "dump multi");
+        CF_TRY(tmp.get(&d_keys, (size_t)n, "dump keys"));
+        CF_TRY(tmp.get(&d_pres, (size_t)n, "dump pres"));
+        return tmp.get(&d_multi, (size_t)n, "dump multi");
     };
-    int rc = table_compact(ctx, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, counts, alloc, &d_keys, &d_pres, &d_multi);
-    if (rc == 0 && keys && n_alloc) {
-        hipError_t e = hipMemcpy(keys, d_keys, (size_t)n_alloc * 8, hipMemcpyDefault);
-        if (e == hipSuccess) e = hipMemcpy(pres, d_pres, (size_t)n_alloc * 4, hipMemcpyDefault);
-        if (e == hipSuccess) e = hipMemcpy(multi, d_multi, (size_t)n_alloc * 4, hipMemcpyDefault);
-        if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("cf_get_table copy: ") + hipGetErrorString(e));
+    CF_TRY(table_compact(ctx, 0xFFFFFFFFu, 0u, 0xFFFFFFFFu, counts, alloc, &d_keys, &d_pres, &d_multi));
+    if (keys && n_alloc) {
+        CF_HIP(hipMemcpy(keys, d_keys, (size_t)n_alloc * 8, hipMemcpyDefault));
+        CF_HIP(hipMemcpy(pres, d_pres, (size_t)n_alloc * 4, hipMemcpyDefault));
+        CF_HIP(hipMemcpy(multi, d_multi, (size_t)n_alloc * 4, hipMemcpyDefault));
     }
-    if (d_multi) cf_release_t(ctx, d_multi, (size_t)n_alloc);
-    if (d_pres) cf_release_t(ctx, d_pres, (size_t)n_alloc);
-    if (d_keys) cf_release_t(ctx, d_keys, (size_t)n_alloc);
-    return rc;
+    return 0;
 }
 
 int cf_merge_table(cf_ctx* ctx, const uint64_t* keys, const uint32_t* pres, const uint32_t* multi, int64_t n) {
@@ -658,31 +633,24 @@ int cf_merge_table(cf_ctx* ctx, const uint64_t* keys, const uint32_t* pres, cons
     if (ctx->table_dense) return cf_fail(ctx, -22, "cf_merge_table: the table of cf_count_kmers is a dense array (call cf_reset_table first)");
     if (n <= 0) return 0;
     CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
     unsigned long long* d_keys = nullptr; uint32_t *d_pres = nullptr, *d_multi = nullptr; unsigned int* d_flags = nullptr;
-    int rc = 0;
     unsigned int flags = 0;
-    do {
-        if ((rc = cf_alloc_t(ctx, &d_keys, (size_t)n, "merge keys"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_pres, (size_t)n, "merge pres"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_multi, (size_t)n, "merge multi"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_flags, 4, "merge flags"))) break;
-        hipError_t e = hipMemcpy(d_keys, keys, (size_t)n * 8, hipMemcpyDefault);
-        if (e == hipSuccess) e = hipMemcpy(d_pres, pres, (size_t)n * 4, hipMemcpyDefault);
-        if (e == hipSuccess) e = hipMemcpy(d_multi, multi, (size_t)n * 4, hipMemcpyDefault);
-        if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 16, ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_merge_table copy: ") + hipGetErrorString(e)); break; }
-        const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
-        hipLaunchKernelGGL(cf_table_merge_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, ctx->d_table,
-                           (uint64_t)(ctx->table_cap - 1), (const unsigned long long*)d_keys, (const uint32_t*)d_pres,
-                           (const uint32_t*)d_multi, n, d_flags);
-        if (hipMemcpy(&flags, d_flags, 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = cf_fail(ctx, -5, "cf_merge_table sync"); break; }
-        if (flags & 1u) rc = cf_fail(ctx, -34, "cf_merge_table: table full");
-    } while (0);
-    if (d_flags) cf_release_t(ctx, d_flags, 4);
-    if (d_multi) cf_release_t(ctx, d_multi, (size_t)n);
-    if (d_pres) cf_release_t(ctx, d_pres, (size_t)n);
-    if (d_keys) cf_release_t(ctx, d_keys, (size_t)n);
-    return rc;
+    CF_TRY(tmp.get(&d_keys, (size_t)n, "merge keys"));
+    CF_TRY(tmp.get(&d_pres, (size_t)n, "merge pres"));
+    CF_TRY(tmp.get(&d_multi, (size_t)n, "merge multi"));
+    CF_TRY(tmp.get(&d_flags, 4, "merge flags"));
+    CF_HIP(hipMemcpy(d_keys, keys, (size_t)n * 8, hipMemcpyDefault));
+    CF_HIP(hipMemcpy(d_pres, pres, (size_t)n * 4, hipMemcpyDefault));
+    CF_HIP(hipMemcpy(d_multi, multi, (size_t)n * 4, hipMemcpyDefault));
+    CF_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
+    const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
+    hipLaunchKernelGGL(cf_table_merge_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, ctx->d_table,
+                       (uint64_t)(ctx->table_cap - 1), (const unsigned long long*)d_keys, (const uint32_t*)d_pres,
+                       (const uint32_t*)d_multi, n, d_flags);
+    CF_HIP(hipMemcpy(&flags, d_flags, 4, hipMemcpyDeviceToHost));
+    if (flags & 1u) return cf_fail(ctx, -34, "cf_merge_table: table full");
+    return 0;
 }
 
 int cf_select_rare(cf_ctx* ctx, int32_t max_nonuniq, uint32_t lo, uint32_t hi, int64_t* n_out) {
@@ -692,24 +660,23 @@ int cf_select_rare(cf_ctx* ctx, int32_t max_nonuniq, uint32_t lo, uint32_t hi, i
     const uint32_t mn = max_nonuniq < 0 ? 0u : (uint32_t)max_nonuniq;
     if (max_nonuniq < 0) hi = 0, lo = 1;  // multi <= negative is never true: empty set
     CF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    cf_scratch tmp(ctx);
     unsigned long long *d_keys = nullptr, *d_tmp = nullptr;
     unsigned long long counts[3] = {0, 0, 0};
     int64_t n_sel = 0;
     auto alloc = [&](int64_t n) -> int {
         if (n >= (int64_t)1 << 31) return cf_fail(ctx, -34, "more than 2^31 selected k-mers");
         n_sel = n;
-        CF_TRY(cf_alloc_t(ctx, &d_keys, (size_t)n, "selected k-mers"));
-        return cf_alloc_t(ctx, &d_tmp, (size_t)n, "sort scratch");
+        CF_TRY(tmp.get(&d_keys, (size_t)n, "selected k-mers"));
+        return tmp.get(&d_tmp, (size_t)n, "sort scratch");
     };
-    int rc = table_compact(ctx, mn, lo, hi, counts, alloc, &d_keys, nullptr, nullptr);
-    if (rc == 0) {
-        ctx->stats.n_distinct = (int64_t)counts[0];
-        ctx->stats.n_kept = (int64_t)counts[1];
-        if (n_sel) rc = cf_radix_sort_u64(ctx, d_keys, d_tmp, n_sel, 2 * ctx->k);
-    }
-    if (d_tmp) cf_release_t(ctx, d_tmp, (size_t)n_sel);
-    if (rc) { if (d_keys) cf_release_t(ctx, d_keys, (size_t)n_sel); return rc; }
+    CF_TRY(table_compact(ctx, mn, lo, hi, counts, alloc, &d_keys, nullptr, nullptr));
+    ctx->stats.n_distinct = (int64_t)counts[0];
+    ctx->stats.n_kept = (int64_t)counts[1];
+    if (n_sel) CF_TRY(cf_radix_sort_u64(ctx, d_keys, d_tmp, n_sel, 2 * ctx->k));
+    tmp.drop(d_tmp);
     cf_free_kmers(ctx);
+    tmp.keep(d_keys);
     ctx->d_kmers = d_keys;
     ctx->n_kmers = n_sel;
     CF_TRY(cf_install_kmers(ctx, ctx->k));

@@ -560,19 +560,6 @@ cf_c2_reduce_occ_kernel(const unsigned long long* __restrict__ recs, int64_t n, 
 }
 
 namespace {
-struct Bufs2 {
-    cf_ctx* ctx;
-    std::vector<std::pair<void*, size_t>> v;
-    explicit Bufs2(cf_ctx* c) : ctx(c) {}
-    ~Bufs2() { for (auto it = v.rbegin(); it != v.rend(); ++it) cf_release(ctx, it->first, it->second); }
-    template <class T> int get(T** p, size_t n, const char* what) {
-        int rc = cf_alloc_t(ctx, p, n, what);
-        if (rc == 0) v.emplace_back((void*)*p, n * sizeof(T));
-        return rc;
-    }
-    void keep(void* p) { for (auto& e : v) if (e.first == p) e.first = nullptr; }
-};
-
 template <class K>
 int launch_nb(int nb, K&& k) {      // radix bits of a pass -> template instance
     switch (nb) {
@@ -620,12 +607,14 @@ int cf_count_sorted(cf_ctx* ctx, int32_t k, int64_t read_lo, int64_t read_hi, in
     if (!occ && !ctx->count_bits && n_w > ((int64_t)1 << 24) && (max_win >> bits) > 256) return 1;
     CF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     cf_free_table(ctx);
-    Bufs2 tmp(ctx);
+    cf_scratch tmp(ctx);
     unsigned long long *d_a = nullptr, *d_b = nullptr;
     cf_c2_tile* d_tiles = nullptr;
     unsigned long long* d_cnt = nullptr;
-    CF_TRY(tmp.get(&d_a, (size_t)std::max<int64_t>(n_w, 2), "count records"));
-    CF_TRY(tmp.get(&d_b, (size_t)std::max<int64_t>(n_w, 2), "count records (pong)"));
+    // (an even number of records: the buffer that the reduce writes becomes the table, whose size is kept in whole slots)
+    const size_t n_alloc = ((size_t)std::max<int64_t>(n_w, 2) + 1) & ~(size_t)1;
+    CF_TRY(tmp.get(&d_a, n_alloc, "count records"));
+    CF_TRY(tmp.get(&d_b, n_alloc, "count records (pong)"));
     CF_TRY(tmp.get(&d_tiles, tiles.size() + 1, "count tiles"));
     CF_TRY(tmp.get(&d_cnt, 16, "count counters"));
     if (n_tiles1) CF_HIP(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(cf_c2_tile), hipMemcpyHostToDevice, ctx->stream));
@@ -641,7 +630,7 @@ int cf_count_sorted(cf_ctx* ctx, int32_t k, int64_t read_lo, int64_t read_hi, in
         const int64_t nh = (int64_t)n_tiles << nb;
         uint32_t* d_hist = nullptr;
         int64_t* d_offs = nullptr;
-        Bufs2 pass(ctx);
+        cf_scratch pass(ctx);
         CF_TRY(pass.get(&d_hist, (size_t)nh + 1, "count histogram"));
         CF_TRY(pass.get(&d_offs, (size_t)nh + 1, "count offsets"));
         const int grid = std::min(n_tiles, max_grid);
@@ -686,7 +675,7 @@ int cf_count_sorted(cf_ctx* ctx, int32_t k, int64_t read_lo, int64_t read_hi, in
     unsigned long long h_cnt[4] = {0, 0, 0, 0};
     cf_slot* d_out = (cf_slot*)dst;
     unsigned long long out_cap = (unsigned long long)std::max<int64_t>(n_w, 2) / 2;
-    size_t out_bytes = (size_t)std::max<int64_t>(n_w, 2) * 8;
+    size_t out_bytes = n_alloc * 8;
     const size_t lds_r = (size_t)C2_RTILE * 8 + (size_t)C2_TAB * (8 + 4 + 4) + 24 + 16;
     cf_slot* d_exact = nullptr;
     const int64_t n_buckets = (int64_t)1 << bits;
@@ -717,18 +706,18 @@ int cf_count_sorted(cf_ctx* ctx, int32_t k, int64_t read_lo, int64_t read_hi, in
         { unsigned long long st[8]; if (hipMemcpy(st, d_cnt + 8, 64, hipMemcpyDeviceToHost) == hipSuccess)
             std::fprintf(stderr, "[cf_c2 stamps] ticket=%llu clear=%llu stage=%llu lookback=%llu table=%llu wait=%llu flush=%llu (shader cycles over %d workgroups)\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], grid); }
 #endif
-        if (h_cnt[2] & 1ull) { if (d_exact) cf_release(ctx, d_exact, out_bytes); return 1; }     // a bucket with too many k-mers for the LDS table: table path
+        if (h_cnt[2] & 1ull) return 1;     // a bucket with too many k-mers for the LDS table: table path
         if (h_cnt[0] <= out_cap) break;
-        if (attempt == 1) { if (d_exact) cf_release(ctx, d_exact, out_bytes); return cf_fail(ctx, -5, "cf_count_kmers: reduce output overflow"); }
+        if (attempt == 1) return cf_fail(ctx, -5, "cf_count_kmers: reduce output overflow");
         // (chunks are handed out dynamically: the next run may leave other holes) what was written + two chunks per workgroup
         out_cap = h_cnt[3] + 2ull * chunk * (unsigned long long)grid; out_bytes = (size_t)out_cap * sizeof(cf_slot);
-        CF_TRY(cf_alloc(ctx, (void**)&d_exact, out_bytes, "k-mer table (dense)"));
+        CF_TRY(tmp.get(&d_exact, (size_t)out_cap, "k-mer table (dense)"));
         d_out = d_exact;
     }
     (void)hipEventRecord(ctx->ev3, ctx->stream);
     // hand the dense table to the context
     if (n_w > 0) {
-        if (!d_exact) tmp.keep(dst);
+        tmp.keep(d_out);
         ctx->d_table = d_out;
         ctx->table_alloc = out_bytes / sizeof(cf_slot);
     } else {

@@ -1952,20 +1952,18 @@ int cf_edges_checksum(cf_ctx* ctx, int64_t n, uint64_t* out) {
     n = std::min(n, ctx->n_edges_stored);
     if (n <= 0) return 0;
     CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
     unsigned long long* d_sum = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_sum, 1, "edge checksum"));
-    int rc = 0;
+    CF_TRY(tmp.get(&d_sum, 1, "edge checksum"));
     unsigned long long h = 0;
-    if (hipMemsetAsync(d_sum, 0, 8, ctx->stream) != hipSuccess) rc = cf_fail(ctx, -5, "edge checksum memset");
-    if (!rc) {
-        hipLaunchKernelGGL(cf_edge_checksum_kernel, dim3((unsigned)cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 16)), dim3(256), 0, ctx->stream,
-                           (const uint32_t*)ctx->d_edges, n, d_sum);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, d_sum, 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) rc = cf_fail(ctx, -5, "edge checksum kernel");
-    }
-    cf_release_t(ctx, d_sum, 1);
-    if (!rc) *out = (uint64_t)h;
-    return rc;
+    CF_HIP(hipMemsetAsync(d_sum, 0, 8, ctx->stream));
+    hipLaunchKernelGGL(cf_edge_checksum_kernel, dim3((unsigned)cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 16)), dim3(256), 0, ctx->stream,
+                       (const uint32_t*)ctx->d_edges, n, d_sum);
+    CF_KERNEL_CHECK("cf_edge_checksum_kernel");
+    CF_HIP(hipMemcpyAsync(&h, d_sum, 8, hipMemcpyDeviceToHost, ctx->stream));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    *out = (uint64_t)h;
+    return 0;
 }
 
 int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int32_t max_d, uint32_t min_cov,
@@ -1998,13 +1996,12 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     uint32_t *d_pcnt = nullptr, *d_cursor = nullptr, *d_first = nullptr;
     unsigned long long *d_okeys = nullptr, *d_otmp = nullptr;
     int32_t* d_order = nullptr;
-    int64_t n_order = 0, n_a_alloc = 0, n_item_slots = 0;
+    int64_t n_order = 0, n_item_slots = 0;
     uint32_t *d_icnt = nullptr, *d_ialloc = nullptr;
     int64_t* d_ibase = nullptr;
     cf_dist_head* d_heads = nullptr;
     cf_dist_item* d_items = nullptr;
     unsigned long long* d_holes = nullptr;
-    size_t n_holes_alloc = 0;
     int64_t n_stored = 0;
     int64_t* d_post_ptr = nullptr;
     int32_t *d_post = nullptr, *d_rend = nullptr, *d_rbeg = nullptr;
@@ -2016,356 +2013,317 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     uint8_t* d_entry_i8 = nullptr;
     unsigned long long* d_cnt = nullptr;
     int64_t n_post = 0;
-    int rc = 0;
     unsigned long long h_cnt[8] = {0};
     const size_t n_cnt = 8 + 16 * 9;   // counters + 8 queue heads on their own cache lines
     const int max_blocks = std::max(1, ctx->n_cu) * 8;
-    do {
-        cf_free_edges(ctx);      // (the buffer of this call is allocated below, once the launch shape is known)
-        if ((rc = cf_alloc_t(ctx, &d_pcnt, (size_t)K + 1, "posting counts"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_cursor, (size_t)K + 1, "posting cursors"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_post_ptr, (size_t)K + 1, "posting offsets"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_rend, (size_t)U + 1, "unit read ends"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_rbeg, (size_t)U + 1, "unit read begins"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_urange, (size_t)U + 1, "unit partner ranges"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_cnt, n_cnt, "dist counters"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_first, (size_t)K + 1, "first posting units"))) break;
-        hipError_t e = hipMemsetAsync(d_pcnt, 0, (size_t)(K + 1) * 4, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_cursor, 0, (size_t)(K + 1) * 4, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_cnt, 0, n_cnt * 8, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_first, 0xFF, (size_t)(K + 1) * 4, ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, "cf_dist_edges memset"); break; }
-        int64_t e0 = 0, e1 = 0;
+    cf_free_edges(ctx);      // (the buffer of this call is allocated below, once the launch shape is known)
+    cf_scratch tmp(ctx);
+    CF_TRY(tmp.get(&d_pcnt, (size_t)K + 1, "posting counts"));
+    CF_TRY(tmp.get(&d_cursor, (size_t)K + 1, "posting cursors"));
+    CF_TRY(tmp.get(&d_post_ptr, (size_t)K + 1, "posting offsets"));
+    CF_TRY(tmp.get(&d_rend, (size_t)U + 1, "unit read ends"));
+    CF_TRY(tmp.get(&d_rbeg, (size_t)U + 1, "unit read begins"));
+    CF_TRY(tmp.get(&d_urange, (size_t)U + 1, "unit partner ranges"));
+    CF_TRY(tmp.get(&d_cnt, n_cnt, "dist counters"));
+    CF_TRY(tmp.get(&d_first, (size_t)K + 1, "first posting units"));
+    CF_HIP(hipMemsetAsync(d_pcnt, 0, (size_t)(K + 1) * 4, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_cursor, 0, (size_t)(K + 1) * 4, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_cnt, 0, n_cnt * 8, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_first, 0xFF, (size_t)(K + 1) * 4, ctx->stream));
+    int64_t e0 = 0, e1 = 0;
+    CF_HIP(hipMemcpy(&e0, v_cloud_ptr + u0, 8, hipMemcpyDeviceToHost));
+    CF_HIP(hipMemcpy(&e1, v_cloud_ptr + u1, 8, hipMemcpyDeviceToHost));
+    const bool by_sort = !ctx->dist_post_atomics && e1 > e0 && (e1 - e0) < ((int64_t)1 << 32) && U < ((int64_t)1 << 31);
+    if (by_sort) {
+        int64_t n = e1 - e0;
+        const int64_t K_part = (K + n_parts - 1) / n_parts;      // sort keys: the rank, or rank / n_parts for one partition
+        int kb = 1; while (kb < 32 && ((int64_t)1 << kb) < std::max<int64_t>(K_part, 2)) ++kb;
+        kb = (kb + 7) & ~7;      // whole 8-bit digits: the last radix pass must not reach into the unit bits
+        const unsigned g_units = (unsigned)cf_grid_for((u1 - u0) * 64, 256, max_blocks);
         {
-            int64_t tmp[2] = {0, 0};
-            if (hipMemcpy(&tmp[0], v_cloud_ptr + u0, 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(&tmp[1], v_cloud_ptr + u1, 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = cf_fail(ctx, -5, "cloud_ptr read"); break; }
-            e0 = tmp[0]; e1 = tmp[1];
-        }
-        const bool by_sort = !ctx->dist_post_atomics && e1 > e0 && (e1 - e0) < ((int64_t)1 << 32) && U < ((int64_t)1 << 31);
-        if (by_sort) {
-            int64_t n = e1 - e0;
-            const int64_t K_part = (K + n_parts - 1) / n_parts;      // sort keys: the rank, or rank / n_parts for one partition
-            int kb = 1; while (kb < 32 && ((int64_t)1 << kb) < std::max<int64_t>(K_part, 2)) ++kb;
-            kb = (kb + 7) & ~7;      // whole 8-bit digits: the last radix pass must not reach into the unit bits
+            cf_scratch recs(ctx);      // the records are gone again before the tables of the sweeps are taken
             unsigned long long *d_recs = nullptr, *d_rtmp = nullptr, *d_sorted = nullptr;
             uint32_t* d_ucnt = nullptr; int64_t* d_uoff = nullptr;
-            const unsigned g_units = (unsigned)cf_grid_for((u1 - u0) * 64, 256, max_blocks);
             if (n_parts > 1) {       // what this partition keeps of every unit's cloud, and where its records go
-                if ((rc = cf_alloc_t(ctx, &d_ucnt, (size_t)(u1 - u0) + 1, "kept entries per unit"))) break;
-                if ((rc = cf_alloc_t(ctx, &d_uoff, (size_t)(u1 - u0) + 1, "record offsets per unit"))) { cf_release_t(ctx, d_ucnt, (size_t)(u1 - u0) + 1); break; }
-                if (hipMemsetAsync(d_ucnt + (u1 - u0), 0, 4, ctx->stream) != hipSuccess) rc = cf_fail(ctx, -5, "cf_dist_edges memset");
+                CF_TRY(recs.get(&d_ucnt, (size_t)(u1 - u0) + 1, "kept entries per unit"));
+                CF_TRY(recs.get(&d_uoff, (size_t)(u1 - u0) + 1, "record offsets per unit"));
+                CF_HIP(hipMemsetAsync(d_ucnt + (u1 - u0), 0, 4, ctx->stream));
                 hipLaunchKernelGGL(cf_post_ucount_kernel, dim3(g_units), dim3(256), 0, ctx->stream, v_cloud_ptr, v_entries, u0, u1, (uint32_t)part, (uint32_t)n_parts, d_ucnt);
-                if (!rc) rc = cf_scan_exclusive_u32_to_i64(ctx, d_ucnt, d_uoff, (u1 - u0) + 1, &n);
+                CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_ucnt, d_uoff, (u1 - u0) + 1, &n));
             }
-            if (!rc && (rc = cf_alloc_t(ctx, &d_recs, (size_t)n + 1, "posting records")) == 0 &&
-                (rc = cf_alloc_t(ctx, &d_rtmp, (size_t)n + 1, "posting records (sort)")) != 0) { cf_release_t(ctx, d_recs, (size_t)n + 1); d_recs = nullptr; }
-            if (!rc) {
-                if (n_parts > 1)
-                    hipLaunchKernelGGL(cf_post_recs_part_kernel, dim3(g_units), dim3(256), 0, ctx->stream,
-                                       v_cloud_ptr, v_entries, u0, u1, (uint32_t)part, (uint32_t)n_parts, (const int64_t*)d_uoff, kb, d_recs);
-                else
-                    hipLaunchKernelGGL(cf_post_recs_kernel, dim3(g_units), dim3(256), 0, ctx->stream, v_cloud_ptr, v_entries, u0, u1, e0, kb, d_recs);
-                if (n) rc = cf_radix_sort_u64_any(ctx, d_recs, d_rtmp, n, kb, &d_sorted);
-                if (!rc) rc = cf_alloc_t(ctx, &d_post, (size_t)n, "postings");
-                if (!rc) {
-                    n_post = n;
-                    if (n) hipLaunchKernelGGL(cf_post_bounds_kernel, dim3((unsigned)cf_grid_for(n, 256, max_blocks)), dim3(256), 0, ctx->stream,
-                                       (const unsigned long long*)d_sorted, n, kb, (uint32_t)part, (uint32_t)n_parts, d_post, d_cursor, d_pcnt, d_first);      // (d_cursor = run starts, d_pcnt = run ends)
-                    hipLaunchKernelGGL(cf_post_counts_kernel, dim3((unsigned)cf_grid_for(K, 256, max_blocks)), dim3(256), 0, ctx->stream, (const uint32_t*)d_cursor, d_pcnt, K);
-                    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) rc = cf_fail(ctx, -5, "postings by sort");
-                }
-                cf_release_t(ctx, d_rtmp, (size_t)n + 1);
-                cf_release_t(ctx, d_recs, (size_t)n + 1);
-            }
-            if (d_uoff) cf_release_t(ctx, d_uoff, (size_t)(u1 - u0) + 1);
-            if (d_ucnt) cf_release_t(ctx, d_ucnt, (size_t)(u1 - u0) + 1);
-            if (rc) break;
-            int64_t n_chk = 0;
-            if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_pcnt, d_post_ptr, K + 1, &n_chk))) break;
-            if (n_chk != n_post) { rc = cf_fail(ctx, -5, "cf_dist_edges: internal error, posting counts do not add up"); break; }
-        } else {
+            CF_TRY(recs.get(&d_recs, (size_t)n + 1, "posting records"));
+            CF_TRY(recs.get(&d_rtmp, (size_t)n + 1, "posting records (sort)"));
+            if (n_parts > 1)
+                hipLaunchKernelGGL(cf_post_recs_part_kernel, dim3(g_units), dim3(256), 0, ctx->stream,
+                                   v_cloud_ptr, v_entries, u0, u1, (uint32_t)part, (uint32_t)n_parts, (const int64_t*)d_uoff, kb, d_recs);
+            else
+                hipLaunchKernelGGL(cf_post_recs_kernel, dim3(g_units), dim3(256), 0, ctx->stream, v_cloud_ptr, v_entries, u0, u1, e0, kb, d_recs);
+            if (n) CF_TRY(cf_radix_sort_u64_any(ctx, d_recs, d_rtmp, n, kb, &d_sorted));
+            CF_TRY(tmp.get(&d_post, (size_t)n, "postings"));
+            n_post = n;
+            if (n) hipLaunchKernelGGL(cf_post_bounds_kernel, dim3((unsigned)cf_grid_for(n, 256, max_blocks)), dim3(256), 0, ctx->stream,
+                               (const unsigned long long*)d_sorted, n, kb, (uint32_t)part, (uint32_t)n_parts, d_post, d_cursor, d_pcnt, d_first);      // (d_cursor = run starts, d_pcnt = run ends)
+            hipLaunchKernelGGL(cf_post_counts_kernel, dim3((unsigned)cf_grid_for(K, 256, max_blocks)), dim3(256), 0, ctx->stream, (const uint32_t*)d_cursor, d_pcnt, K);
+            CF_KERNEL_CHECK("the postings-by-sort kernels");
+            CF_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        int64_t n_chk = 0;
+        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_pcnt, d_post_ptr, K + 1, &n_chk));
+        if (n_chk != n_post) return cf_fail(ctx, -5, "cf_dist_edges: internal error, posting counts do not add up");
+    } else {
         if (e1 > e0)
             hipLaunchKernelGGL(cf_post_hist_kernel, dim3((unsigned)cf_grid_for(e1 - e0, 256, max_blocks)), dim3(256), 0, ctx->stream,
                                v_entries, e0, e1, (uint32_t)part, (uint32_t)n_parts, d_pcnt);
-        if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_pcnt, d_post_ptr, K + 1, &n_post))) break;
-        if ((rc = cf_alloc_t(ctx, &d_post, (size_t)n_post, "postings"))) break;
+        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_pcnt, d_post_ptr, K + 1, &n_post));
+        CF_TRY(tmp.get(&d_post, (size_t)n_post, "postings"));
         if (u1 > u0 && n_post)
             hipLaunchKernelGGL(cf_post_fill_kernel, dim3((unsigned)cf_grid_for((u1 - u0) * 64, 256, max_blocks)), dim3(256), 0, ctx->stream,
                                v_cloud_ptr, v_entries, u0, u1, (uint32_t)part, (uint32_t)n_parts, (const int64_t*)d_post_ptr, d_cursor, d_post, d_first);
-        }
-        if (R)
-            hipLaunchKernelGGL(cf_unit_rend_kernel, dim3((unsigned)cf_grid_for(R, 256, max_blocks)), dim3(256), 0, ctx->stream,
-                               v_unit_ptr, v_cloud_ptr, R, min_d_eff, max_d, d_rend, d_rbeg, d_urange);
-        // table layout: 6-byte slots (32-bit keys, 16-bit counts) whenever ranks fit 24 bits and counts 15 bits
-        uint32_t max_post = 0;
-        if (K) {
-            hipLaunchKernelGGL(cf_max_u32_kernel, dim3((unsigned)cf_grid_for(K, 256, max_blocks)), dim3(256), 0, ctx->stream,
-                               (const uint32_t*)d_pcnt, K, (uint32_t*)(d_cnt + 7));
-            if (hipMemcpy(&max_post, d_cnt + 7, 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = cf_fail(ctx, -5, "max postings"); break; }
-        }
-        // 6-byte slots [d : DB | b : 32 - DB] need the k-mer ranks in 32 - DB bits and every distance that can occur in DB
-        // bits: d <= min(max_d, units of the longest read - 1)
-        int64_t u_max = 0;
-        for (int64_t r = min_n; r < max_n; ++r) u_max = std::max(u_max, v_h_unit_ptr[(size_t)r + 1] - v_h_unit_ptr[(size_t)r]);
-        const int64_t d_need = std::max<int64_t>(1, std::min<int64_t>(max_d, u_max - 1));
-        int need_bits = 1; while (((int64_t)1 << need_bits) <= d_need) ++need_bits;
-        wide16 = d_need > 255;         // 16-bit distance field: [b:32 | d:16 | sel:1 | cnt:15]
-        int kb = 24; while (kb < 32 && K >= ((int64_t)1 << kb) - 1) ++kb;       // ranks 0 .. K - 1 and the all-ones key stays free
-        narrow_db = 32 - kb;                                                       // the widest distance field the ranks leave
-        if (ctx->dist_dbits) narrow_db = std::min(narrow_db, ctx->dist_dbits);
-        // (the 4-byte stream is read with buffer loads whose scalar byte offset has 32 bits: 2^30 entries and more take the other layouts)
-        const bool stream4_ok = v_n_entries + (int64_t)DIST_ITEM < ((int64_t)1 << 30);
-        narrow = !wide16 && !ctx->dist_wide && narrow_db >= 5 && narrow_db >= need_bits && max_post <= 32767u && stream4_ok;
-        if (ctx->dist_dbits && !narrow) { rc = cf_fail(ctx, -22, "cf_dist_edges: dist_dbits does not fit this input (distances or k-mer ranks need more bits)"); break; }
-        // ranks that do not fit next to the distance: the 6-byte slots in 2^S table regions (the key drops the rank's low S bits)
-        if (!narrow || ctx->dist_regions) {
-            reg_shift = 0;
-            while (reg_shift < 3 && ((K - 1) >> reg_shift) > ((int64_t)1 << 24) - 2) ++reg_shift;
-            if (ctx->dist_regions) { int want = 0; while ((1 << want) < ctx->dist_regions) ++want; reg_shift = std::max(reg_shift, want); }
-            region = !wide16 && !ctx->dist_wide && !ctx->dist_dbits && reg_shift <= 3 && ((K - 1) >> reg_shift) <= ((int64_t)1 << 24) - 2 && max_post <= 32767u && K < ((int64_t)1 << 31);
-            if (ctx->dist_regions && !region) { rc = cf_fail(ctx, -22, "cf_dist_edges: dist_regions does not fit this input"); break; }
-            if (region) narrow = false;
-            // up to 2^26 ranks and distances up to 127: the region table behind the 4-byte stream [unit index mod 64 : 6 | rank : 26]
-            region26 = region && !ctx->dist_region_bytes && K <= ((int64_t)1 << 26) && d_need <= 127 && stream4_ok;
-        }
-        if (max_post >= (1u << 23) || (wide16 && max_post > 32767u)) { rc = cf_fail(ctx, -34, wide16 ? "cf_dist_edges: distances above 255 with a k-mer of more than 32767 postings" : "cf_dist_edges: a k-mer has more than 2^23 postings"); break; }
-        if (narrow || region26) { if ((rc = cf_alloc_t(ctx, &d_packed, (size_t)v_n_entries + DIST_ITEM, "packed cloud entries"))) break; }
-        else if (region) { if ((rc = cf_alloc_t(ctx, &d_entry_i8, (size_t)v_n_entries + 4 * DIST_ITEM, "entry unit indices (bytes)"))) break; }
-        else if ((rc = cf_alloc_t(ctx, &d_entry_i, (size_t)v_n_entries + 1, "entry unit indices"))) break;
-        if (U && v_n_entries)
-            hipLaunchKernelGGL(cf_entry_unit_kernel, dim3((unsigned)cf_grid_for(U * 64, 256, max_blocks)), dim3(256), 0, ctx->stream,
-                               v_cloud_ptr, (const int32_t*)d_rbeg, v_entries, U, d_entry_i, d_packed, region26 ? 26 : 32 - narrow_db, d_entry_i8);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev2, ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("postings: ") + hipGetErrorString(e)); break; }
+    }
+    if (R)
+        hipLaunchKernelGGL(cf_unit_rend_kernel, dim3((unsigned)cf_grid_for(R, 256, max_blocks)), dim3(256), 0, ctx->stream,
+                           v_unit_ptr, v_cloud_ptr, R, min_d_eff, max_d, d_rend, d_rbeg, d_urange);
+    // table layout: 6-byte slots (32-bit keys, 16-bit counts) whenever ranks fit 24 bits and counts 15 bits
+    uint32_t max_post = 0;
+    if (K) {
+        hipLaunchKernelGGL(cf_max_u32_kernel, dim3((unsigned)cf_grid_for(K, 256, max_blocks)), dim3(256), 0, ctx->stream,
+                           (const uint32_t*)d_pcnt, K, (uint32_t*)(d_cnt + 7));
+        CF_HIP(hipMemcpy(&max_post, d_cnt + 7, 4, hipMemcpyDeviceToHost));
+    }
+    // 6-byte slots [d : DB | b : 32 - DB] need the k-mer ranks in 32 - DB bits and every distance that can occur in DB
+    // bits: d <= min(max_d, units of the longest read - 1)
+    int64_t u_max = 0;
+    for (int64_t r = min_n; r < max_n; ++r) u_max = std::max(u_max, v_h_unit_ptr[(size_t)r + 1] - v_h_unit_ptr[(size_t)r]);
+    const int64_t d_need = std::max<int64_t>(1, std::min<int64_t>(max_d, u_max - 1));
+    int need_bits = 1; while (((int64_t)1 << need_bits) <= d_need) ++need_bits;
+    wide16 = d_need > 255;         // 16-bit distance field: [b:32 | d:16 | sel:1 | cnt:15]
+    int kb = 24; while (kb < 32 && K >= ((int64_t)1 << kb) - 1) ++kb;       // ranks 0 .. K - 1 and the all-ones key stays free
+    narrow_db = 32 - kb;                                                       // the widest distance field the ranks leave
+    if (ctx->dist_dbits) narrow_db = std::min(narrow_db, ctx->dist_dbits);
+    // (the 4-byte stream is read with buffer loads whose scalar byte offset has 32 bits: 2^30 entries and more take the other layouts)
+    const bool stream4_ok = v_n_entries + (int64_t)DIST_ITEM < ((int64_t)1 << 30);
+    narrow = !wide16 && !ctx->dist_wide && narrow_db >= 5 && narrow_db >= need_bits && max_post <= 32767u && stream4_ok;
+    if (ctx->dist_dbits && !narrow) return cf_fail(ctx, -22, "cf_dist_edges: dist_dbits does not fit this input (distances or k-mer ranks need more bits)");
+    // ranks that do not fit next to the distance: the 6-byte slots in 2^S table regions (the key drops the rank's low S bits)
+    if (!narrow || ctx->dist_regions) {
+        reg_shift = 0;
+        while (reg_shift < 3 && ((K - 1) >> reg_shift) > ((int64_t)1 << 24) - 2) ++reg_shift;
+        if (ctx->dist_regions) { int want = 0; while ((1 << want) < ctx->dist_regions) ++want; reg_shift = std::max(reg_shift, want); }
+        region = !wide16 && !ctx->dist_wide && !ctx->dist_dbits && reg_shift <= 3 && ((K - 1) >> reg_shift) <= ((int64_t)1 << 24) - 2 && max_post <= 32767u && K < ((int64_t)1 << 31);
+        if (ctx->dist_regions && !region) return cf_fail(ctx, -22, "cf_dist_edges: dist_regions does not fit this input");
+        if (region) narrow = false;
+        // up to 2^26 ranks and distances up to 127: the region table behind the 4-byte stream [unit index mod 64 : 6 | rank : 26]
+        region26 = region && !ctx->dist_region_bytes && K <= ((int64_t)1 << 26) && d_need <= 127 && stream4_ok;
+    }
+    if (max_post >= (1u << 23) || (wide16 && max_post > 32767u)) return cf_fail(ctx, -34, wide16 ? "cf_dist_edges: distances above 255 with a k-mer of more than 32767 postings" : "cf_dist_edges: a k-mer has more than 2^23 postings");
+    if (narrow || region26) { CF_TRY(tmp.get(&d_packed, (size_t)v_n_entries + DIST_ITEM, "packed cloud entries")); }
+    else if (region) { CF_TRY(tmp.get(&d_entry_i8, (size_t)v_n_entries + 4 * DIST_ITEM, "entry unit indices (bytes)")); }
+    else CF_TRY(tmp.get(&d_entry_i, (size_t)v_n_entries + 1, "entry unit indices"));
+    if (U && v_n_entries)
+        hipLaunchKernelGGL(cf_entry_unit_kernel, dim3((unsigned)cf_grid_for(U * 64, 256, max_blocks)), dim3(256), 0, ctx->stream,
+                           v_cloud_ptr, (const int32_t*)d_rbeg, v_entries, U, d_entry_i, d_packed, region26 ? 26 : 32 - narrow_db, d_entry_i8);
+    CF_KERNEL_CHECK("the postings kernels");
+    CF_HIP(hipEventRecord(ctx->ev2, ctx->stream));
 
-        cf_dist_args A;
-        A.post_ptr = d_post_ptr; A.post = d_post; A.cloud_ptr = v_cloud_ptr; A.entries = v_entries; A.unit_rend = d_rend; A.unit_rbeg = d_rbeg; A.urange = d_urange; A.entry_i = d_entry_i; A.packed = d_packed; A.entry_i8 = d_entry_i8; A.reg_shift = (uint32_t)reg_shift;
-        A.n_kmers = K; A.part = part; A.n_parts = n_parts; A.min_d = min_d_eff; A.max_d = max_d; A.min_cov = min_cov; A.thr = rel_threshold;
-        A.thr_num = (rel_threshold == 0.8 && ctx->dist_int_thr) ? 4u : 0u; A.thr_den = A.thr_num ? 5u : 0u;
-        A.stage_cap = (uint32_t)std::min(ctx->dist_stage, DIST_STAGE_CAP);
-        A.hot_cap = ctx->dist_hot_cap > 0 ? (uint32_t)ctx->dist_hot_cap : 0xFFFFFFFFu;
-        A.hot_entries = ctx->dist_hot_entries >= 0 ? (uint32_t)ctx->dist_hot_entries : 0xFFFFFFFFu;
-        const uint32_t slot_bytes = (narrow || region) ? cf_tab_narrow::kSlotBytes : cf_tab_wide::kSlotBytes;
-        // launch shape: two 512-thread workgroups per CU (80 KiB of LDS each) overlap each other's latency-bound phases
-        // and win when a first k-mer has few pair emissions; with many (long reads, high coverage) the halved table and
-        // sketch cost more than the overlap gains, and one 1024-thread workgroup with the whole LDS wins (measured:
-        // 20 k emissions per first k-mer: 480 vs 716 ms; 53 k: 437 vs 274 ms; 160 k: 2097 vs 739 ms)
-        // pair emissions per first k-mer, ESTIMATED on the host (round 6; rounds 2-5 summed the partner ranges of every posting on the device —
-        // a kernel of random gathers, 1.05 ms of every launch, and a blocking copy — for a figure that only picks the launch shape): the
-        // partner units of every unit of the reads in range, exactly, times the mean cloud size, times the mean postings per unit
-        double per_first = 0.0;
-        if (n_post && u1 > u0) {
-            unsigned long long partner_units = 0;
-            for (int64_t r = min_n; r < max_n; ++r) {
-                const int64_t nu = v_h_unit_ptr[(size_t)r + 1] - v_h_unit_ptr[(size_t)r];
-                // unit i of a read of nu units has max(0, min(nu - 1, i + max_d) - (i + min_d) + 1) partner units
-                const int64_t span = (int64_t)max_d - min_d_eff + 1;
-                if (nu <= min_d_eff || span <= 0) continue;
-                const int64_t full = std::max<int64_t>(0, nu - max_d);           // units with the whole span behind them
-                const int64_t tail = nu - min_d_eff - full;                      // the rest: nu - min_d - i partner units each, down to 1
-                partner_units += (unsigned long long)(full * span) + (unsigned long long)(tail > 0 ? tail * (tail + 1) / 2 : 0);
-            }
-            const double cloud = (double)(e1 - e0) / (double)(u1 - u0), post_per_unit = (double)n_post / (double)(u1 - u0);
-            per_first = (double)partner_units * cloud * post_per_unit / (double)std::max<int64_t>(1, (K - part + n_parts - 1) / n_parts);
+    cf_dist_args A;
+    A.post_ptr = d_post_ptr; A.post = d_post; A.cloud_ptr = v_cloud_ptr; A.entries = v_entries; A.unit_rend = d_rend; A.unit_rbeg = d_rbeg; A.urange = d_urange; A.entry_i = d_entry_i; A.packed = d_packed; A.entry_i8 = d_entry_i8; A.reg_shift = (uint32_t)reg_shift;
+    A.n_kmers = K; A.part = part; A.n_parts = n_parts; A.min_d = min_d_eff; A.max_d = max_d; A.min_cov = min_cov; A.thr = rel_threshold;
+    A.thr_num = (rel_threshold == 0.8 && ctx->dist_int_thr) ? 4u : 0u; A.thr_den = A.thr_num ? 5u : 0u;
+    A.stage_cap = (uint32_t)std::min(ctx->dist_stage, DIST_STAGE_CAP);
+    A.hot_cap = ctx->dist_hot_cap > 0 ? (uint32_t)ctx->dist_hot_cap : 0xFFFFFFFFu;
+    A.hot_entries = ctx->dist_hot_entries >= 0 ? (uint32_t)ctx->dist_hot_entries : 0xFFFFFFFFu;
+    const uint32_t slot_bytes = (narrow || region) ? cf_tab_narrow::kSlotBytes : cf_tab_wide::kSlotBytes;
+    // launch shape: two 512-thread workgroups per CU (80 KiB of LDS each) overlap each other's latency-bound phases
+    // and win when a first k-mer has few pair emissions; with many (long reads, high coverage) the halved table and
+    // sketch cost more than the overlap gains, and one 1024-thread workgroup with the whole LDS wins (measured:
+    // 20 k emissions per first k-mer: 480 vs 716 ms; 53 k: 437 vs 274 ms; 160 k: 2097 vs 739 ms)
+    // pair emissions per first k-mer, ESTIMATED on the host (round 6; rounds 2-5 summed the partner ranges of every posting on the device —
+    // a kernel of random gathers, 1.05 ms of every launch, and a blocking copy — for a figure that only picks the launch shape): the
+    // partner units of every unit of the reads in range, exactly, times the mean cloud size, times the mean postings per unit
+    double per_first = 0.0;
+    if (n_post && u1 > u0) {
+        unsigned long long partner_units = 0;
+        for (int64_t r = min_n; r < max_n; ++r) {
+            const int64_t nu = v_h_unit_ptr[(size_t)r + 1] - v_h_unit_ptr[(size_t)r];
+            // unit i of a read of nu units has max(0, min(nu - 1, i + max_d) - (i + min_d) + 1) partner units
+            const int64_t span = (int64_t)max_d - min_d_eff + 1;
+            if (nu <= min_d_eff || span <= 0) continue;
+            const int64_t full = std::max<int64_t>(0, nu - max_d);           // units with the whole span behind them
+            const int64_t tail = nu - min_d_eff - full;                      // the rest: nu - min_d - i partner units each, down to 1
+            partner_units += (unsigned long long)(full * span) + (unsigned long long)(tail > 0 ? tail * (tail + 1) / 2 : 0);
         }
-        int wgs = ctx->dist_wgs, block = ctx->dist_block;
-        if (wgs == 0) wgs = (block > 512 || per_first > 32768.0) ? 1 : 2;
-        if (block == 0) block = wgs == 1 ? 1024 : 512;
-        // LDS: everything but the table is fixed; dist_slots (the table budget in 8-byte units) defaults to all the rest
-        const size_t qitem_bytes = narrow ? sizeof(cf_tab_narrow::qitem) : sizeof(cf_tab_wide::qitem);      // (the region layouts queue 64-bit items, like the wide one)
-        const size_t lds_fixed = DIST_LDS_HEAD + (size_t)(2 * DIST_STACK) * 4 + DIST_STAGE_CAP * 2 + 16 + (size_t)(block / 64) * (DIST_QSTRIDE + DIST_OVQ) * qitem_bytes + DIST_HOT_CAP * 2;
-        const int64_t budget8 = ((int64_t)160 * 1024 / wgs - (int64_t)lds_fixed) / 8;
-        if (budget8 < 256) { rc = cf_fail(ctx, -22, "cf_dist_edges: dist_wgs leaves no LDS for the table"); break; }
-        if (ctx->dist_slots > budget8) { rc = cf_fail(ctx, -22, "cf_dist_edges: dist_slots does not fit the 160 KiB LDS next to the work lists"); break; }
-        const int64_t slots8 = ctx->dist_slots ? ctx->dist_slots : budget8;
-        A.slots = (int32_t)((slots8 * 8 / slot_bytes) & ~(region ? (int64_t)(32 << reg_shift) - 1 : 7ll));      // (regions: equal parts of whole 8-slot groups)
-        if (A.slots >= 0xFFFF) { rc = cf_fail(ctx, -22, "cf_dist_edges: more than 65534 table slots (16-bit slot indices; 0xFFFF marks an unused entry of the hot list)"); break; }
-        A.fill_limit = (uint32_t)((int64_t)A.slots * ctx->dist_fill_pct / 100);   // checked once per wave step: leave slack below the physical size
-        {   //  the fill level a drain looks at lags by one drain: every wave may put 2 x 128 fresh keys behind the limit before it
-            // stops — the limit leaves that room below the physical size where the table is large enough for it (tables that tests force down
-            // to a few hundred slots keep their limit: a pass that fills up there is void and split, as it always was, and all the pairs of ONE
-            // b must fit one partition)
-            const int64_t slack = (int64_t)(block / 64) * 2 * 128;
-            if (slack * 4 <= (int64_t)A.slots) A.fill_limit = (uint32_t)std::min<int64_t>(A.fill_limit, (int64_t)A.slots - slack);
-        }
-        A.est_limit = (uint32_t)((int64_t)A.fill_limit * 100 / ctx->dist_est_pct);
-        A.counters = d_cnt; A.unique_bits = ctx->d_unique_bits;
-        const size_t lds = (size_t)A.slots * slot_bytes + lds_fixed;
-        A.sketch = (ctx->dist_sketch && min_cov >= 2 && min_cov <= 200) ? 1 : 0;
-        A.sk_shift = 32; A.sk_counters = 1;
-        const size_t sk_room = (size_t)A.slots * slot_bytes + DIST_STAGE_CAP * 2 + 16 + (size_t)(block / 64) * (DIST_QSTRIDE + DIST_OVQ) * qitem_bytes + 2 * DIST_STACK * 4 + DIST_HOT_CAP * 2;   // table + stage + stack + queues + hot list: all dead while the sketch runs
-        while (A.sk_shift > 8 && (size_t)A.sk_counters * 2 <= sk_room) { A.sk_counters *= 2; --A.sk_shift; }
-        if (A.sk_counters < 16) A.sketch = 0;
-        A.sk_bytes = A.sk_counters;
-        // 4-bit counters when min_cov - 1 fits well below their guard ("dist_sketch_bits" 8 keeps the bytes)
-        const bool sk4 = A.sketch && min_cov <= 9 && ctx->dist_sketch_bits != 8 && A.sk_shift > 9;
-        if (sk4) { A.sk_counters *= 2; --A.sk_shift; A.sk_fbits = 4; A.sk_fsh = 2; A.sk_wshift = 3; A.sk_fmask = 15; A.sk_guard = 12; }
-        else { A.sk_fbits = 8; A.sk_fsh = 3; A.sk_wshift = 2; A.sk_fmask = 255; A.sk_guard = 0x7FFFFFFFu; }
-        A.sk_mask = A.sk_counters - 1u;
-        const int per_cu = std::max(1, std::min((int)((160 * 1024) / lds), 2048 / block));
-        // locality order of the first k-mers: sort (first posting unit, a); k-mers without postings drop out
-        n_a_alloc = (K > part) ? (K - part + n_parts - 1) / n_parts : 0;
-        if ((rc = cf_alloc_t(ctx, &d_okeys, (size_t)n_a_alloc, "order keys"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_otmp, (size_t)n_a_alloc, "order scratch"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_order, (size_t)n_a_alloc, "order"))) break;
-        int ab = 1, ub = 1;      // bits of a rank, bits of a unit number
-        while (ab < 32 && ((int64_t)1 << ab) < K) ++ab;
-        while (ub < 32 && ((int64_t)1 << ub) < std::max<int64_t>(U, 2)) ++ub;
-        if (K) {
-            hipLaunchKernelGGL(cf_order_keys_kernel, dim3((unsigned)cf_grid_for(K, 256, max_blocks)), dim3(256), 0, ctx->stream,
-                               (const uint32_t*)d_pcnt, (const uint32_t*)d_first, K, (int)part, (int)n_parts, ab, d_okeys, d_cnt + 6);
-            unsigned long long h_n = 0;
-            if (hipMemcpy(&h_n, d_cnt + 6, 8, hipMemcpyDeviceToHost) != hipSuccess) { rc = cf_fail(ctx, -5, "order count"); break; }
-            n_order = (int64_t)h_n;
-            if ((rc = cf_radix_sort_u64(ctx, d_okeys, d_otmp, n_order, ab + ub))) break;      // (round 6: the key's own bits — 6 radix passes at 50 000 reads; rounds 2-5 sorted all 64)
-            if (n_order)
-                hipLaunchKernelGGL(cf_order_extract_kernel, dim3((unsigned)cf_grid_for(n_order, 256, max_blocks)), dim3(256), 0, ctx->stream,
-                                   (const unsigned long long*)d_okeys, n_order, ab, d_order);
-        }
-        A.order = d_order; A.n_order = n_order;
-        // the work lists of the sweeps (heads + item records, laid out for workgroups of `block` threads): count, scan, fill
-        if (n_order) {
-            const uint32_t nw = (uint32_t)block / 64u;
-            const int g_items = cf_grid_for(n_order * 16, 256, max_blocks);
-            if ((rc = cf_alloc_t(ctx, &d_icnt, (size_t)n_order + 1, "item counts"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_ialloc, (size_t)n_order + 1, "item slots"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_ibase, (size_t)n_order + 1, "item bases"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_heads, (size_t)n_order, "first k-mer heads"))) break;
-            hipLaunchKernelGGL(cf_items_count_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_order, (const int64_t*)d_post_ptr,
-                               (const int32_t*)d_post, (const cf_dist_rec*)d_urange, (const int32_t*)d_rbeg, min_d_eff, max_d, nw, by_sort ? 1 : 0, d_icnt, d_ialloc, d_cnt + 3);
-            if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_ialloc, d_ibase, n_order, &n_item_slots))) break;
-            if ((rc = cf_alloc_t(ctx, &d_items, (size_t)n_item_slots + 64, "item records"))) break;
-            hipLaunchKernelGGL(cf_items_fill_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_order, (const int64_t*)d_post_ptr,
-                               (const int32_t*)d_post, (const cf_dist_rec*)d_urange, nw, (const uint32_t*)d_icnt, (const int64_t*)d_ibase, d_heads, d_items,
-                               region26 ? v_cloud_ptr : (const int64_t*)nullptr, U);
-        }
-        A.heads = d_heads; A.items = d_items;
-        const int64_t n_a = n_order;
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_a, (int64_t)std::max(1, ctx->n_cu) * per_cu));
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev2, ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("order: ") + hipGetErrorString(e)); break; }
-        void (*kern)(cf_dist_args) = region26 ? cf_dist_kernel<cf_tab_region26> : region ? cf_dist_kernel<cf_tab_region> : !narrow ? (wide16 ? cf_dist_kernel<cf_tab_wide16> : cf_dist_kernel<cf_tab_wide>)
-                                   : narrow_db == 8 ? cf_dist_kernel<cf_tab_narrow_t<8>> : narrow_db == 7 ? cf_dist_kernel<cf_tab_narrow_t<7>>
-                                   : narrow_db == 6 ? cf_dist_kernel<cf_tab_narrow_t<6>> : cf_dist_kernel<cf_tab_narrow_t<5>>;
-        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("dist LDS attribute: ") + hipGetErrorString(e)); break; }
-        // the edge output: edge_cap rows + the unused rest of one chunk per workgroup (the holes; closed below), so that every
-        // selected edge is in memory whenever edge_cap >= their number
-        {
-            A.edge_chunk = ctx->dist_edge_chunk > 0 ? (unsigned long long)ctx->dist_edge_chunk : DIST_EDGE_CHUNK;
-            const int64_t rows = edge_cap > 0 ? edge_cap + (int64_t)grid * (int64_t)A.edge_chunk : 0;
-            if ((rc = cf_alloc_t(ctx, &ctx->d_edges, (size_t)rows * 4, "edges"))) break;
-            ctx->edge_cap = rows;
-            A.edges = ctx->d_edges; A.edge_cap = (unsigned long long)rows;
-        }
-        n_holes_alloc = (size_t)grid + 1;
-        if ((rc = cf_alloc_t(ctx, &d_holes, 2 * n_holes_alloc, "edge holes"))) break;
-        A.holes = d_holes;
-        if (hipMemsetAsync(d_cnt + 6, 0, 16, ctx->stream) != hipSuccess) { rc = cf_fail(ctx, -5, "counter reset"); break; }      // [6] selected edges, [7] holes
-        if (n_a > 0 && max_d >= min_d_eff && n_post > 0) {
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)block), lds, ctx->stream, A);
-            e = hipGetLastError();
-            if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_dist_kernel: ") + hipGetErrorString(e)); break; }
-        }
-        e = hipEventRecord(ctx->ev3, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, 64, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev1);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_dist_edges: ") + hipGetErrorString(e)); break; }
+        const double cloud = (double)(e1 - e0) / (double)(u1 - u0), post_per_unit = (double)n_post / (double)(u1 - u0);
+        per_first = (double)partner_units * cloud * post_per_unit / (double)std::max<int64_t>(1, (K - part + n_parts - 1) / n_parts);
+    }
+    int wgs = ctx->dist_wgs, block = ctx->dist_block;
+    if (wgs == 0) wgs = (block > 512 || per_first > 32768.0) ? 1 : 2;
+    if (block == 0) block = wgs == 1 ? 1024 : 512;
+    // LDS: everything but the table is fixed; dist_slots (the table budget in 8-byte units) defaults to all the rest
+    const size_t qitem_bytes = narrow ? sizeof(cf_tab_narrow::qitem) : sizeof(cf_tab_wide::qitem);      // (the region layouts queue 64-bit items, like the wide one)
+    const size_t lds_fixed = DIST_LDS_HEAD + (size_t)(2 * DIST_STACK) * 4 + DIST_STAGE_CAP * 2 + 16 + (size_t)(block / 64) * (DIST_QSTRIDE + DIST_OVQ) * qitem_bytes + DIST_HOT_CAP * 2;
+    const int64_t budget8 = ((int64_t)160 * 1024 / wgs - (int64_t)lds_fixed) / 8;
+    if (budget8 < 256) return cf_fail(ctx, -22, "cf_dist_edges: dist_wgs leaves no LDS for the table");
+    if (ctx->dist_slots > budget8) return cf_fail(ctx, -22, "cf_dist_edges: dist_slots does not fit the 160 KiB LDS next to the work lists");
+    const int64_t slots8 = ctx->dist_slots ? ctx->dist_slots : budget8;
+    A.slots = (int32_t)((slots8 * 8 / slot_bytes) & ~(region ? (int64_t)(32 << reg_shift) - 1 : 7ll));      // (regions: equal parts of whole 8-slot groups)
+    if (A.slots >= 0xFFFF) return cf_fail(ctx, -22, "cf_dist_edges: more than 65534 table slots (16-bit slot indices; 0xFFFF marks an unused entry of the hot list)");
+    A.fill_limit = (uint32_t)((int64_t)A.slots * ctx->dist_fill_pct / 100);   // checked once per wave step: leave slack below the physical size
+    {   //  the fill level a drain looks at lags by one drain: every wave may put 2 x 128 fresh keys behind the limit before it
+        // stops — the limit leaves that room below the physical size where the table is large enough for it (tables that tests force down
+        // to a few hundred slots keep their limit: a pass that fills up there is void and split, as it always was, and all the pairs of ONE
+        // b must fit one partition)
+        const int64_t slack = (int64_t)(block / 64) * 2 * 128;
+        if (slack * 4 <= (int64_t)A.slots) A.fill_limit = (uint32_t)std::min<int64_t>(A.fill_limit, (int64_t)A.slots - slack);
+    }
+    A.est_limit = (uint32_t)((int64_t)A.fill_limit * 100 / ctx->dist_est_pct);
+    A.counters = d_cnt; A.unique_bits = ctx->d_unique_bits;
+    const size_t lds = (size_t)A.slots * slot_bytes + lds_fixed;
+    A.sketch = (ctx->dist_sketch && min_cov >= 2 && min_cov <= 200) ? 1 : 0;
+    A.sk_shift = 32; A.sk_counters = 1;
+    const size_t sk_room = (size_t)A.slots * slot_bytes + DIST_STAGE_CAP * 2 + 16 + (size_t)(block / 64) * (DIST_QSTRIDE + DIST_OVQ) * qitem_bytes + 2 * DIST_STACK * 4 + DIST_HOT_CAP * 2;   // table + stage + stack + queues + hot list: all dead while the sketch runs
+    while (A.sk_shift > 8 && (size_t)A.sk_counters * 2 <= sk_room) { A.sk_counters *= 2; --A.sk_shift; }
+    if (A.sk_counters < 16) A.sketch = 0;
+    A.sk_bytes = A.sk_counters;
+    // 4-bit counters when min_cov - 1 fits well below their guard ("dist_sketch_bits" 8 keeps the bytes)
+    const bool sk4 = A.sketch && min_cov <= 9 && ctx->dist_sketch_bits != 8 && A.sk_shift > 9;
+    if (sk4) { A.sk_counters *= 2; --A.sk_shift; A.sk_fbits = 4; A.sk_fsh = 2; A.sk_wshift = 3; A.sk_fmask = 15; A.sk_guard = 12; }
+    else { A.sk_fbits = 8; A.sk_fsh = 3; A.sk_wshift = 2; A.sk_fmask = 255; A.sk_guard = 0x7FFFFFFFu; }
+    A.sk_mask = A.sk_counters - 1u;
+    const int per_cu = std::max(1, std::min((int)((160 * 1024) / lds), 2048 / block));
+    // locality order of the first k-mers: sort (first posting unit, a); k-mers without postings drop out
+    const int64_t n_a_alloc = (K > part) ? (K - part + n_parts - 1) / n_parts : 0;
+    CF_TRY(tmp.get(&d_okeys, (size_t)n_a_alloc, "order keys"));
+    CF_TRY(tmp.get(&d_otmp, (size_t)n_a_alloc, "order scratch"));
+    CF_TRY(tmp.get(&d_order, (size_t)n_a_alloc, "order"));
+    int ab = 1, ub = 1;      // bits of a rank, bits of a unit number
+    while (ab < 32 && ((int64_t)1 << ab) < K) ++ab;
+    while (ub < 32 && ((int64_t)1 << ub) < std::max<int64_t>(U, 2)) ++ub;
+    if (K) {
+        hipLaunchKernelGGL(cf_order_keys_kernel, dim3((unsigned)cf_grid_for(K, 256, max_blocks)), dim3(256), 0, ctx->stream,
+                           (const uint32_t*)d_pcnt, (const uint32_t*)d_first, K, (int)part, (int)n_parts, ab, d_okeys, d_cnt + 6);
+        unsigned long long h_n = 0;
+        CF_HIP(hipMemcpy(&h_n, d_cnt + 6, 8, hipMemcpyDeviceToHost));
+        n_order = (int64_t)h_n;
+        CF_TRY(cf_radix_sort_u64(ctx, d_okeys, d_otmp, n_order, ab + ub));      // (round 6: the key's own bits — 6 radix passes at 50 000 reads; rounds 2-5 sorted all 64)
+        if (n_order)
+            hipLaunchKernelGGL(cf_order_extract_kernel, dim3((unsigned)cf_grid_for(n_order, 256, max_blocks)), dim3(256), 0, ctx->stream,
+                               (const unsigned long long*)d_okeys, n_order, ab, d_order);
+    }
+    A.order = d_order; A.n_order = n_order;
+    // the work lists of the sweeps (heads + item records, laid out for workgroups of `block` threads): count, scan, fill
+    if (n_order) {
+        const uint32_t nw = (uint32_t)block / 64u;
+        const int g_items = cf_grid_for(n_order * 16, 256, max_blocks);
+        CF_TRY(tmp.get(&d_icnt, (size_t)n_order + 1, "item counts"));
+        CF_TRY(tmp.get(&d_ialloc, (size_t)n_order + 1, "item slots"));
+        CF_TRY(tmp.get(&d_ibase, (size_t)n_order + 1, "item bases"));
+        CF_TRY(tmp.get(&d_heads, (size_t)n_order, "first k-mer heads"));
+        hipLaunchKernelGGL(cf_items_count_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_order, (const int64_t*)d_post_ptr,
+                           (const int32_t*)d_post, (const cf_dist_rec*)d_urange, (const int32_t*)d_rbeg, min_d_eff, max_d, nw, by_sort ? 1 : 0, d_icnt, d_ialloc, d_cnt + 3);
+        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_ialloc, d_ibase, n_order, &n_item_slots));
+        CF_TRY(tmp.get(&d_items, (size_t)n_item_slots + 64, "item records"));
+        hipLaunchKernelGGL(cf_items_fill_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_order, (const int64_t*)d_post_ptr,
+                           (const int32_t*)d_post, (const cf_dist_rec*)d_urange, nw, (const uint32_t*)d_icnt, (const int64_t*)d_ibase, d_heads, d_items,
+                           region26 ? v_cloud_ptr : (const int64_t*)nullptr, U);
+    }
+    A.heads = d_heads; A.items = d_items;
+    const int64_t n_a = n_order;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_a, (int64_t)std::max(1, ctx->n_cu) * per_cu));
+    CF_KERNEL_CHECK("the work-list kernels");
+    CF_HIP(hipEventRecord(ctx->ev2, ctx->stream));
+    void (*kern)(cf_dist_args) = region26 ? cf_dist_kernel<cf_tab_region26> : region ? cf_dist_kernel<cf_tab_region> : !narrow ? (wide16 ? cf_dist_kernel<cf_tab_wide16> : cf_dist_kernel<cf_tab_wide>)
+                               : narrow_db == 8 ? cf_dist_kernel<cf_tab_narrow_t<8>> : narrow_db == 7 ? cf_dist_kernel<cf_tab_narrow_t<7>>
+                               : narrow_db == 6 ? cf_dist_kernel<cf_tab_narrow_t<6>> : cf_dist_kernel<cf_tab_narrow_t<5>>;
+    CF_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    // the edge output: edge_cap rows + the unused rest of one chunk per workgroup (the holes; closed below), so that every
+    // selected edge is in memory whenever edge_cap >= their number
+    {
+        A.edge_chunk = ctx->dist_edge_chunk > 0 ? (unsigned long long)ctx->dist_edge_chunk : DIST_EDGE_CHUNK;
+        const int64_t rows = edge_cap > 0 ? edge_cap + (int64_t)grid * (int64_t)A.edge_chunk : 0;
+        CF_TRY(cf_alloc_t(ctx, &ctx->d_edges, (size_t)rows * 4, "edges"));
+        ctx->edge_cap = rows;
+        A.edges = ctx->d_edges; A.edge_cap = (unsigned long long)rows;
+    }
+    CF_TRY(tmp.get(&d_holes, 2 * ((size_t)grid + 1), "edge holes"));
+    A.holes = d_holes;
+    CF_HIP(hipMemsetAsync(d_cnt + 6, 0, 16, ctx->stream));      // [6] selected edges, [7] holes
+    if (n_a > 0 && max_d >= min_d_eff && n_post > 0) {
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3((unsigned)block), lds, ctx->stream, A);
+        CF_KERNEL_CHECK("cf_dist_kernel");
+    }
+    CF_HIP(hipEventRecord(ctx->ev3, ctx->stream));
+    CF_HIP(hipMemcpyAsync(h_cnt, d_cnt, 64, hipMemcpyDeviceToHost, ctx->stream));
+    CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    CF_HIP(hipEventSynchronize(ctx->ev1));
 #if defined(CF_DIST_DIAG_COUNT)
-        {
-            unsigned long long st[8];
-            if (hipMemcpy(st, d_cnt + 8, 64, hipMemcpyDeviceToHost) == hipSuccess)
-                std::fprintf(stderr, "[cf_dist diag] parked-insert loop trips=%llu overflow calls=%llu parked inserts run=%llu drains=%llu inserts drained=%llu cycles(sum over waves): parked runs=%llu drains=%llu table sweeps=%llu; waves=%d passes=%llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], grid * (block / 64), h_cnt[5]);
-        }
+    {
+        unsigned long long st[8];
+        if (hipMemcpy(st, d_cnt + 8, 64, hipMemcpyDeviceToHost) == hipSuccess)
+            std::fprintf(stderr, "[cf_dist diag] parked-insert loop trips=%llu overflow calls=%llu parked inserts run=%llu drains=%llu inserts drained=%llu cycles(sum over waves): parked runs=%llu drains=%llu table sweeps=%llu; waves=%d passes=%llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], grid * (block / 64), h_cnt[5]);
+    }
 #endif
 #if defined(CF_DIST_STAMPS)
-        {
-            unsigned long long st[8];
-            if (hipMemcpy(st, d_cnt + 8, 64, hipMemcpyDeviceToHost) == hipSuccess)
-                std::fprintf(stderr, "[cf_dist stamps] pop=%llu prologue=%llu sketch=%llu clear=%llu stream=%llu filter=%llu write=%llu sweep_end_wait=%llu (shader cycles summed over %d workgroups; passes=%llu)\n",
-                             st[0], st[1], st[6], st[2], st[3], st[4], st[5], st[7], grid, h_cnt[5]);
-        }
+    {
+        unsigned long long st[8];
+        if (hipMemcpy(st, d_cnt + 8, 64, hipMemcpyDeviceToHost) == hipSuccess)
+            std::fprintf(stderr, "[cf_dist stamps] pop=%llu prologue=%llu sketch=%llu clear=%llu stream=%llu filter=%llu write=%llu sweep_end_wait=%llu (shader cycles summed over %d workgroups; passes=%llu)\n",
+                         st[0], st[1], st[6], st[2], st[3], st[4], st[5], st[7], grid, h_cnt[5]);
+    }
 #endif
-        if (h_cnt[4] & 2ull) { rc = cf_fail(ctx, -5, "cf_dist_edges: the kernel's dynamic LDS does not begin at address 0"); break; }
-        if (h_cnt[4]) { rc = cf_fail(ctx, -34, "cf_dist_edges: (b,d) table could not be partitioned far enough"); break; }
-        // close the holes of the chunked edge output: the valid rows at or above n_valid move into the holes below it
-        {
-            const unsigned long long a_cap = std::min<unsigned long long>(h_cnt[0], A.edge_cap);      // rows that exist in memory
-            std::vector<unsigned long long> hh(2 * (size_t)h_cnt[7]);
-            if (!hh.empty() && (hipMemcpyAsync(hh.data(), d_holes, hh.size() * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)) { rc = cf_fail(ctx, -5, "edge holes copy"); break; }
-            std::vector<std::pair<unsigned long long, unsigned long long>> holes;      // [start, end) clipped to the rows in memory, sorted
-            for (size_t i = 0; i + 1 < hh.size(); i += 2) {
-                const unsigned long long s0 = std::min(hh[i], a_cap), s1 = std::min(hh[i] + hh[i + 1], a_cap);
-                if (s1 > s0) holes.emplace_back(s0, s1);
-            }
-            std::sort(holes.begin(), holes.end());
-            unsigned long long hole_rows = 0;
-            for (auto& h : holes) hole_rows += h.second - h.first;
-            const unsigned long long n_valid = a_cap - hole_rows;
-            n_stored = (int64_t)std::min<unsigned long long>(n_valid, (unsigned long long)edge_cap);
-            std::vector<unsigned long long> dst_start, dst_pre, src_start, src_pre;
-            unsigned long long dsum = 0, ssum = 0, at = n_valid;
-            for (auto& h : holes) {
-                if (h.first < n_valid) { const unsigned long long e1 = std::min(h.second, n_valid); dsum += e1 - h.first; dst_start.push_back(h.first); dst_pre.push_back(dsum); }
-                if (h.second > n_valid) {      // valid rows between `at` and this hole's part above n_valid
-                    const unsigned long long h0 = std::max(h.first, n_valid);
-                    if (h0 > at) { ssum += h0 - at; src_start.push_back(at); src_pre.push_back(ssum); }
-                    at = h.second;
-                }
-            }
-            if (a_cap > at) { ssum += a_cap - at; src_start.push_back(at); src_pre.push_back(ssum); }
-            if (dsum != ssum) { rc = cf_fail(ctx, -5, "cf_dist_edges: internal error, edge holes do not match the rows above them"); break; }
-            if (dsum) {
-                unsigned long long* d_seg = nullptr;
-                const size_t n_seg = src_start.size() * 2 + dst_start.size() * 2;
-                if ((rc = cf_alloc_t(ctx, &d_seg, n_seg, "edge move lists"))) break;
-                std::vector<unsigned long long> pack;
-                pack.insert(pack.end(), src_start.begin(), src_start.end()); pack.insert(pack.end(), src_pre.begin(), src_pre.end());
-                pack.insert(pack.end(), dst_start.begin(), dst_start.end()); pack.insert(pack.end(), dst_pre.begin(), dst_pre.end());
-                hipError_t e2 = hipMemcpyAsync(d_seg, pack.data(), n_seg * 8, hipMemcpyHostToDevice, ctx->stream);
-                if (e2 == hipSuccess) {
-                    hipLaunchKernelGGL(cf_edge_compact_kernel, dim3((unsigned)cf_grid_for((int64_t)dsum, 256, max_blocks)), dim3(256), 0, ctx->stream, ctx->d_edges,
-                                       (const unsigned long long*)d_seg, (const unsigned long long*)(d_seg + src_start.size()), (int)src_start.size(),
-                                       (const unsigned long long*)(d_seg + 2 * src_start.size()), (const unsigned long long*)(d_seg + 2 * src_start.size() + dst_start.size()), (int)dst_start.size(), dsum);
-                    e2 = hipGetLastError();
-                }
-                if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
-                cf_release_t(ctx, d_seg, n_seg);
-                if (e2 != hipSuccess) { rc = cf_fail(ctx, -5, std::string("edge compaction: ") + hipGetErrorString(e2)); break; }
+    if (h_cnt[4] & 2ull) return cf_fail(ctx, -5, "cf_dist_edges: the kernel's dynamic LDS does not begin at address 0");
+    if (h_cnt[4]) return cf_fail(ctx, -34, "cf_dist_edges: (b,d) table could not be partitioned far enough");
+    // close the holes of the chunked edge output: the valid rows at or above n_valid move into the holes below it
+    {
+        const unsigned long long a_cap = std::min<unsigned long long>(h_cnt[0], A.edge_cap);      // rows that exist in memory
+        std::vector<unsigned long long> hh(2 * (size_t)h_cnt[7]);
+        if (!hh.empty()) {
+            CF_HIP(hipMemcpyAsync(hh.data(), d_holes, hh.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+            CF_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        std::vector<std::pair<unsigned long long, unsigned long long>> holes;      // [start, end) clipped to the rows in memory, sorted
+        for (size_t i = 0; i + 1 < hh.size(); i += 2) {
+            const unsigned long long s0 = std::min(hh[i], a_cap), s1 = std::min(hh[i] + hh[i + 1], a_cap);
+            if (s1 > s0) holes.emplace_back(s0, s1);
+        }
+        std::sort(holes.begin(), holes.end());
+        unsigned long long hole_rows = 0;
+        for (auto& h : holes) hole_rows += h.second - h.first;
+        const unsigned long long n_valid = a_cap - hole_rows;
+        n_stored = (int64_t)std::min<unsigned long long>(n_valid, (unsigned long long)edge_cap);
+        std::vector<unsigned long long> dst_start, dst_pre, src_start, src_pre;
+        unsigned long long dsum = 0, ssum = 0, at = n_valid;
+        for (auto& h : holes) {
+            if (h.first < n_valid) { const unsigned long long e1 = std::min(h.second, n_valid); dsum += e1 - h.first; dst_start.push_back(h.first); dst_pre.push_back(dsum); }
+            if (h.second > n_valid) {      // valid rows between `at` and this hole's part above n_valid
+                const unsigned long long h0 = std::max(h.first, n_valid);
+                if (h0 > at) { ssum += h0 - at; src_start.push_back(at); src_pre.push_back(ssum); }
+                at = h.second;
             }
         }
-        // (the stage ends behind the compaction of the chunked edge output, not behind the kernel)
-        if (hipEventRecord(ctx->ev1, ctx->stream) != hipSuccess || hipEventSynchronize(ctx->ev1) != hipSuccess) { rc = cf_fail(ctx, -5, "cf_dist_edges: final event"); break; }
-        (void)hipEventElapsedTime(&ctx->times.dist_ms, ctx->ev0, ctx->ev1);
-        (void)hipEventElapsedTime(&ctx->times.postings_ms, ctx->ev0, ctx->ev2);
-        (void)hipEventElapsedTime(&ctx->times.dist_kernel_ms, ctx->ev2, ctx->ev3);
-    } while (0);
-    if (d_holes) cf_release_t(ctx, d_holes, 2 * n_holes_alloc);
-    if (d_items) cf_release_t(ctx, d_items, (size_t)n_item_slots + 64);
-    if (d_heads) cf_release_t(ctx, d_heads, (size_t)n_order);
-    if (d_ibase) cf_release_t(ctx, d_ibase, (size_t)n_order + 1);
-    if (d_ialloc) cf_release_t(ctx, d_ialloc, (size_t)n_order + 1);
-    if (d_icnt) cf_release_t(ctx, d_icnt, (size_t)n_order + 1);
-    if (d_order) cf_release_t(ctx, d_order, (size_t)n_a_alloc);
-    if (d_otmp) cf_release_t(ctx, d_otmp, (size_t)n_a_alloc);
-    if (d_okeys) cf_release_t(ctx, d_okeys, (size_t)n_a_alloc);
-    if (d_first) cf_release_t(ctx, d_first, (size_t)K + 1);
-    if (d_cnt) cf_release_t(ctx, d_cnt, n_cnt);
-    if (d_entry_i) cf_release_t(ctx, d_entry_i, (size_t)v_n_entries + 1);
-    if (d_packed) cf_release_t(ctx, d_packed, (size_t)v_n_entries + DIST_ITEM);
-    if (d_entry_i8) cf_release_t(ctx, d_entry_i8, (size_t)v_n_entries + 4 * DIST_ITEM);
-    if (d_urange) cf_release_t(ctx, d_urange, (size_t)U + 1);
-    if (d_rbeg) cf_release_t(ctx, d_rbeg, (size_t)U + 1);
-    if (d_rend) cf_release_t(ctx, d_rend, (size_t)U + 1);
-    if (d_post) cf_release_t(ctx, d_post, (size_t)n_post);
-    if (d_post_ptr) cf_release_t(ctx, d_post_ptr, (size_t)K + 1);
-    if (d_cursor) cf_release_t(ctx, d_cursor, (size_t)K + 1);
-    if (d_pcnt) cf_release_t(ctx, d_pcnt, (size_t)K + 1);
-    if (rc) return rc;
+        if (a_cap > at) { ssum += a_cap - at; src_start.push_back(at); src_pre.push_back(ssum); }
+        if (dsum != ssum) return cf_fail(ctx, -5, "cf_dist_edges: internal error, edge holes do not match the rows above them");
+        if (dsum) {
+            cf_scratch seg(ctx);
+            unsigned long long* d_seg = nullptr;
+            const size_t n_seg = src_start.size() * 2 + dst_start.size() * 2;
+            CF_TRY(seg.get(&d_seg, n_seg, "edge move lists"));
+            std::vector<unsigned long long> pack;
+            pack.insert(pack.end(), src_start.begin(), src_start.end()); pack.insert(pack.end(), src_pre.begin(), src_pre.end());
+            pack.insert(pack.end(), dst_start.begin(), dst_start.end()); pack.insert(pack.end(), dst_pre.begin(), dst_pre.end());
+            CF_HIP(hipMemcpyAsync(d_seg, pack.data(), n_seg * 8, hipMemcpyHostToDevice, ctx->stream));
+            hipLaunchKernelGGL(cf_edge_compact_kernel, dim3((unsigned)cf_grid_for((int64_t)dsum, 256, max_blocks)), dim3(256), 0, ctx->stream, ctx->d_edges,
+                               (const unsigned long long*)d_seg, (const unsigned long long*)(d_seg + src_start.size()), (int)src_start.size(),
+                               (const unsigned long long*)(d_seg + 2 * src_start.size()), (const unsigned long long*)(d_seg + 2 * src_start.size() + dst_start.size()), (int)dst_start.size(), dsum);
+            CF_KERNEL_CHECK("cf_edge_compact_kernel");
+            CF_HIP(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    // (the stage ends behind the compaction of the chunked edge output, not behind the kernel)
+    CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    CF_HIP(hipEventSynchronize(ctx->ev1));
+    (void)hipEventElapsedTime(&ctx->times.dist_ms, ctx->ev0, ctx->ev1);
+    (void)hipEventElapsedTime(&ctx->times.postings_ms, ctx->ev0, ctx->ev2);
+    (void)hipEventElapsedTime(&ctx->times.dist_kernel_ms, ctx->ev2, ctx->ev3);
     ctx->stats.n_edges = (int64_t)h_cnt[6];
     ctx->stats.n_emissions = (int64_t)h_cnt[1] - (int64_t)h_cnt[3];      // partner entries swept, less those that are the first k-mer itself (a != b in the reference)
     ctx->stats.n_spilled = (int64_t)h_cnt[2];

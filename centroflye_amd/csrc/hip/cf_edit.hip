@@ -321,47 +321,33 @@ int cf_edit_distances(cf_ctx* ctx, const uint8_t* bytes, const int64_t* a_off, c
     int32_t *d_scratch = nullptr, *d_dist = nullptr;
     unsigned long long* d_ticket = nullptr;
     const size_t n_scratch = (size_t)grid * 2 * (size_t)scratch_diags;
-    int rc = 0;
-    do {
-        if (bytes) {
-            if ((rc = cf_alloc_t(ctx, &d_bytes, (size_t)total + CF_EDIT_PAD, "edit bytes"))) break;
-            if (total > 0 && (rc = cf_copy_h2d(ctx, d_bytes, bytes, (size_t)total))) break;
-            hipError_t e = hipMemsetAsync(d_bytes + total, 0, CF_EDIT_PAD, ctx->stream);
-            if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_edit_distances: ") + hipGetErrorString(e)); break; }
-        }
-        if ((rc = cf_alloc_t(ctx, &d_a, (size_t)n_pairs + 1, "edit offsets"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_b, (size_t)n_pairs + 1, "edit offsets"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_order, (size_t)n_pairs, "edit order"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_dist, (size_t)n_pairs, "edit distances"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_ticket, 1, "edit ticket"))) break;
-        if (n_scratch && (rc = cf_alloc_t(ctx, &d_scratch, n_scratch, "edit wavefronts"))) break;
-        if ((rc = cf_copy_h2d(ctx, d_a, a_off, ((size_t)n_pairs + 1) * 8))) break;
-        if ((rc = cf_copy_h2d(ctx, d_b, b_off, ((size_t)n_pairs + 1) * 8))) break;
-        if ((rc = cf_copy_h2d(ctx, d_order, order.data(), (size_t)n_pairs * 8))) break;
-        hipError_t e = hipMemsetAsync(d_ticket, 0, 8, ctx->stream);
-        if (e == hipSuccess && lds > ((size_t)64 << 10))
-            e = hipFuncSetAttribute((const void*)cf_edit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_edit_distances: ") + hipGetErrorString(e)); break; }
-        hipLaunchKernelGGL(cf_edit_kernel, dim3((unsigned)grid), dim3((unsigned)block), lds, ctx->stream,
-                           (const uint8_t*)(bytes ? d_bytes : ctx->d_edit), (const int64_t*)d_a, (const int64_t*)d_b, (const int64_t*)d_order,
-                           n_pairs, k, lds_diags, d_scratch, scratch_diags, d_ticket, d_dist);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev1);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_edit_distances: ") + hipGetErrorString(e)); break; }
-        float t = 0.f;
-        (void)hipEventElapsedTime(&t, ctx->ev0, ctx->ev1);
-        if (ms) *ms = t;
-        if ((rc = cf_copy_d2h(ctx, dist, d_dist, (size_t)n_pairs * 4))) break;
-    } while (0);
-    if (d_scratch) cf_release_t(ctx, d_scratch, n_scratch);
-    if (d_ticket) cf_release_t(ctx, d_ticket, 1);
-    if (d_dist) cf_release_t(ctx, d_dist, (size_t)n_pairs);
-    if (d_order) cf_release_t(ctx, d_order, (size_t)n_pairs);
-    if (d_b) cf_release_t(ctx, d_b, (size_t)n_pairs + 1);
-    if (d_a) cf_release_t(ctx, d_a, (size_t)n_pairs + 1);
-    if (d_bytes) cf_release_t(ctx, d_bytes, (size_t)total + CF_EDIT_PAD);
-    return rc;
+    cf_scratch tmp(ctx);
+    if (bytes) {
+        CF_TRY(tmp.get(&d_bytes, (size_t)total + CF_EDIT_PAD, "edit bytes"));
+        if (total > 0) CF_TRY(cf_copy_h2d(ctx, d_bytes, bytes, (size_t)total));
+        CF_HIP(hipMemsetAsync(d_bytes + total, 0, CF_EDIT_PAD, ctx->stream));
+    }
+    CF_TRY(tmp.get(&d_a, (size_t)n_pairs + 1, "edit offsets"));
+    CF_TRY(tmp.get(&d_b, (size_t)n_pairs + 1, "edit offsets"));
+    CF_TRY(tmp.get(&d_order, (size_t)n_pairs, "edit order"));
+    CF_TRY(tmp.get(&d_dist, (size_t)n_pairs, "edit distances"));
+    CF_TRY(tmp.get(&d_ticket, 1, "edit ticket"));
+    if (n_scratch) CF_TRY(tmp.get(&d_scratch, n_scratch, "edit wavefronts"));
+    CF_TRY(cf_copy_h2d(ctx, d_a, a_off, ((size_t)n_pairs + 1) * 8));
+    CF_TRY(cf_copy_h2d(ctx, d_b, b_off, ((size_t)n_pairs + 1) * 8));
+    CF_TRY(cf_copy_h2d(ctx, d_order, order.data(), (size_t)n_pairs * 8));
+    CF_HIP(hipMemsetAsync(d_ticket, 0, 8, ctx->stream));
+    if (lds > ((size_t)64 << 10)) CF_HIP(hipFuncSetAttribute((const void*)cf_edit_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(cf_edit_kernel, dim3((unsigned)grid), dim3((unsigned)block), lds, ctx->stream,
+                       (const uint8_t*)(bytes ? d_bytes : ctx->d_edit), (const int64_t*)d_a, (const int64_t*)d_b, (const int64_t*)d_order,
+                       n_pairs, k, lds_diags, d_scratch, scratch_diags, d_ticket, d_dist);
+    CF_KERNEL_CHECK("cf_edit_kernel");
+    CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    CF_HIP(hipEventSynchronize(ctx->ev1));
+    float t = 0.f;
+    (void)hipEventElapsedTime(&t, ctx->ev0, ctx->ev1);
+    if (ms) *ms = t;
+    return cf_copy_d2h(ctx, dist, d_dist, (size_t)n_pairs * 4);
 }
 
 int cf_hpc(cf_ctx* ctx, const uint8_t* bytes, const int64_t* off, int64_t n_seqs, uint8_t* out_bytes, int64_t* out_off) {
@@ -384,44 +370,37 @@ int cf_hpc(cf_ctx* ctx, const uint8_t* bytes, const int64_t* off, int64_t n_seqs
     const int64_t G = (total + 7) >> 3;
     const int grid = cf_grid_for(G, CF_HPC_THREADS, std::max(1, ctx->n_cu) * 16);
     const int sgrid = cf_grid_for(n_seqs + 1, CF_HPC_THREADS, std::max(1, ctx->n_cu) * 16);
+    uint8_t* d_seq = nullptr;      // the context's once everything worked
     uint32_t *d_keep = nullptr, *d_cnt = nullptr;
     int64_t *d_idx = nullptr, *d_off = nullptr, *d_out_off = nullptr;
     int64_t total_out = 0;
-    int rc = 0;
-    do {
-        if ((rc = cf_alloc_t(ctx, &ctx->d_edit, cap, "resident sequences"))) break;
-        ctx->edit_cap = cap;
-        if ((rc = cf_alloc_t(ctx, &d_keep, (size_t)G, "hpc keep masks"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_cnt, (size_t)G, "hpc counts"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_idx, (size_t)G, "hpc offsets"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_off, (size_t)n_seqs + 1, "sequence offsets"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_out_off, (size_t)n_seqs + 1, "compressed offsets"))) break;
-        if ((rc = cf_copy_h2d(ctx, ctx->d_edit, bytes, (size_t)total))) break;
-        if ((rc = cf_copy_h2d(ctx, d_off, off, ((size_t)n_seqs + 1) * 8))) break;
-        hipError_t e = hipMemsetAsync(ctx->d_edit + total, 0, cap - (size_t)total, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_keep, 0, (size_t)G * 4, ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_hpc: ") + hipGetErrorString(e)); break; }
-        hipLaunchKernelGGL(cf_hpc_start_kernel, dim3((unsigned)sgrid), dim3(CF_HPC_THREADS), 0, ctx->stream, (const int64_t*)d_off, n_seqs, total, d_keep);
-        hipLaunchKernelGGL(cf_hpc_flag_kernel, dim3((unsigned)grid), dim3(CF_HPC_THREADS), 0, ctx->stream, (const uint8_t*)ctx->d_edit, total, d_keep, d_cnt);
-        if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_cnt, d_idx, G, &total_out))) break;
-        hipLaunchKernelGGL(cf_hpc_compact_kernel, dim3((unsigned)grid), dim3(CF_HPC_THREADS), 0, ctx->stream, (const uint8_t*)ctx->d_edit, total,
-                           (const uint32_t*)d_keep, (const int64_t*)d_idx, ctx->d_edit + total);
-        hipLaunchKernelGGL(cf_hpc_off_kernel, dim3((unsigned)sgrid), dim3(CF_HPC_THREADS), 0, ctx->stream, (const int64_t*)d_off, n_seqs, total, total_out,
-                           (const uint32_t*)d_keep, (const int64_t*)d_idx, d_out_off);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_hpc: ") + hipGetErrorString(e)); break; }
-        if ((rc = cf_copy_d2h(ctx, out_bytes, ctx->d_edit + total, (size_t)total_out))) break;
-        if ((rc = cf_copy_d2h(ctx, out_off, d_out_off, ((size_t)n_seqs + 1) * 8))) break;
-        ctx->edit_len = total + total_out;
-    } while (0);
-    if (d_out_off) cf_release_t(ctx, d_out_off, (size_t)n_seqs + 1);
-    if (d_off) cf_release_t(ctx, d_off, (size_t)n_seqs + 1);
-    if (d_idx) cf_release_t(ctx, d_idx, (size_t)G);
-    if (d_cnt) cf_release_t(ctx, d_cnt, (size_t)G);
-    if (d_keep) cf_release_t(ctx, d_keep, (size_t)G);
-    if (rc != 0) cf_edit_free(ctx);
-    return rc;
+    cf_scratch tmp(ctx);
+    CF_TRY(tmp.get(&d_seq, cap, "resident sequences"));
+    CF_TRY(tmp.get(&d_keep, (size_t)G, "hpc keep masks"));
+    CF_TRY(tmp.get(&d_cnt, (size_t)G, "hpc counts"));
+    CF_TRY(tmp.get(&d_idx, (size_t)G, "hpc offsets"));
+    CF_TRY(tmp.get(&d_off, (size_t)n_seqs + 1, "sequence offsets"));
+    CF_TRY(tmp.get(&d_out_off, (size_t)n_seqs + 1, "compressed offsets"));
+    CF_TRY(cf_copy_h2d(ctx, d_seq, bytes, (size_t)total));
+    CF_TRY(cf_copy_h2d(ctx, d_off, off, ((size_t)n_seqs + 1) * 8));
+    CF_HIP(hipMemsetAsync(d_seq + total, 0, cap - (size_t)total, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_keep, 0, (size_t)G * 4, ctx->stream));
+    hipLaunchKernelGGL(cf_hpc_start_kernel, dim3((unsigned)sgrid), dim3(CF_HPC_THREADS), 0, ctx->stream, (const int64_t*)d_off, n_seqs, total, d_keep);
+    hipLaunchKernelGGL(cf_hpc_flag_kernel, dim3((unsigned)grid), dim3(CF_HPC_THREADS), 0, ctx->stream, (const uint8_t*)d_seq, total, d_keep, d_cnt);
+    CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_cnt, d_idx, G, &total_out));
+    hipLaunchKernelGGL(cf_hpc_compact_kernel, dim3((unsigned)grid), dim3(CF_HPC_THREADS), 0, ctx->stream, (const uint8_t*)d_seq, total,
+                       (const uint32_t*)d_keep, (const int64_t*)d_idx, d_seq + total);
+    hipLaunchKernelGGL(cf_hpc_off_kernel, dim3((unsigned)sgrid), dim3(CF_HPC_THREADS), 0, ctx->stream, (const int64_t*)d_off, n_seqs, total, total_out,
+                       (const uint32_t*)d_keep, (const int64_t*)d_idx, d_out_off);
+    CF_KERNEL_CHECK("the cf_hpc kernels");
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    CF_TRY(cf_copy_d2h(ctx, out_bytes, d_seq + total, (size_t)total_out));
+    CF_TRY(cf_copy_d2h(ctx, out_off, d_out_off, ((size_t)n_seqs + 1) * 8));
+    tmp.keep(d_seq);
+    ctx->d_edit = d_seq;
+    ctx->edit_cap = cap;
+    ctx->edit_len = total + total_out;
+    return 0;
 }
 
 }  // extern "C"

@@ -122,26 +122,12 @@ void cf_free_gview(cf_ctx* c) {
 
 namespace {
 
-// temporaries of one call: released in reverse order when the guard goes out of scope
-struct Bufs {
-    cf_ctx* ctx;
-    std::vector<std::pair<void*, size_t>> v;
-    explicit Bufs(cf_ctx* c) : ctx(c) {}
-    ~Bufs() { for (auto it = v.rbegin(); it != v.rend(); ++it) cf_release(ctx, it->first, it->second); }
-    template <class T> int get(T** p, size_t n, const char* what) {
-        int rc = cf_alloc_t(ctx, p, n, what);
-        if (rc == 0) v.emplace_back((void*)*p, n * sizeof(T));
-        return rc;
-    }
-    void keep(void* p) { for (auto& e : v) if (e.first == p) e.first = nullptr; }   // cf_release(nullptr) is a no-op
-};
-
 int comm_fail(cf_ctx* ctx, int rc, const std::string& err) { return cf_fail(ctx, rc, err); }
 
 // every rank's n (one int64 each)
 int gather_counts(cf_ctx* ctx, int64_t mine, std::vector<int64_t>& all) {
     cf_comm* cm = ctx->comm;
-    Bufs tmp(ctx);
+    cf_scratch tmp(ctx);
     int64_t *d_one = nullptr, *d_all = nullptr;
     CF_TRY(tmp.get(&d_one, 1, "comm count"));
     CF_TRY(tmp.get(&d_all, (size_t)cm->world, "comm counts"));
@@ -157,7 +143,7 @@ int gather_counts(cf_ctx* ctx, int64_t mine, std::vector<int64_t>& all) {
 
 // all-gather of device arrays of different lengths (bytes): every rank sends its array to every peer (send/recv pairs:
 // all links at once); *d_out (allocated here, sum of counts) holds them in rank order
-int allgatherv(cf_ctx* ctx, Bufs& keep, const void* d_mine, int64_t my_bytes, char** d_out, std::vector<int64_t>& bytes, const char* what) {
+int allgatherv(cf_ctx* ctx, cf_scratch& keep, const void* d_mine, int64_t my_bytes, char** d_out, std::vector<int64_t>& bytes, const char* what) {
     cf_comm* cm = ctx->comm;
     CF_TRY(gather_counts(ctx, my_bytes, bytes));
     const int W = cm->world;
@@ -212,7 +198,7 @@ int cf_comm_allreduce_i64(cf_ctx* ctx, int64_t* vals, int64_t n, int32_t op) {
     if (!ctx->comm) return cf_fail(ctx, -22, "cf_comm_allreduce_i64: no communicator (cf_comm_init)");
     if (n == 0) return 0;
     CF_HIP(hipSetDevice(ctx->device));
-    Bufs tmp(ctx);
+    cf_scratch tmp(ctx);
     int64_t* d = nullptr;
     CF_TRY(tmp.get(&d, (size_t)n, "allreduce values"));
     CF_HIP(hipMemcpyAsync(d, vals, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -232,7 +218,7 @@ int cf_exchange_table(cf_ctx* ctx, int64_t* bytes_sent) {
     cf_comm* cm = ctx->comm;
     const uint32_t W = (uint32_t)cm->world;
     const int grid = std::max(1, ctx->n_cu) * 8;
-    Bufs tmp(ctx);
+    cf_scratch tmp(ctx);
     int64_t* d_blk = nullptr;
     CF_TRY(tmp.get(&d_blk, (size_t)W * grid + 1, "exchange block counts"));
     const size_t lds = (size_t)W * 4 + 16;
@@ -305,7 +291,7 @@ int cf_allgather_kmers(cf_ctx* ctx, int64_t* n_out) {
     if (!ctx->comm) return cf_fail(ctx, -22, "cf_allgather_kmers: no communicator (cf_comm_init)");
     if (!ctx->d_lut) return cf_fail(ctx, -22, "cf_allgather_kmers: no k-mer set selected");
     CF_HIP(hipSetDevice(ctx->device));
-    Bufs tmp(ctx);
+    cf_scratch tmp(ctx);
     char* d_all = nullptr;
     std::vector<int64_t> bytes;
     CF_TRY(allgatherv(ctx, tmp, ctx->d_kmers, ctx->n_kmers * 8, &d_all, bytes, "gathered k-mers"));
@@ -334,7 +320,7 @@ int cf_allgather_clouds(cf_ctx* ctx, int64_t* n_entries) {
     cf_free_gview(ctx);
     const int64_t R = ctx->n_reads, U = ctx->n_units, N = ctx->n_entries;
     const int grid = std::max(1, ctx->n_cu) * 8;
-    Bufs tmp(ctx);
+    cf_scratch tmp(ctx);
     int64_t *d_upr = nullptr, *d_sizes = nullptr;
     CF_TRY(tmp.get(&d_upr, (size_t)R + 1, "units per read"));
     CF_TRY(tmp.get(&d_sizes, (size_t)U + 1, "cloud sizes"));
@@ -400,7 +386,7 @@ int cf_allreduce_unique(cf_ctx* ctx, int64_t* n_unique) {
     CF_HIP(hipSetDevice(ctx->device));
     const int64_t n = ctx->n_kmers;
     if (n) {
-        Bufs tmp(ctx);
+        cf_scratch tmp(ctx);
         uint8_t* d_bytes = nullptr;
         CF_TRY(tmp.get(&d_bytes, (size_t)n, "unique mask bytes"));
         const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);

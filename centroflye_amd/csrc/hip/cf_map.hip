@@ -264,92 +264,76 @@ static int contig_build(cf_ctx* ctx, const int64_t* reads, const int64_t* pos, i
     uint32_t *d_freq = nullptr, *d_flag = nullptr;
     int64_t n_rec = 0, n_pairs = 0, n_exact = 0;
     unsigned long long h_counts[2] = {0, 0};
-    int rc = 0;
     ctx->contig_K = K;
     ctx->contig_cov_n = covered ? max_pos + 1 : 0;
-    do {
-        if ((rc = cf_alloc_t(ctx, &ctx->d_contig_ptr, (size_t)K + 1, "contig_ptr"))) break;
-        if ((rc = cf_alloc_t(ctx, &ctx->d_contig_cov, (size_t)ctx->contig_cov_n, "contig coverage"))) break;
-        if ((rc = cf_alloc_t(ctx, &ctx->d_exact_ptr, (size_t)K + 1, "exact contig_ptr"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_freq, (size_t)K + 1, "frequent ranks"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_counts, 2, "contig counters"))) break;
-        hipError_t e = hipMemsetAsync(ctx->d_contig_ptr, 0, (size_t)(K + 1) * 8, ctx->stream);
-        if (e == hipSuccess && ctx->contig_cov_n) e = hipMemsetAsync(ctx->d_contig_cov, 0, (size_t)ctx->contig_cov_n * 4, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(ctx->d_exact_ptr, 0, (size_t)(K + 1) * 8, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_freq, 0, (size_t)(K + 1) * 4, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, 16, ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_contig_build memset: ") + hipGetErrorString(e)); break; }
-        if (n > 0) {
-            if ((rc = cf_alloc_t(ctx, &d_breads, (size_t)n, "backbone reads"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_bpos, (size_t)n, "backbone positions"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_sizes, (size_t)n, "backbone sizes"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_off, (size_t)n, "backbone offsets"))) break;
-            if ((rc = cf_copy_h2d(ctx, d_breads, reads, (size_t)n * 8))) break;
-            if ((rc = cf_copy_h2d(ctx, d_bpos, pos, (size_t)n * 8))) break;
-            hipLaunchKernelGGL(cf_contig_sizes_kernel, dim3((unsigned)cf_grid_for(n, 256, max_grid)), dim3(256), 0, ctx->stream,
-                               (const int64_t*)d_breads, n, (const int64_t*)ctx->d_unit_ptr, (const int64_t*)ctx->d_cloud_ptr, d_sizes);
-            if ((rc = cf_scan_exclusive_i64(ctx, d_sizes, d_off, n, &n_rec))) break;      // (its total sizes the record buffers)
-            if ((rc = cf_alloc_t(ctx, &d_recs, (size_t)n_rec, "contig records"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_tmp, (size_t)n_rec, "contig sort scratch"))) break;
-            hipLaunchKernelGGL(cf_contig_emit_kernel, dim3((unsigned)cf_grid_for(n * 64, 256, max_grid * 4)), dim3(256), 0, ctx->stream,
-                               (const int64_t*)d_breads, (const int64_t*)d_bpos, n, (const int64_t*)ctx->d_unit_ptr,
-                               (const int64_t*)ctx->d_cloud_ptr, (const int32_t*)ctx->d_entries, (const int64_t*)d_off, pbits, d_recs,
-                               ctx->d_contig_cov);
-            e = hipGetLastError();
-            if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("launch of cf_contig_emit_kernel: ") + hipGetErrorString(e)); break; }
-        }
-        sorted = d_recs;
-        if (n_rec > 0) {
-            if ((rc = cf_radix_sort_u64_any(ctx, d_recs, d_tmp, n_rec, pbits + kbits, &sorted))) break;
-            if ((rc = cf_alloc_t(ctx, &d_flag, (size_t)n_rec, "contig flags"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_idx, (size_t)n_rec, "contig offsets"))) break;
-            const int grid = cf_grid_for(n_rec, 256, max_grid * 4);
-            hipLaunchKernelGGL(cf_contig_freq_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec, f,
-                               pbits, d_freq);
-            hipLaunchKernelGGL(cf_contig_flag_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec,
-                               pbits, (const uint32_t*)d_freq, d_flag);
-            if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_flag, d_idx, n_rec, &n_pairs))) break;
-            ctx->contig_pairs = n_pairs;
-            if ((rc = cf_alloc_t(ctx, &ctx->d_contig_pos, (size_t)n_pairs, "contig positions"))) break;
-            if (n_pairs)
-                hipLaunchKernelGGL(cf_contig_fill_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec,
-                                   pbits, (const uint32_t*)d_flag, (const int64_t*)d_idx, ctx->d_contig_pos);
-            hipLaunchKernelGGL(cf_contig_ptr_kernel, dim3((unsigned)cf_grid_for(K + 1, 256, max_grid * 4)), dim3(256), 0, ctx->stream,
-                               (const unsigned long long*)sorted, n_rec, pbits, (const int64_t*)d_idx, n_pairs, K, ctx->d_contig_ptr,
-                               ctx->d_exact_ptr);
-            hipLaunchKernelGGL(cf_contig_nonzero_kernel, dim3((unsigned)cf_grid_for(K, 256, max_grid)), dim3(256), 64, ctx->stream,
-                               (const uint32_t*)d_freq, K, d_counts + 1);
-            // the exact CSR from the same sorted records; the flags and offsets of the CSR above are done with (stream order)
-            hipLaunchKernelGGL(cf_contig_exact_flag_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted,
-                               n_rec, f, d_flag);
-            if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_flag, d_idx, n_rec, &n_exact))) break;
-            ctx->exact_pairs = n_exact;
-            if ((rc = cf_alloc_t(ctx, &ctx->d_exact_pos, (size_t)n_exact, "exact contig positions"))) break;
-            if (n_exact)
-                hipLaunchKernelGGL(cf_contig_fill_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec,
-                                   pbits, (const uint32_t*)d_flag, (const int64_t*)d_idx, ctx->d_exact_pos);
-            hipLaunchKernelGGL(cf_contig_ptr_of_first_kernel, dim3((unsigned)cf_grid_for(K + 1, 256, max_grid * 4)), dim3(256), 0, ctx->stream,
-                               ctx->d_exact_ptr, K, n_rec, (const int64_t*)d_idx, n_exact);
-        }
-        if (ctx->contig_cov_n)
-            hipLaunchKernelGGL(cf_contig_nonzero_kernel, dim3((unsigned)cf_grid_for(ctx->contig_cov_n, 256, max_grid)), dim3(256), 64, ctx->stream,
-                               (const uint32_t*)ctx->d_contig_cov, ctx->contig_cov_n, d_counts);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(h_counts, d_counts, 16, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_contig_build: ") + hipGetErrorString(e)); break; }
-    } while (0);
-    if (d_idx) cf_release_t(ctx, d_idx, (size_t)n_rec);
-    if (d_flag) cf_release_t(ctx, d_flag, (size_t)n_rec);
-    if (d_tmp) cf_release_t(ctx, d_tmp, (size_t)n_rec);
-    if (d_recs) cf_release_t(ctx, d_recs, (size_t)n_rec);
-    if (d_off) cf_release_t(ctx, d_off, (size_t)n);
-    if (d_sizes) cf_release_t(ctx, d_sizes, (size_t)n);
-    if (d_bpos) cf_release_t(ctx, d_bpos, (size_t)n);
-    if (d_breads) cf_release_t(ctx, d_breads, (size_t)n);
-    if (d_counts) cf_release_t(ctx, d_counts, 2);
-    if (d_freq) cf_release_t(ctx, d_freq, (size_t)K + 1);
-    if (rc) { cf_free_contig(ctx); return rc; }
+    cf_scratch tmp(ctx);
+    CF_TRY(cf_alloc_t(ctx, &ctx->d_contig_ptr, (size_t)K + 1, "contig_ptr"));
+    CF_TRY(cf_alloc_t(ctx, &ctx->d_contig_cov, (size_t)ctx->contig_cov_n, "contig coverage"));
+    CF_TRY(cf_alloc_t(ctx, &ctx->d_exact_ptr, (size_t)K + 1, "exact contig_ptr"));
+    CF_TRY(tmp.get(&d_freq, (size_t)K + 1, "frequent ranks"));
+    CF_TRY(tmp.get(&d_counts, 2, "contig counters"));
+    CF_HIP(hipMemsetAsync(ctx->d_contig_ptr, 0, (size_t)(K + 1) * 8, ctx->stream));
+    if (ctx->contig_cov_n) CF_HIP(hipMemsetAsync(ctx->d_contig_cov, 0, (size_t)ctx->contig_cov_n * 4, ctx->stream));
+    CF_HIP(hipMemsetAsync(ctx->d_exact_ptr, 0, (size_t)(K + 1) * 8, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_freq, 0, (size_t)(K + 1) * 4, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_counts, 0, 16, ctx->stream));
+    if (n > 0) {
+        CF_TRY(tmp.get(&d_breads, (size_t)n, "backbone reads"));
+        CF_TRY(tmp.get(&d_bpos, (size_t)n, "backbone positions"));
+        CF_TRY(tmp.get(&d_sizes, (size_t)n, "backbone sizes"));
+        CF_TRY(tmp.get(&d_off, (size_t)n, "backbone offsets"));
+        CF_TRY(cf_copy_h2d(ctx, d_breads, reads, (size_t)n * 8));
+        CF_TRY(cf_copy_h2d(ctx, d_bpos, pos, (size_t)n * 8));
+        hipLaunchKernelGGL(cf_contig_sizes_kernel, dim3((unsigned)cf_grid_for(n, 256, max_grid)), dim3(256), 0, ctx->stream,
+                           (const int64_t*)d_breads, n, (const int64_t*)ctx->d_unit_ptr, (const int64_t*)ctx->d_cloud_ptr, d_sizes);
+        CF_TRY(cf_scan_exclusive_i64(ctx, d_sizes, d_off, n, &n_rec));      // (its total sizes the record buffers)
+        CF_TRY(tmp.get(&d_recs, (size_t)n_rec, "contig records"));
+        CF_TRY(tmp.get(&d_tmp, (size_t)n_rec, "contig sort scratch"));
+        hipLaunchKernelGGL(cf_contig_emit_kernel, dim3((unsigned)cf_grid_for(n * 64, 256, max_grid * 4)), dim3(256), 0, ctx->stream,
+                           (const int64_t*)d_breads, (const int64_t*)d_bpos, n, (const int64_t*)ctx->d_unit_ptr,
+                           (const int64_t*)ctx->d_cloud_ptr, (const int32_t*)ctx->d_entries, (const int64_t*)d_off, pbits, d_recs,
+                           ctx->d_contig_cov);
+        CF_KERNEL_CHECK("cf_contig_emit_kernel");
+    }
+    sorted = d_recs;
+    if (n_rec > 0) {
+        CF_TRY(cf_radix_sort_u64_any(ctx, d_recs, d_tmp, n_rec, pbits + kbits, &sorted));
+        CF_TRY(tmp.get(&d_flag, (size_t)n_rec, "contig flags"));
+        CF_TRY(tmp.get(&d_idx, (size_t)n_rec, "contig offsets"));
+        const int grid = cf_grid_for(n_rec, 256, max_grid * 4);
+        hipLaunchKernelGGL(cf_contig_freq_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec, f,
+                           pbits, d_freq);
+        hipLaunchKernelGGL(cf_contig_flag_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec,
+                           pbits, (const uint32_t*)d_freq, d_flag);
+        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_flag, d_idx, n_rec, &n_pairs));
+        ctx->contig_pairs = n_pairs;
+        CF_TRY(cf_alloc_t(ctx, &ctx->d_contig_pos, (size_t)n_pairs, "contig positions"));
+        if (n_pairs)
+            hipLaunchKernelGGL(cf_contig_fill_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec,
+                               pbits, (const uint32_t*)d_flag, (const int64_t*)d_idx, ctx->d_contig_pos);
+        hipLaunchKernelGGL(cf_contig_ptr_kernel, dim3((unsigned)cf_grid_for(K + 1, 256, max_grid * 4)), dim3(256), 0, ctx->stream,
+                           (const unsigned long long*)sorted, n_rec, pbits, (const int64_t*)d_idx, n_pairs, K, ctx->d_contig_ptr,
+                           ctx->d_exact_ptr);
+        hipLaunchKernelGGL(cf_contig_nonzero_kernel, dim3((unsigned)cf_grid_for(K, 256, max_grid)), dim3(256), 64, ctx->stream,
+                           (const uint32_t*)d_freq, K, d_counts + 1);
+        // the exact CSR from the same sorted records; the flags and offsets of the CSR above are done with (stream order)
+        hipLaunchKernelGGL(cf_contig_exact_flag_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted,
+                           n_rec, f, d_flag);
+        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_flag, d_idx, n_rec, &n_exact));
+        ctx->exact_pairs = n_exact;
+        CF_TRY(cf_alloc_t(ctx, &ctx->d_exact_pos, (size_t)n_exact, "exact contig positions"));
+        if (n_exact)
+            hipLaunchKernelGGL(cf_contig_fill_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const unsigned long long*)sorted, n_rec,
+                               pbits, (const uint32_t*)d_flag, (const int64_t*)d_idx, ctx->d_exact_pos);
+        hipLaunchKernelGGL(cf_contig_ptr_of_first_kernel, dim3((unsigned)cf_grid_for(K + 1, 256, max_grid * 4)), dim3(256), 0, ctx->stream,
+                           ctx->d_exact_ptr, K, n_rec, (const int64_t*)d_idx, n_exact);
+    }
+    if (ctx->contig_cov_n)
+        hipLaunchKernelGGL(cf_contig_nonzero_kernel, dim3((unsigned)cf_grid_for(ctx->contig_cov_n, 256, max_grid)), dim3(256), 64, ctx->stream,
+                           (const uint32_t*)ctx->d_contig_cov, ctx->contig_cov_n, d_counts);
+    CF_KERNEL_CHECK("the cf_contig kernels");
+    CF_HIP(hipMemcpyAsync(h_counts, d_counts, 16, hipMemcpyDeviceToHost, ctx->stream));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
     ctx->contig_P = (int64_t)h_counts[0];
     ctx->contig_n_freq = (int64_t)h_counts[1];
     ctx->contig_max_pos = covered ? max_pos : 0;      // (cloud_contig.py:20-24: 0 for an empty contig)
@@ -384,7 +368,8 @@ int cf_contig_build(cf_ctx* ctx, const int64_t* reads, const int64_t* pos, int64
     CF_HIP(hipSetDevice(ctx->device));
     cf_free_contig(ctx);
     CF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-    CF_TRY(contig_build(ctx, reads, pos, n, std::max<int64_t>(1, min_cloud_kmer_freq), max_pos, covered));
+    const int rc = contig_build(ctx, reads, pos, n, std::max<int64_t>(1, min_cloud_kmer_freq), max_pos, covered);
+    if (rc) { cf_free_contig(ctx); return rc; }      // no half-built contig stays behind
     CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     CF_HIP(hipEventSynchronize(ctx->ev1));
     CF_HIP(hipEventElapsedTime(&ctx->contig_build_ms, ctx->ev0, ctx->ev1));
@@ -430,33 +415,25 @@ int cf_map_reads(cf_ctx* ctx, const int64_t* reads, int64_t n, int32_t t0, int32
     const int W = ctx->map_window > 0 ? ctx->map_window : CF_MAP_WINDOW_DEFAULT;
     int64_t *d_q = nullptr, *d_pos = nullptr;
     int32_t *d_s0 = nullptr, *d_s1 = nullptr;
-    int rc = 0;
-    do {
-        if (reads) {
-            if ((rc = cf_alloc_t(ctx, &d_q, (size_t)n, "query reads"))) break;
-            if ((rc = cf_copy_h2d(ctx, d_q, reads, (size_t)n * 8))) break;
-        }
-        if ((rc = cf_alloc_t(ctx, &d_pos, (size_t)n, "mapped positions"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_s0, (size_t)n, "mapped s0"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_s1, (size_t)n, "mapped s1"))) break;
-        const int grid = (int)std::min<int64_t>(n, (int64_t)std::max(1, ctx->n_cu) * 64);
-        hipLaunchKernelGGL(cf_map_kernel, dim3((unsigned)grid), dim3(CF_MAP_THREADS), (size_t)W * 12, ctx->stream, (const int64_t*)d_q, n,
-                           (const int64_t*)ctx->d_unit_ptr, (const int64_t*)ctx->d_cloud_ptr, (const int32_t*)ctx->d_entries,
-                           (const int64_t*)ctx->d_contig_ptr, (const int32_t*)ctx->d_contig_pos, ctx->contig_P, W, t0, t1, d_pos, d_s0, d_s1);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev1);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_map_reads: ") + hipGetErrorString(e)); break; }
-        (void)hipEventElapsedTime(&ctx->map_ms, ctx->ev0, ctx->ev1);
-        if ((rc = cf_copy_d2h(ctx, out_pos, d_pos, (size_t)n * 8))) break;
-        if ((rc = cf_copy_d2h(ctx, out_s0, d_s0, (size_t)n * 4))) break;
-        if ((rc = cf_copy_d2h(ctx, out_s1, d_s1, (size_t)n * 4))) break;
-    } while (0);
-    if (d_s1) cf_release_t(ctx, d_s1, (size_t)n);
-    if (d_s0) cf_release_t(ctx, d_s0, (size_t)n);
-    if (d_pos) cf_release_t(ctx, d_pos, (size_t)n);
-    if (d_q) cf_release_t(ctx, d_q, (size_t)n);
-    return rc;
+    cf_scratch tmp(ctx);
+    if (reads) {
+        CF_TRY(tmp.get(&d_q, (size_t)n, "query reads"));
+        CF_TRY(cf_copy_h2d(ctx, d_q, reads, (size_t)n * 8));
+    }
+    CF_TRY(tmp.get(&d_pos, (size_t)n, "mapped positions"));
+    CF_TRY(tmp.get(&d_s0, (size_t)n, "mapped s0"));
+    CF_TRY(tmp.get(&d_s1, (size_t)n, "mapped s1"));
+    const int grid = (int)std::min<int64_t>(n, (int64_t)std::max(1, ctx->n_cu) * 64);
+    hipLaunchKernelGGL(cf_map_kernel, dim3((unsigned)grid), dim3(CF_MAP_THREADS), (size_t)W * 12, ctx->stream, (const int64_t*)d_q, n,
+                       (const int64_t*)ctx->d_unit_ptr, (const int64_t*)ctx->d_cloud_ptr, (const int32_t*)ctx->d_entries,
+                       (const int64_t*)ctx->d_contig_ptr, (const int32_t*)ctx->d_contig_pos, ctx->contig_P, W, t0, t1, d_pos, d_s0, d_s1);
+    CF_KERNEL_CHECK("cf_map_kernel");
+    CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    CF_HIP(hipEventSynchronize(ctx->ev1));
+    (void)hipEventElapsedTime(&ctx->map_ms, ctx->ev0, ctx->ev1);
+    CF_TRY(cf_copy_d2h(ctx, out_pos, d_pos, (size_t)n * 8));
+    CF_TRY(cf_copy_d2h(ctx, out_s0, d_s0, (size_t)n * 4));
+    return cf_copy_d2h(ctx, out_s1, d_s1, (size_t)n * 4);
 }
 
 }  // extern "C"

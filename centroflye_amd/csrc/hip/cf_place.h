@@ -149,20 +149,6 @@ __device__ __forceinline__ cf_key cf_block_best_key(cf_key mine) {
 }
 __device__ __forceinline__ cf_cand cf_block_best(const cf_key& mine) { return cf_cand_of(cf_block_best_key(mine)); }
 
-namespace {
-struct Bufs {
-    cf_ctx* ctx;
-    std::vector<std::pair<void*, size_t>> owned;
-    template <class T> int get(T** p, size_t n, const char* what) {
-        int rc = cf_alloc_t(ctx, p, n, what);
-        if (rc == 0) owned.emplace_back((void*)*p, n * sizeof(T));
-        return rc;
-    }
-    void release_all() { for (auto it = owned.rbegin(); it != owned.rend(); ++it) cf_release(ctx, it->first, it->second); owned.clear(); }
-    ~Bufs() { release_all(); }
-};
-}  // namespace
-
 // cf_place2.hip
 bool cf_place2_fits(const cf_ctx* ctx);
 int cf_place2_run(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, int32_t min_freq, int32_t min_unit, int32_t min_inters, int32_t min_prop,

@@ -297,7 +297,7 @@ static int place_attempt(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank
                          int32_t min_inters, int32_t min_prop, uint64_t score_cap, uint64_t seen_cap,
                          std::vector<int64_t>& o_read, std::vector<int64_t>& o_pos, std::vector<int32_t>& o_s0, std::vector<int32_t>& o_s1) {
     const int64_t R = ctx->n_reads, U = ctx->n_units, N = ctx->n_entries, K = ctx->n_kmers;
-    Bufs B{ctx, {}};
+    cf_scratch B(ctx);
     cf_place_state S;
     std::memset(&S, 0, sizeof S);
     S.unit_ptr = ctx->d_unit_ptr; S.cloud_ptr = ctx->d_cloud_ptr; S.entries = ctx->d_entries;
@@ -479,7 +479,7 @@ extern "C" {
 int cf_selftest_argmax(cf_ctx* ctx, const uint32_t* cands, int64_t n, uint32_t* out6) {
     if (!ctx || !out6 || n < 0 || (n && !cands)) return -22;
     CF_HIP(hipSetDevice(ctx->device));
-    Bufs B{ctx, {}};
+    cf_scratch B(ctx);
     uint32_t *d_c = nullptr, *d_o = nullptr;
     CF_TRY(B.get(&d_c, (size_t)5 * (size_t)std::max<int64_t>(n, 1), "selftest candidates"));
     CF_TRY(B.get(&d_o, 8, "selftest winner"));

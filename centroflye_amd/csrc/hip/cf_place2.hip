@@ -838,7 +838,7 @@ static int pl2_attempt(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, 
                        int slots_per_unit, int cmap_grow, std::vector<int64_t>& o_read, std::vector<int64_t>& o_pos, std::vector<int32_t>& o_s0, std::vector<int32_t>& o_s1) {
     const int64_t R = ctx->n_reads, N = ctx->n_entries, K = ctx->n_kmers;
     const std::vector<int64_t>& up = ctx->h_unit_ptr;
-    Bufs B{ctx, {}};
+    cf_scratch B(ctx);
     cf_pl2 S;
     std::memset(&S, 0, sizeof S);
     S.C.thr = (uint32_t)std::max(1, min_freq); S.C.min_unit = (uint32_t)std::max(0, min_unit);
@@ -947,7 +947,7 @@ static int pl2_attempt(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, 
         CF_HIP(hipMemsetAsync(d_pcnt, 0, (size_t)(K + 1) * 4, st));
         hipLaunchKernelGGL(cf_pl2_post_kernel, dim3((unsigned)g_reads), dim3(256), 0, st, S, (const uint8_t*)d_cls, stage_cls, R, 1, d_pcnt, d_post);
         // posting rows: as wide as the longest posting list needs (32 words hold 31 postings, 64 words 63; beyond: the CSR arrays)
-        Bufs PB{ctx, {}};
+        cf_scratch PB(ctx);
         int pw = 32;
         if (K) {
             const unsigned g_k = (unsigned)cf_grid_for(K * 16, 256, n_blocks * 4);
@@ -965,7 +965,7 @@ static int pl2_attempt(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, 
         CF_KERNEL_CHECK("placement postings");
         // regions of this stage's reads, then the seed.  The seed changes nothing but the scores: when it fills a region (a
         // late stage's few reads meet every position of a long contig) only this step is repeated with larger regions.
-        Bufs SB{ctx, {}};      // the stage's score memory
+        cf_scratch SB(ctx);      // the stage's score memory
         unsigned int h_ctl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int spu = slots_per_unit, tries = 0;; spu *= 4, ++tries) {
             if (tries == 6) return cf_fail(ctx, -34, "cf_place_reads: the seed of a stage kept overflowing the score regions");

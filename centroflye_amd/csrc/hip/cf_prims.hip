@@ -65,31 +65,23 @@ template <class TIn>
 static int scan_impl(cf_ctx* ctx, const TIn* d_in, int64_t* d_out, int64_t n, int64_t* total) {
     if (n <= 0) { if (total) *total = 0; return 0; }
     const int64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+    cf_scratch tmp(ctx);
     int64_t* d_sums = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_sums, (size_t)nb + 1, "scan block sums"));
+    CF_TRY(tmp.get(&d_sums, (size_t)nb + 1, "scan block sums"));
     hipLaunchKernelGGL((cf_scan_local<TIn>), dim3((unsigned)nb), dim3(SCAN_THREADS), 64, ctx->stream, d_in, d_out, d_sums, n);
     CF_KERNEL_CHECK("cf_scan_local");
-    int rc = 0;
     int64_t tot = 0;
+    if (total) *total = 0;
     if (nb > 1) {
-        rc = scan_impl<int64_t>(ctx, d_sums, d_sums, nb, &tot);
-        if (rc == 0) {
-            hipLaunchKernelGGL(cf_scan_add, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, ctx->stream, d_out, d_sums, n);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("launch of cf_scan_add: ") + hipGetErrorString(e));
-        }
+        CF_TRY(scan_impl<int64_t>(ctx, d_sums, d_sums, nb, &tot));
+        hipLaunchKernelGGL(cf_scan_add, dim3((unsigned)nb), dim3(SCAN_THREADS), 0, ctx->stream, d_out, d_sums, n);
+        CF_KERNEL_CHECK("cf_scan_add");
     } else {
-        hipError_t e = hipMemcpyAsync(&tot, d_sums, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("scan total copy: ") + hipGetErrorString(e));
+        CF_HIP(hipMemcpyAsync(&tot, d_sums, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
-    if (rc == 0) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("scan sync: ") + hipGetErrorString(e));
-    }
-    cf_release_t(ctx, d_sums, (size_t)nb + 1);
+    CF_HIP(hipStreamSynchronize(ctx->stream));
     if (total) *total = tot;
-    return rc;
+    return 0;
 }
 
 int cf_scan_exclusive_i64(cf_ctx* ctx, const int64_t* d_in, int64_t* d_out, int64_t n, int64_t* total) {
@@ -275,40 +267,29 @@ int cf_radix_sort_u64_any(cf_ctx* ctx, unsigned long long* d_keys, unsigned long
     const int ntiles = (int)((n + RX_TILE - 1) / RX_TILE);
     const int64_t nh = (int64_t)ntiles * RX_D, nc = (int64_t)cf_tile_digit_chunks(ntiles) * RX_D;
     const int grid = std::min(ntiles, std::max(1, ctx->n_cu) * 8);
+    cf_scratch tmp(ctx);
     uint32_t* d_hist = nullptr;
     int64_t* d_offs = nullptr;
     uint32_t* d_part = nullptr;
     int64_t* d_base = nullptr;
-    int rc = cf_alloc_t(ctx, &d_hist, (size_t)nh, "radix histogram");
-    if (rc == 0) rc = cf_alloc_t(ctx, &d_offs, (size_t)nh, "radix offsets");
-    if (rc == 0) rc = cf_alloc_t(ctx, &d_part, (size_t)nc, "radix column sums");
-    if (rc == 0) rc = cf_alloc_t(ctx, &d_base, (size_t)nc, "radix column bases");
+    CF_TRY(tmp.get(&d_hist, (size_t)nh, "radix histogram"));
+    CF_TRY(tmp.get(&d_offs, (size_t)nh, "radix offsets"));
+    CF_TRY(tmp.get(&d_part, (size_t)nc, "radix column sums"));
+    CF_TRY(tmp.get(&d_base, (size_t)nc, "radix column bases"));
     unsigned long long* src = d_keys;
     unsigned long long* dst = d_tmp;
-    for (int shift = 0; rc == 0 && shift < bits; shift += 8) {
+    for (int shift = 0; shift < bits; shift += 8) {
         hipLaunchKernelGGL(cf_radix_hist, dim3((unsigned)grid), dim3(CF_RX_THREADS), RX_D * 4, ctx->stream, (const unsigned long long*)src, d_hist, n, shift, ntiles);
-        rc = cf_tile_digit_offsets(ctx, d_hist, ntiles, RX_D, d_offs, nullptr, d_part, d_base);
-        if (rc) break;
+        CF_TRY(cf_tile_digit_offsets(ctx, d_hist, ntiles, RX_D, d_offs, nullptr, d_part, d_base));
         hipLaunchKernelGGL(cf_radix_scatter, dim3((unsigned)grid), dim3(CF_RX_THREADS), RX_SCATTER_LDS, ctx->stream, (const unsigned long long*)src, dst,
                            (const int64_t*)d_offs, n, shift, ntiles);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("radix launch: ") + hipGetErrorString(e)); break; }
+        CF_KERNEL_CHECK("cf_radix_scatter");
         std::swap(src, dst);
     }
-    if (rc == 0 && result) *result = src;
-    if (rc == 0 && src != d_keys && !result) {
-        hipError_t e = hipMemcpyAsync(d_keys, src, (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("radix copy back: ") + hipGetErrorString(e));
-    }
-    {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess && rc == 0) rc = cf_fail(ctx, -5, std::string("radix sync: ") + hipGetErrorString(e));
-    }
-    if (d_base) cf_release_t(ctx, d_base, (size_t)nc);
-    if (d_part) cf_release_t(ctx, d_part, (size_t)nc);
-    if (d_offs) cf_release_t(ctx, d_offs, (size_t)nh);
-    if (d_hist) cf_release_t(ctx, d_hist, (size_t)nh);
-    return rc;
+    if (result) *result = src;
+    else if (src != d_keys) CF_HIP(hipMemcpyAsync(d_keys, src, (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
 }
 
 // ------------------------------------------------------------------ radix sort of 16-byte records by 32-bit fields
@@ -382,32 +363,23 @@ int cf_radix_sort_rec16(cf_ctx* ctx, void* d_recs, void* d_tmp, int64_t n, const
     if (n <= 1) return 0;
     const int ntiles = (int)((n + RS_TILE - 1) / RS_TILE);
     const int64_t nh = (int64_t)ntiles * 256;
+    cf_scratch tmp(ctx);
     uint32_t* d_hist = nullptr;
     int64_t* d_offs = nullptr;
-    CF_TRY(cf_alloc_t(ctx, &d_hist, (size_t)nh, "radix histogram"));
-    int rc = cf_alloc_t(ctx, &d_offs, (size_t)nh, "radix offsets");
+    CF_TRY(tmp.get(&d_hist, (size_t)nh, "radix histogram"));
+    CF_TRY(tmp.get(&d_offs, (size_t)nh, "radix offsets"));
     cf_rec16* src = (cf_rec16*)d_recs;
     cf_rec16* dst = (cf_rec16*)d_tmp;
-    for (int f = 0; rc == 0 && f < n_fields; ++f) {
-        for (int shift = 0; rc == 0 && shift < bits[f]; shift += 8) {
+    for (int f = 0; f < n_fields; ++f) {
+        for (int shift = 0; shift < bits[f]; shift += 8) {
             hipLaunchKernelGGL(cf_rec16_hist, dim3((unsigned)ntiles), dim3(RS_THREADS), 256 * 4, ctx->stream, (const cf_rec16*)src, d_hist, n, words[f], shift, ntiles);
-            rc = cf_scan_exclusive_u32_to_i64(ctx, d_hist, d_offs, nh, nullptr);
-            if (rc) break;
+            CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_hist, d_offs, nh, nullptr));
             hipLaunchKernelGGL(cf_rec16_scatter, dim3((unsigned)ntiles), dim3(RS_THREADS), 256 * 8 + 4 * 256 * 4, ctx->stream, (const cf_rec16*)src, dst, (const int64_t*)d_offs, n, words[f], shift, ntiles);
-            hipError_t e = hipGetLastError();
-            if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("record sort launch: ") + hipGetErrorString(e)); break; }
+            CF_KERNEL_CHECK("cf_rec16_scatter");
             std::swap(src, dst);
         }
     }
-    if (rc == 0 && src != (cf_rec16*)d_recs) {
-        hipError_t e = hipMemcpyAsync(d_recs, src, (size_t)n * 16, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("record sort copy back: ") + hipGetErrorString(e));
-    }
-    if (rc == 0) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = cf_fail(ctx, -5, std::string("record sort sync: ") + hipGetErrorString(e));
-    }
-    if (d_offs) cf_release_t(ctx, d_offs, (size_t)nh);
-    cf_release_t(ctx, d_hist, (size_t)nh);
-    return rc;
+    if (src != (cf_rec16*)d_recs) CF_HIP(hipMemcpyAsync(d_recs, src, (size_t)n * 16, hipMemcpyDeviceToDevice, ctx->stream));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
 }

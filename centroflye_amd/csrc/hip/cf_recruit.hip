@@ -109,41 +109,30 @@ extern "C" int cf_rr_distances(cf_ctx* ctx, const uint8_t* unit, int32_t unit_le
     if (n_reads == 0) return 0;
     CF_HIP(hipSetDevice(ctx->device));
     const int64_t n_bytes = read_off[n_reads];
+    cf_scratch tmp(ctx);
     uint8_t* d_reads = nullptr; int64_t* d_off = nullptr; unsigned long long *d_peq = nullptr, *d_ticket = nullptr; int32_t* d_out = nullptr;
-    int rc = 0;
     std::vector<int32_t> h_out((size_t)2 * n_reads);
-    do {
-        if ((rc = cf_alloc_t(ctx, &d_reads, (size_t)std::max<int64_t>(n_bytes, 1), "rr reads"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_off, (size_t)n_reads + 1, "rr offsets"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_peq, peq.size(), "rr match masks"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_ticket, 1, "rr ticket"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_out, (size_t)2 * n_reads, "rr distances"))) break;
-        hipError_t e = hipSuccess;
-        if (n_bytes) e = hipMemcpyAsync(d_reads, reads, (size_t)n_bytes, hipMemcpyDefault, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_off, read_off, (size_t)(n_reads + 1) * 8, hipMemcpyDefault, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_peq, peq.data(), peq.size() * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_ticket, 0, 8, ctx->stream);
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev0, ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_rr_distances copy: ") + hipGetErrorString(e)); break; }
-        cf_rr_args A;
-        A.reads = d_reads; A.read_off = d_off; A.n_items = 2 * n_reads; A.peq = d_peq; A.m = unit_len; A.nb = (unit_len + 63) / 64;
-        A.k = threshold; A.ticket = d_ticket; A.out = d_out;
-        const int64_t waves = 2 * n_reads;
-        const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)std::max(1, ctx->n_cu) * 8));
-        hipLaunchKernelGGL(cf_rr_kernel, dim3((unsigned)grid), dim3(RR_THREADS), 0, ctx->stream, A);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d_out, h_out.size() * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_rr_kernel: ") + hipGetErrorString(e)); break; }
-        (void)hipEventElapsedTime(&ctx->times.rr_kernel_ms, ctx->ev0, ctx->ev1);
-    } while (0);
-    if (d_out) cf_release_t(ctx, d_out, (size_t)2 * n_reads);
-    if (d_ticket) cf_release_t(ctx, d_ticket, 1);
-    if (d_peq) cf_release_t(ctx, d_peq, peq.size());
-    if (d_off) cf_release_t(ctx, d_off, (size_t)n_reads + 1);
-    if (d_reads) cf_release_t(ctx, d_reads, (size_t)std::max<int64_t>(n_bytes, 1));
-    if (rc) return rc;
+    CF_TRY(tmp.get(&d_reads, (size_t)std::max<int64_t>(n_bytes, 1), "rr reads"));
+    CF_TRY(tmp.get(&d_off, (size_t)n_reads + 1, "rr offsets"));
+    CF_TRY(tmp.get(&d_peq, peq.size(), "rr match masks"));
+    CF_TRY(tmp.get(&d_ticket, 1, "rr ticket"));
+    CF_TRY(tmp.get(&d_out, (size_t)2 * n_reads, "rr distances"));
+    if (n_bytes) CF_HIP(hipMemcpyAsync(d_reads, reads, (size_t)n_bytes, hipMemcpyDefault, ctx->stream));
+    CF_HIP(hipMemcpyAsync(d_off, read_off, (size_t)(n_reads + 1) * 8, hipMemcpyDefault, ctx->stream));
+    CF_HIP(hipMemcpyAsync(d_peq, peq.data(), peq.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_ticket, 0, 8, ctx->stream));
+    CF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    cf_rr_args A;
+    A.reads = d_reads; A.read_off = d_off; A.n_items = 2 * n_reads; A.peq = d_peq; A.m = unit_len; A.nb = (unit_len + 63) / 64;
+    A.k = threshold; A.ticket = d_ticket; A.out = d_out;
+    const int64_t waves = 2 * n_reads;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)std::max(1, ctx->n_cu) * 8));
+    hipLaunchKernelGGL(cf_rr_kernel, dim3((unsigned)grid), dim3(RR_THREADS), 0, ctx->stream, A);
+    CF_KERNEL_CHECK("cf_rr_kernel");
+    CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    CF_HIP(hipMemcpyAsync(h_out.data(), d_out, h_out.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    (void)hipEventElapsedTime(&ctx->times.rr_kernel_ms, ctx->ev0, ctx->ev1);
     for (int64_t r = 0; r < n_reads; ++r) { dist_fwd[r] = h_out[(size_t)2 * r]; dist_rc[r] = h_out[(size_t)2 * r + 1]; }
     return 0;
 }

@@ -169,44 +169,34 @@ int cf_score_reads(cf_ctx* ctx, const int64_t* reads, int64_t n, const int64_t* 
     const int W = ctx->map_window > 0 ? ctx->map_window : CF_SCORE_WINDOW_DEFAULT;
     int64_t *d_q = nullptr, *d_lo = nullptr, *d_hi = nullptr, *d_pos = nullptr;
     int32_t *d_s0 = nullptr, *d_s1 = nullptr;
-    int rc = 0;
-    do {
-        if (reads) {
-            if ((rc = cf_alloc_t(ctx, &d_q, (size_t)n, "query reads"))) break;
-            if ((rc = cf_copy_h2d(ctx, d_q, reads, (size_t)n * 8))) break;
-        }
-        if (lo) {
-            if ((rc = cf_alloc_t(ctx, &d_lo, (size_t)n, "first starts"))) break;
-            if ((rc = cf_copy_h2d(ctx, d_lo, lo, (size_t)n * 8))) break;
-        }
-        if (hi) {
-            if ((rc = cf_alloc_t(ctx, &d_hi, (size_t)n, "last starts"))) break;
-            if ((rc = cf_copy_h2d(ctx, d_hi, hi, (size_t)n * 8))) break;
-        }
-        if ((rc = cf_alloc_t(ctx, &d_pos, (size_t)n, "scored positions"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_s0, (size_t)n, "scored s0"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_s1, (size_t)n, "scored s1"))) break;
-        const int grid = (int)std::min<int64_t>(n, (int64_t)std::max(1, ctx->n_cu) * 64);
-        hipLaunchKernelGGL(cf_score_kernel, dim3((unsigned)grid), dim3(CF_SCORE_THREADS), (size_t)W * 12, ctx->stream, (const int64_t*)d_q, n,
-                           (const int64_t*)d_lo, (const int64_t*)d_hi, (const int64_t*)ctx->d_unit_ptr, (const int64_t*)ctx->d_cloud_ptr,
-                           (const int32_t*)ctx->d_entries, (const int64_t*)ctx->d_exact_ptr, (const int32_t*)ctx->d_exact_pos,
-                           ctx->contig_max_pos, W, min_unit, min_inters, d_pos, d_s0, d_s1);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(ctx->ev1, ctx->stream);
-        if (e == hipSuccess) e = hipEventSynchronize(ctx->ev1);
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_score_reads: ") + hipGetErrorString(e)); break; }
-        (void)hipEventElapsedTime(&ctx->score_ms, ctx->ev0, ctx->ev1);
-        if ((rc = cf_copy_d2h(ctx, out_pos, d_pos, (size_t)n * 8))) break;
-        if ((rc = cf_copy_d2h(ctx, out_s0, d_s0, (size_t)n * 4))) break;
-        if ((rc = cf_copy_d2h(ctx, out_s1, d_s1, (size_t)n * 4))) break;
-    } while (0);
-    if (d_s1) cf_release_t(ctx, d_s1, (size_t)n);
-    if (d_s0) cf_release_t(ctx, d_s0, (size_t)n);
-    if (d_pos) cf_release_t(ctx, d_pos, (size_t)n);
-    if (d_hi) cf_release_t(ctx, d_hi, (size_t)n);
-    if (d_lo) cf_release_t(ctx, d_lo, (size_t)n);
-    if (d_q) cf_release_t(ctx, d_q, (size_t)n);
-    return rc;
+    cf_scratch tmp(ctx);
+    if (reads) {
+        CF_TRY(tmp.get(&d_q, (size_t)n, "query reads"));
+        CF_TRY(cf_copy_h2d(ctx, d_q, reads, (size_t)n * 8));
+    }
+    if (lo) {
+        CF_TRY(tmp.get(&d_lo, (size_t)n, "first starts"));
+        CF_TRY(cf_copy_h2d(ctx, d_lo, lo, (size_t)n * 8));
+    }
+    if (hi) {
+        CF_TRY(tmp.get(&d_hi, (size_t)n, "last starts"));
+        CF_TRY(cf_copy_h2d(ctx, d_hi, hi, (size_t)n * 8));
+    }
+    CF_TRY(tmp.get(&d_pos, (size_t)n, "scored positions"));
+    CF_TRY(tmp.get(&d_s0, (size_t)n, "scored s0"));
+    CF_TRY(tmp.get(&d_s1, (size_t)n, "scored s1"));
+    const int grid = (int)std::min<int64_t>(n, (int64_t)std::max(1, ctx->n_cu) * 64);
+    hipLaunchKernelGGL(cf_score_kernel, dim3((unsigned)grid), dim3(CF_SCORE_THREADS), (size_t)W * 12, ctx->stream, (const int64_t*)d_q, n,
+                       (const int64_t*)d_lo, (const int64_t*)d_hi, (const int64_t*)ctx->d_unit_ptr, (const int64_t*)ctx->d_cloud_ptr,
+                       (const int32_t*)ctx->d_entries, (const int64_t*)ctx->d_exact_ptr, (const int32_t*)ctx->d_exact_pos,
+                       ctx->contig_max_pos, W, min_unit, min_inters, d_pos, d_s0, d_s1);
+    CF_KERNEL_CHECK("cf_score_kernel");
+    CF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    CF_HIP(hipEventSynchronize(ctx->ev1));
+    (void)hipEventElapsedTime(&ctx->score_ms, ctx->ev0, ctx->ev1);
+    CF_TRY(cf_copy_d2h(ctx, out_pos, d_pos, (size_t)n * 8));
+    CF_TRY(cf_copy_d2h(ctx, out_s0, d_s0, (size_t)n * 4));
+    return cf_copy_d2h(ctx, out_s1, d_s1, (size_t)n * 4);
 }
 
 int cf_contig_spread(cf_ctx* ctx, int64_t max_npos, int32_t* ranks, int64_t cap, int64_t* n_out) {
@@ -223,28 +213,21 @@ int cf_contig_spread(cf_ctx* ctx, int64_t max_npos, int32_t* ranks, int64_t cap,
     int64_t* d_idx = nullptr;
     int32_t* d_ranks = nullptr;
     int64_t total = 0;
-    int rc = 0;
-    do {
-        if ((rc = cf_alloc_t(ctx, &d_flag, (size_t)K, "spread flags"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_idx, (size_t)K, "spread offsets"))) break;
-        // a frequent k-mer has at least one position, the other ranks have an empty row: max_npos < 0 asks for every frequent one
-        hipLaunchKernelGGL(cf_spread_flag_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const int64_t*)ctx->d_contig_ptr, K,
-                           std::max<int64_t>(0, max_npos), d_flag);
-        if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_flag, d_idx, K, &total))) break;
-        *n_out = total;
-        if (!ranks || total == 0) break;      // the count alone
-        if (cap < total) { rc = cf_fail(ctx, -22, "cf_contig_spread: " + std::to_string(total) + " ranks do not fit the buffer"); break; }
-        if ((rc = cf_alloc_t(ctx, &d_ranks, (size_t)total, "spread ranks"))) break;
-        hipLaunchKernelGGL(cf_spread_fill_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const uint32_t*)d_flag, (const int64_t*)d_idx,
-                           K, d_ranks);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_contig_spread: ") + hipGetErrorString(e)); break; }
-        if ((rc = cf_copy_d2h(ctx, ranks, d_ranks, (size_t)total * 4))) break;
-    } while (0);
-    if (d_ranks) cf_release_t(ctx, d_ranks, (size_t)total);
-    if (d_idx) cf_release_t(ctx, d_idx, (size_t)K);
-    if (d_flag) cf_release_t(ctx, d_flag, (size_t)K);
-    return rc;
+    cf_scratch tmp(ctx);
+    CF_TRY(tmp.get(&d_flag, (size_t)K, "spread flags"));
+    CF_TRY(tmp.get(&d_idx, (size_t)K, "spread offsets"));
+    // a frequent k-mer has at least one position, the other ranks have an empty row: max_npos < 0 asks for every frequent one
+    hipLaunchKernelGGL(cf_spread_flag_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const int64_t*)ctx->d_contig_ptr, K,
+                       std::max<int64_t>(0, max_npos), d_flag);
+    CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_flag, d_idx, K, &total));
+    *n_out = total;
+    if (!ranks || total == 0) return 0;      // the count alone
+    if (cap < total) return cf_fail(ctx, -22, "cf_contig_spread: " + std::to_string(total) + " ranks do not fit the buffer");
+    CF_TRY(tmp.get(&d_ranks, (size_t)total, "spread ranks"));
+    hipLaunchKernelGGL(cf_spread_fill_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const uint32_t*)d_flag, (const int64_t*)d_idx,
+                       K, d_ranks);
+    CF_KERNEL_CHECK("cf_spread_fill_kernel");
+    return cf_copy_d2h(ctx, ranks, d_ranks, (size_t)total * 4);
 }
 
 int cf_contig_exact_info(cf_ctx* ctx, int64_t* n_exact_pairs, float* score_ms) {

@@ -379,167 +379,127 @@ static int td_batch(cf_ctx* ctx, const uint8_t* reads, const int64_t* read_off, 
     int32_t *d_bins = nullptr, *d_hook_pos = nullptr;
     cf_tandem_read* d_out = nullptr;
     int64_t n_diff = 0, n_hook = 0;
-    size_t diff_alloc = 0, hook_alloc = 0;
-    int rc = 0;
-#define TD_CHECK(what)                                                                                                                   \
-    {                                                                                                                                    \
-        hipError_t e_ = hipGetLastError();                                                                                               \
-        if (e_ != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_tandem_scan: ") + what + ": " + hipGetErrorString(e_)); break; }   \
+    cf_scratch tmp(ctx);
+    CF_TRY(tmp.get(&d_bases, (size_t)n_bytes + 1, "tandem bases"));
+    CF_TRY(tmp.get(&d_off, (size_t)nb + 1, "tandem read offsets"));
+    CF_TRY(tmp.get(&d_win, (size_t)nb + 1, "tandem window offsets"));
+    CF_TRY(tmp.get(&d_seg, (size_t)nb + 1, "tandem read segments"));
+    CF_TRY(tmp.get(&d_exotic, (size_t)nb + 1, "tandem exotic flags"));
+    CF_TRY(tmp.get(&d_best, (size_t)nb * 3 + 1, "tandem maxima"));
+    CF_TRY(tmp.get(&d_bins, (size_t)nb * 2 + 1, "tandem bins"));
+    CF_TRY(tmp.get(&d_out, (size_t)nb + 1, "tandem results"));
+    CF_TRY(tmp.get(&d_hook_first, (size_t)nb + 1, "tandem hook runs"));
+    CF_TRY(tmp.get(&d_hook_ptr, (size_t)nb + 1, "tandem hook offsets"));
+    CF_TRY(tmp.get(&d_hook_n, (size_t)nb + 1, "tandem hook counts"));
+    if (L.mode == 1) {
+        CF_TRY(tmp.get(&d_keys, (size_t)N + 1, "tandem keys"));
+        CF_TRY(tmp.get(&d_tmp, (size_t)N + 1, "tandem keys"));
+    } else {
+        CF_TRY(tmp.get(&d_recs, (size_t)N + 1, "tandem records"));
+        CF_TRY(tmp.get(&d_rtmp, (size_t)N + 1, "tandem records"));
     }
-#define TD_HIP(expr)                                                                                                                     \
-    {                                                                                                                                    \
-        hipError_t e_ = (expr);                                                                                                          \
-        if (e_ != hipSuccess) { rc = cf_fail(ctx, -5, std::string("cf_tandem_scan: " #expr ": ") + hipGetErrorString(e_)); break; }      \
-    }
-    do {
-        if ((rc = cf_alloc_t(ctx, &d_bases, (size_t)n_bytes + 1, "tandem bases"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_off, (size_t)nb + 1, "tandem read offsets"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_win, (size_t)nb + 1, "tandem window offsets"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_seg, (size_t)nb + 1, "tandem read segments"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_exotic, (size_t)nb + 1, "tandem exotic flags"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_best, (size_t)nb * 3 + 1, "tandem maxima"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_bins, (size_t)nb * 2 + 1, "tandem bins"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_out, (size_t)nb + 1, "tandem results"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_hook_first, (size_t)nb + 1, "tandem hook runs"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_hook_ptr, (size_t)nb + 1, "tandem hook offsets"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_hook_n, (size_t)nb + 1, "tandem hook counts"))) break;
-        if (L.mode == 1) {
-            if ((rc = cf_alloc_t(ctx, &d_keys, (size_t)N + 1, "tandem keys"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_tmp, (size_t)N + 1, "tandem keys"))) break;
-        } else {
-            if ((rc = cf_alloc_t(ctx, &d_recs, (size_t)N + 1, "tandem records"))) break;
-            if ((rc = cf_alloc_t(ctx, &d_rtmp, (size_t)N + 1, "tandem records"))) break;
-        }
-        if ((rc = cf_alloc_t(ctx, &d_is_diff, (size_t)N + 1, "tandem flags"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_is_rep, (size_t)N + 1, "tandem flags"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_pre_diff, (size_t)N + 1, "tandem prefixes"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_pre_rep, (size_t)N + 1, "tandem prefixes"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_pre_in, (size_t)N + 1, "tandem prefixes"))) break;
-        if (n_bytes > 0 && (rc = cf_copy_h2d(ctx, d_bases, reads + base, (size_t)n_bytes))) break;
-        if ((rc = cf_copy_h2d(ctx, d_off, off.data(), ((size_t)nb + 1) * 8))) break;
-        if ((rc = cf_copy_h2d(ctx, d_win, win.data(), ((size_t)nb + 1) * 8))) break;
-        TD_HIP(hipMemsetAsync(d_exotic, 0, ((size_t)nb + 1) * 4, ctx->stream));
-        TD_HIP(hipMemsetAsync(d_best, 0, ((size_t)nb * 3 + 1) * 8, ctx->stream));
-        unsigned long long *d_first = d_best, *d_last = d_best + nb, *d_hook = d_best + 2 * nb;
+    CF_TRY(tmp.get(&d_is_diff, (size_t)N + 1, "tandem flags"));
+    CF_TRY(tmp.get(&d_is_rep, (size_t)N + 1, "tandem flags"));
+    CF_TRY(tmp.get(&d_pre_diff, (size_t)N + 1, "tandem prefixes"));
+    CF_TRY(tmp.get(&d_pre_rep, (size_t)N + 1, "tandem prefixes"));
+    CF_TRY(tmp.get(&d_pre_in, (size_t)N + 1, "tandem prefixes"));
+    if (n_bytes > 0) CF_TRY(cf_copy_h2d(ctx, d_bases, reads + base, (size_t)n_bytes));
+    CF_TRY(cf_copy_h2d(ctx, d_off, off.data(), ((size_t)nb + 1) * 8));
+    CF_TRY(cf_copy_h2d(ctx, d_win, win.data(), ((size_t)nb + 1) * 8));
+    CF_HIP(hipMemsetAsync(d_exotic, 0, ((size_t)nb + 1) * 4, ctx->stream));
+    CF_HIP(hipMemsetAsync(d_best, 0, ((size_t)nb * 3 + 1) * 8, ctx->stream));
+    unsigned long long *d_first = d_best, *d_last = d_best + nb, *d_hook = d_best + 2 * nb;
 
-        // records
-        TD_HIP(hipEventRecord(ev.e[0], ctx->stream));
-        if (N > 0) {
-            hipLaunchKernelGGL(cf_td_records_kernel, dim3((unsigned)gN), dim3(CF_TD_THREADS), 0, ctx->stream, (const uint8_t*)d_bases, (const int64_t*)d_off,
-                               (const int64_t*)d_win, nb, N, k, L.mode, L.code_bits, L.read_bits, L.pos_shift, d_keys, d_recs, d_exotic);
-            TD_CHECK("records");
+    // records
+    CF_HIP(hipEventRecord(ev.e[0], ctx->stream));
+    if (N > 0) {
+        hipLaunchKernelGGL(cf_td_records_kernel, dim3((unsigned)gN), dim3(CF_TD_THREADS), 0, ctx->stream, (const uint8_t*)d_bases, (const int64_t*)d_off,
+                           (const int64_t*)d_win, nb, N, k, L.mode, L.code_bits, L.read_bits, L.pos_shift, d_keys, d_recs, d_exotic);
+        CF_KERNEL_CHECK("cf_td_records_kernel");
+    }
+    CF_HIP(hipEventRecord(ev.e[1], ctx->stream));
+    // sort by (read, code); the position keeps its order
+    cf_td_view v{};
+    v.mode = L.mode; v.code_bits = L.code_bits; v.read_bits = L.read_bits; v.pos_shift = L.pos_shift; v.n_batch = (uint32_t)nb;
+    if (L.mode == 1) {
+        unsigned long long* sorted = d_keys;
+        CF_TRY(cf_radix_sort_u64_any(ctx, d_keys, d_tmp, N, L.code_bits + L.read_bits + 1, &sorted));
+        v.keys = sorted;
+    } else {
+        int words[3], bits[3], nf = 0;
+        words[nf] = 0; bits[nf++] = std::min(32, L.code_bits);
+        if (L.code_bits > 32) { words[nf] = 1; bits[nf++] = L.code_bits - 32; }
+        words[nf] = 2; bits[nf++] = td_bits((uint64_t)nb);      // (the value nb marks an invalid record)
+        CF_TRY(cf_radix_sort_rec16(ctx, d_recs, d_rtmp, N, words, bits, nf));
+        v.recs = d_recs;
+    }
+    CF_HIP(hipEventRecord(ev.e[2], ctx->stream));
+    // runs, per-read segments, the distances
+    hipLaunchKernelGGL(cf_td_runs_kernel, dim3((unsigned)gN), dim3(CF_TD_THREADS), 0, ctx->stream, v, N, d_is_diff, d_is_rep);
+    hipLaunchKernelGGL(cf_td_segments_kernel, dim3((unsigned)gR), dim3(CF_TD_THREADS), 0, ctx->stream, v, N, nb, d_seg);
+    CF_KERNEL_CHECK("cf_td_runs_kernel / cf_td_segments_kernel");
+    CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_is_diff, d_pre_diff, N + 1, &n_diff));
+    CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_is_rep, d_pre_rep, N + 1, nullptr));
+    CF_TRY(tmp.get(&d_dkeys, (size_t)n_diff + 1, "tandem distances"));
+    CF_TRY(tmp.get(&d_dtmp, (size_t)n_diff + 1, "tandem distances"));
+    if (n_diff > 0) {
+        hipLaunchKernelGGL(cf_td_diffs_kernel, dim3((unsigned)gN), dim3(CF_TD_THREADS), 0, ctx->stream, v, N, (const uint32_t*)d_is_diff,
+                           (const int64_t*)d_pre_diff, dshift, d_dkeys);
+        CF_KERNEL_CHECK("cf_td_diffs_kernel");
+    }
+    CF_HIP(hipEventRecord(ev.e[3], ctx->stream));
+    unsigned long long* conv = d_dkeys;
+    CF_TRY(cf_radix_sort_u64_any(ctx, d_dkeys, d_dtmp, n_diff, dshift + L.read_bits, &conv));
+    CF_HIP(hipEventRecord(ev.e[4], ctx->stream));
+    // windows
+    if (n_diff > 0) {
+        const int gD = cf_grid_for(n_diff, CF_TD_THREADS, maxb);
+        hipLaunchKernelGGL(cf_td_windows_kernel, dim3((unsigned)gD), dim3(CF_TD_THREADS), 0, ctx->stream, (const unsigned long long*)conv, n_diff, dshift,
+                           (const int64_t*)d_seg, (const int64_t*)d_pre_diff, bin2, d_first, d_last);
+    }
+    hipLaunchKernelGGL(cf_td_finish_kernel, dim3((unsigned)gR), dim3(CF_TD_THREADS), 0, ctx->stream, (const unsigned long long*)conv, dshift,
+                       (const int64_t*)d_seg, (const int64_t*)d_pre_diff, (const int64_t*)d_pre_rep, (const uint32_t*)d_exotic,
+                       (const unsigned long long*)d_first, (const unsigned long long*)d_last, nb, bin2, d_out, d_bins);
+    CF_KERNEL_CHECK("cf_td_windows_kernel / cf_td_finish_kernel");
+    CF_HIP(hipEventRecord(ev.e[5], ctx->stream));
+    // hook
+    uint32_t* d_in_bin = d_is_diff;      // written in place: entry i depends on is_diff[i] alone, and nothing reads is_diff afterwards
+    hipLaunchKernelGGL(cf_td_inbin_kernel, dim3((unsigned)gN), dim3(CF_TD_THREADS), 0, ctx->stream, v, N, (const uint32_t*)d_is_diff, (const int32_t*)d_bins, d_in_bin);
+    CF_KERNEL_CHECK("cf_td_inbin_kernel");
+    CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_in_bin, d_pre_in, N + 1, nullptr));
+    if (N > 0) {
+        hipLaunchKernelGGL(cf_td_hook_best_kernel, dim3((unsigned)cf_grid_for(N, CF_TD_THREADS, maxb)), dim3(CF_TD_THREADS), 0, ctx->stream, v, N,
+                           (const uint32_t*)d_is_rep, (const int64_t*)d_seg, (const int64_t*)d_pre_in, d_hook);
+    }
+    hipLaunchKernelGGL(cf_td_hook_pick_kernel, dim3((unsigned)gR), dim3(CF_TD_THREADS), 0, ctx->stream, v, (const uint8_t*)d_bases, (const int64_t*)d_off,
+                       (const int64_t*)d_seg, (const unsigned long long*)d_hook, nb, k, d_out, d_hook_first, d_hook_n);
+    CF_KERNEL_CHECK("cf_td_hook_best_kernel / cf_td_hook_pick_kernel");
+    CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_hook_n, d_hook_ptr, nb + 1, &n_hook));
+    CF_TRY(tmp.get(&d_hook_pos, (size_t)n_hook + 1, "tandem hook positions"));
+    if (n_hook > 0) {
+        hipLaunchKernelGGL(cf_td_hook_copy_kernel, dim3((unsigned)cf_grid_for(n_hook, CF_TD_THREADS, maxb)), dim3(CF_TD_THREADS), 0, ctx->stream, v,
+                           (const int64_t*)d_hook_first, (const int64_t*)d_hook_ptr, nb, n_hook, d_hook_pos);
+        CF_KERNEL_CHECK("cf_td_hook_copy_kernel");
+    }
+    CF_HIP(hipEventRecord(ev.e[6], ctx->stream));
+    CF_HIP(hipEventSynchronize(ev.e[6]));
+    {
+        // records | sort | runs and distances | sort | windows | hook
+        static const int phase_of[6] = {0, 1, 2, 1, 3, 4};
+        for (int i = 0; i < 6; ++i) {
+            float t = 0.f;
+            (void)hipEventElapsedTime(&t, ev.e[i], ev.e[i + 1]);
+            phase_ms[phase_of[i]] += t;
         }
-        TD_HIP(hipEventRecord(ev.e[1], ctx->stream));
-        // sort by (read, code); the position keeps its order
-        cf_td_view v{};
-        v.mode = L.mode; v.code_bits = L.code_bits; v.read_bits = L.read_bits; v.pos_shift = L.pos_shift; v.n_batch = (uint32_t)nb;
-        if (L.mode == 1) {
-            unsigned long long* sorted = d_keys;
-            if ((rc = cf_radix_sort_u64_any(ctx, d_keys, d_tmp, N, L.code_bits + L.read_bits + 1, &sorted))) break;
-            v.keys = sorted;
-        } else {
-            int words[3], bits[3], nf = 0;
-            words[nf] = 0; bits[nf++] = std::min(32, L.code_bits);
-            if (L.code_bits > 32) { words[nf] = 1; bits[nf++] = L.code_bits - 32; }
-            words[nf] = 2; bits[nf++] = td_bits((uint64_t)nb);      // (the value nb marks an invalid record)
-            if ((rc = cf_radix_sort_rec16(ctx, d_recs, d_rtmp, N, words, bits, nf))) break;
-            v.recs = d_recs;
-        }
-        TD_HIP(hipEventRecord(ev.e[2], ctx->stream));
-        // runs, per-read segments, the distances
-        hipLaunchKernelGGL(cf_td_runs_kernel, dim3((unsigned)gN), dim3(CF_TD_THREADS), 0, ctx->stream, v, N, d_is_diff, d_is_rep);
-        hipLaunchKernelGGL(cf_td_segments_kernel, dim3((unsigned)gR), dim3(CF_TD_THREADS), 0, ctx->stream, v, N, nb, d_seg);
-        TD_CHECK("runs");
-        if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_is_diff, d_pre_diff, N + 1, &n_diff))) break;
-        if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_is_rep, d_pre_rep, N + 1, nullptr))) break;
-        diff_alloc = (size_t)n_diff + 1;
-        if ((rc = cf_alloc_t(ctx, &d_dkeys, diff_alloc, "tandem distances"))) break;
-        if ((rc = cf_alloc_t(ctx, &d_dtmp, diff_alloc, "tandem distances"))) break;
-        if (n_diff > 0) {
-            hipLaunchKernelGGL(cf_td_diffs_kernel, dim3((unsigned)gN), dim3(CF_TD_THREADS), 0, ctx->stream, v, N, (const uint32_t*)d_is_diff,
-                               (const int64_t*)d_pre_diff, dshift, d_dkeys);
-            TD_CHECK("distances");
-        }
-        TD_HIP(hipEventRecord(ev.e[3], ctx->stream));
-        unsigned long long* conv = d_dkeys;
-        if ((rc = cf_radix_sort_u64_any(ctx, d_dkeys, d_dtmp, n_diff, dshift + L.read_bits, &conv))) break;
-        TD_HIP(hipEventRecord(ev.e[4], ctx->stream));
-        // windows
-        if (n_diff > 0) {
-            const int gD = cf_grid_for(n_diff, CF_TD_THREADS, maxb);
-            hipLaunchKernelGGL(cf_td_windows_kernel, dim3((unsigned)gD), dim3(CF_TD_THREADS), 0, ctx->stream, (const unsigned long long*)conv, n_diff, dshift,
-                               (const int64_t*)d_seg, (const int64_t*)d_pre_diff, bin2, d_first, d_last);
-        }
-        hipLaunchKernelGGL(cf_td_finish_kernel, dim3((unsigned)gR), dim3(CF_TD_THREADS), 0, ctx->stream, (const unsigned long long*)conv, dshift,
-                           (const int64_t*)d_seg, (const int64_t*)d_pre_diff, (const int64_t*)d_pre_rep, (const uint32_t*)d_exotic,
-                           (const unsigned long long*)d_first, (const unsigned long long*)d_last, nb, bin2, d_out, d_bins);
-        TD_CHECK("windows");
-        TD_HIP(hipEventRecord(ev.e[5], ctx->stream));
-        // hook
-        uint32_t* d_in_bin = d_is_diff;      // written in place: entry i depends on is_diff[i] alone, and nothing reads is_diff afterwards
-        hipLaunchKernelGGL(cf_td_inbin_kernel, dim3((unsigned)gN), dim3(CF_TD_THREADS), 0, ctx->stream, v, N, (const uint32_t*)d_is_diff, (const int32_t*)d_bins, d_in_bin);
-        TD_CHECK("hook flags");
-        if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_in_bin, d_pre_in, N + 1, nullptr))) break;
-        if (N > 0) {
-            hipLaunchKernelGGL(cf_td_hook_best_kernel, dim3((unsigned)cf_grid_for(N, CF_TD_THREADS, maxb)), dim3(CF_TD_THREADS), 0, ctx->stream, v, N,
-                               (const uint32_t*)d_is_rep, (const int64_t*)d_seg, (const int64_t*)d_pre_in, d_hook);
-        }
-        hipLaunchKernelGGL(cf_td_hook_pick_kernel, dim3((unsigned)gR), dim3(CF_TD_THREADS), 0, ctx->stream, v, (const uint8_t*)d_bases, (const int64_t*)d_off,
-                           (const int64_t*)d_seg, (const unsigned long long*)d_hook, nb, k, d_out, d_hook_first, d_hook_n);
-        TD_CHECK("hook");
-        if ((rc = cf_scan_exclusive_u32_to_i64(ctx, d_hook_n, d_hook_ptr, nb + 1, &n_hook))) break;
-        hook_alloc = (size_t)n_hook + 1;
-        if ((rc = cf_alloc_t(ctx, &d_hook_pos, hook_alloc, "tandem hook positions"))) break;
-        if (n_hook > 0) {
-            hipLaunchKernelGGL(cf_td_hook_copy_kernel, dim3((unsigned)cf_grid_for(n_hook, CF_TD_THREADS, maxb)), dim3(CF_TD_THREADS), 0, ctx->stream, v,
-                               (const int64_t*)d_hook_first, (const int64_t*)d_hook_ptr, nb, n_hook, d_hook_pos);
-            TD_CHECK("hook positions");
-        }
-        TD_HIP(hipEventRecord(ev.e[6], ctx->stream));
-        TD_HIP(hipEventSynchronize(ev.e[6]));
-        {
-            // records | sort | runs and distances | sort | windows | hook
-            static const int phase_of[6] = {0, 1, 2, 1, 3, 4};
-            for (int i = 0; i < 6; ++i) {
-                float t = 0.f;
-                (void)hipEventElapsedTime(&t, ev.e[i], ev.e[i + 1]);
-                phase_ms[phase_of[i]] += t;
-            }
-        }
-        if ((rc = cf_copy_d2h(ctx, out + r0, d_out, (size_t)nb * sizeof(cf_tandem_read)))) break;
-        const size_t h0 = hook_pos.size();
-        std::vector<int64_t> ptr((size_t)nb + 1);
-        if ((rc = cf_copy_d2h(ctx, ptr.data(), d_hook_ptr, ((size_t)nb + 1) * 8))) break;
-        hook_pos.resize(h0 + (size_t)n_hook);
-        if (n_hook > 0 && (rc = cf_copy_d2h(ctx, hook_pos.data() + h0, d_hook_pos, (size_t)n_hook * 4))) break;
-        for (int64_t i = 1; i <= nb; ++i) hook_ptr.push_back((int64_t)h0 + ptr[(size_t)i]);
-    } while (0);
-#undef TD_CHECK
-#undef TD_HIP
-    if (d_hook_pos) cf_release_t(ctx, d_hook_pos, hook_alloc);
-    if (d_dtmp) cf_release_t(ctx, d_dtmp, diff_alloc);
-    if (d_dkeys) cf_release_t(ctx, d_dkeys, diff_alloc);
-    if (d_pre_in) cf_release_t(ctx, d_pre_in, (size_t)N + 1);
-    if (d_pre_rep) cf_release_t(ctx, d_pre_rep, (size_t)N + 1);
-    if (d_pre_diff) cf_release_t(ctx, d_pre_diff, (size_t)N + 1);
-    if (d_is_rep) cf_release_t(ctx, d_is_rep, (size_t)N + 1);
-    if (d_is_diff) cf_release_t(ctx, d_is_diff, (size_t)N + 1);
-    if (d_rtmp) cf_release_t(ctx, d_rtmp, (size_t)N + 1);
-    if (d_recs) cf_release_t(ctx, d_recs, (size_t)N + 1);
-    if (d_tmp) cf_release_t(ctx, d_tmp, (size_t)N + 1);
-    if (d_keys) cf_release_t(ctx, d_keys, (size_t)N + 1);
-    if (d_hook_n) cf_release_t(ctx, d_hook_n, (size_t)nb + 1);
-    if (d_hook_ptr) cf_release_t(ctx, d_hook_ptr, (size_t)nb + 1);
-    if (d_hook_first) cf_release_t(ctx, d_hook_first, (size_t)nb + 1);
-    if (d_out) cf_release_t(ctx, d_out, (size_t)nb + 1);
-    if (d_bins) cf_release_t(ctx, d_bins, (size_t)nb * 2 + 1);
-    if (d_best) cf_release_t(ctx, d_best, (size_t)nb * 3 + 1);
-    if (d_exotic) cf_release_t(ctx, d_exotic, (size_t)nb + 1);
-    if (d_seg) cf_release_t(ctx, d_seg, (size_t)nb + 1);
-    if (d_win) cf_release_t(ctx, d_win, (size_t)nb + 1);
-    if (d_off) cf_release_t(ctx, d_off, (size_t)nb + 1);
-    if (d_bases) cf_release_t(ctx, d_bases, (size_t)n_bytes + 1);
-    return rc;
+    }
+    CF_TRY(cf_copy_d2h(ctx, out + r0, d_out, (size_t)nb * sizeof(cf_tandem_read)));
+    const size_t h0 = hook_pos.size();
+    std::vector<int64_t> ptr((size_t)nb + 1);
+    CF_TRY(cf_copy_d2h(ctx, ptr.data(), d_hook_ptr, ((size_t)nb + 1) * 8));
+    hook_pos.resize(h0 + (size_t)n_hook);
+    if (n_hook > 0) CF_TRY(cf_copy_d2h(ctx, hook_pos.data() + h0, d_hook_pos, (size_t)n_hook * 4));
+    for (int64_t i = 1; i <= nb; ++i) hook_ptr.push_back((int64_t)h0 + ptr[(size_t)i]);
+    return 0;
 }
 
 extern "C" {
@@ -600,13 +560,12 @@ int cf_tandem_scan(cf_ctx* ctx, const uint8_t* reads, const int64_t* read_off, i
     std::vector<int32_t> hook_pos;
     cf_tandem_shape shape{};
     shape.n_reads = n_reads;
-    int rc = 0;
     for (const td_range& b : batches) {
         float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
         hipEvent_t start = ctx->ev0, stop = ctx->ev1;
         CF_HIP(hipEventRecord(start, ctx->stream));
-        rc = td_batch(ctx, reads, read_off, b.r0, b.r1, k, 2 * (int64_t)bin_size, b.L, ev, out, hook_ptr, hook_pos, &shape.n_records, ms);
-        if (rc) break;
+        // (on a failure the results of the call before stay)
+        CF_TRY(td_batch(ctx, reads, read_off, b.r0, b.r1, k, 2 * (int64_t)bin_size, b.L, ev, out, hook_ptr, hook_pos, &shape.n_records, ms));
         CF_HIP(hipEventRecord(stop, ctx->stream));
         CF_HIP(hipEventSynchronize(stop));
         float all = 0.f;
@@ -618,7 +577,6 @@ int cf_tandem_scan(cf_ctx* ctx, const uint8_t* reads, const int64_t* read_off, i
         ++shape.n_batches;
         if (b.L.mode == 1) ++shape.n_key_batches;
     }
-    if (rc) return rc;      // (the results of the call before stay)
     ctx->tandem_hook_ptr.swap(hook_ptr);
     ctx->tandem_hook_pos.swap(hook_pos);
     ctx->tandem_last = shape;

@@ -17,7 +17,13 @@ namespace cfemu {
 size_t g_bytes_live = 0;
 static std::map<void*, size_t> g_allocs;
 
+// test hook (tests/test_emu_scratch.py): from the n-th hipMalloc after this call on, EVERY hipMalloc fails (cf_alloc flushes its
+// pools and tries once more: one failure alone would not reach the caller); 0 switches the hook off and restarts the count
+static long g_fail_from = 0, g_n_allocs = 0;
+extern "C" void cfemu_fail_allocs_from(long n) { g_fail_from = n; g_n_allocs = 0; }
+
 void* dev_alloc(size_t n) {
+    if (g_fail_from > 0 && ++g_n_allocs >= g_fail_from) return nullptr;
     if (n == 0) n = 1;
     void* p = nullptr;
     if (posix_memalign(&p, 256, n) != 0) return nullptr;
