@@ -3,11 +3,14 @@
 (unit, read, threshold) cases with the distances the REFERENCE's own code returns — vendored edlib compiled from
 /root/reference by oracle/ref/Makefile into oracle/_ref/librr_ref.so (build container only).
 
-    python tests/golden/make_golden_rr.py          # writes rr_vectors.json and rr_ref_random.json
+    python tests/golden/make_golden_rr.py          # writes rr_vectors.json, rr_ref_random.json and rr_limits.json
     python tests/golden/make_golden_rr.py --check
 
 rr_ref_random.json: the reference's distance for each of the seeded random cases of tests/test_read_recruitment.py
 (random_cases), so that the test needs no reference library.
+rr_limits.json: the reference's distances, integers only, for the seeded cases of tests/rrcheck.py (block_cases, chunk_cases,
+edge_cases: units of up to 4096 bases = 64 blocks, reads at the chunk borders of the kernel's text loop, thresholds at the
+distance itself); the units and reads are rebuilt from the seeds by the tests.
 """
 import json
 import os
@@ -67,17 +70,23 @@ def main():
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     from test_read_recruitment import random_cases
     rnd = dict(ref_distance=[rr.ref_distance(unit, read, k) for unit, read, k in random_cases()])
-    path, path_rnd = os.path.join(HERE, "rr_vectors.json"), os.path.join(HERE, "rr_ref_random.json")
+    import rrcheck
+    limits = rrcheck.reference_limits(rr.ref_distance)
+    rrcheck.check_golden_is_sound(limits)
+    path, path_rnd, path_lim = os.path.join(HERE, "rr_vectors.json"), os.path.join(HERE, "rr_ref_random.json"), rrcheck.GOLDEN
     if check:
-        with open(path) as f, open(path_rnd) as g:
-            same = json.load(f) == vec and json.load(g) == rnd
+        with open(path) as f, open(path_rnd) as g, open(path_lim) as h:
+            same = json.load(f) == vec and json.load(g) == rnd and json.load(h) == limits
         print("IDENTICAL" if same else "DIFFERENT")
         sys.exit(0 if same else 1)
     with open(path, "w") as f:
         json.dump(vec, f, indent=0)
     with open(path_rnd, "w") as f:
         json.dump(rnd, f)
-    print(len(vec), "cases;", sum(v["fwd"] != -1 or v["rc"] != -1 for v in vec), "recruited;", len(rnd["ref_distance"]), "random cases")
+    with open(path_lim, "w") as f:
+        json.dump(limits, f, separators=(",", ":"))
+    print(len(vec), "cases;", sum(v["fwd"] != -1 or v["rc"] != -1 for v in vec), "recruited;", len(rnd["ref_distance"]), "random cases;",
+          sum(len(r[s]) for n in limits for c in limits[n] for r in c["by_threshold"].values() for s in r), "limit distances")
 
 
 if __name__ == "__main__":

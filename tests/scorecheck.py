@@ -28,6 +28,7 @@ MAP_GOLDEN = os.path.join(ROOT, "tests", "golden", "map_reads_cases.json")
 WRONG_RULES = ("frequent_elsewhere_counts", "p_for_max_pos", "smaller_start_on_ties", "overhang_refused", "keep_on_equal",
                "no_start_zero_rule", "inner_is_the_callers_threshold")
 SPREAD_MAX_NPOS = (0, 1, 5)
+STRIDE_CASE = "hand_gap_b"      # check_past_the_launch_cap: the hand-built source (no pipeline run), max_pos 57, 18 reads
 INNER = (2, 10)      # calc_inters_score's defaults, which map_reads does not override (cloud_contig.py:48, :105-106)
 
 
@@ -279,3 +280,58 @@ def check_synthetic(engine, window=0):
     return dict(reads=R, entries=ref["entries"], max_pos=c["max_pos"], n_exact_pairs=c["n_exact_pairs"], mapped=len(placed),
                 mapped_where_cut=sum(1 for r in placed if full[r][0] == cut[r]),
                 mapped_elsewhere=sum(1 for r in placed if full[r][0] != cut[r]))
+
+
+# ------------------------------------------------------------------ more queries than launched workgroups
+def stride_queries(case, unit_ptr, row, n_cu, seed=192):
+    """192 x n_cu + 5 queries for a golden case: its reads repeated in a seeded shuffle, each with one of its three recorded ranges
+    (the full range, the overhang range, the sub-range), so that every workgroup of the 64 x n_cu launched takes three queries and
+    some a fourth.  Queries one launch stride apart run in the same workgroup, one after the other on the same LDS window: they are
+    drawn to differ in read and in range.  Returns (reads, lo, hi, the recorded (pos, s0, s1) per query, the stride)."""
+    rng = np.random.default_rng(seed)
+    stride = 64 * n_cu
+    n = 192 * n_cu + 5
+    ids = [row[r] for r in case["read_ids"]]
+    q, lo, hi, want = [], [], [], []
+    for i in range(n):
+        while True:
+            j, kind = int(rng.integers(0, len(ids))), int(rng.integers(0, 3))
+            w = case["reads"][j]
+            r = ids[j]
+            n_units = int(unit_ptr[r + 1] - unit_ptr[r])
+            a, b = ((0, case["max_pos"] - n_units + 1), (0, case["max_pos"]), (w[6], w[7]))[kind]
+            if i < stride or (q[i - stride] != r and (lo[i - stride], hi[i - stride]) != (a, b)):
+                break
+        q.append(r), lo.append(a), hi.append(b), want.append(w[(0, 3, 8)[kind]:(3, 6, 11)[kind]])
+    return np.array(q, np.int64), np.array(lo, np.int64), np.array(hi, np.int64), want, stride
+
+
+def check_past_the_launch_cap(src, case):
+    """One golden case as 192 x n_cu + 5 queries in one call, three times what the launch has workgroups, against the REFERENCE's
+    recorded rows gathered by query, with map_window forced to 3 (a range takes many windows) and left at its default (one window
+    per range).  Returns figures of the run."""
+    ids, unit_ptr, cloud_ptr, entries = src.use(case["source"])
+    e = src.engine
+    n_cu = e.device_info()["n_cu"]
+    row = {r_id: i for i, r_id in enumerate(ids)}
+    q, lo, hi, want, stride = stride_queries(case, np.asarray(unit_ptr), row, n_cu)
+    n = q.size
+    assert n == 192 * n_cu + 5 and n > 3 * stride
+    # neighbours in a workgroup's stride differ in read and in range, and the recorded answers are not all alike
+    assert (q[stride:] != q[:-stride]).all() and ((lo[stride:] != lo[:-stride]) | (hi[stride:] != hi[:-stride])).all()
+    placed = sum(w[0] >= 0 for w in want)
+    assert len({tuple(w) for w in want}) >= 10 and 4 * placed >= n and 8 * (n - placed) >= n
+    assert int((hi - lo).max()) >= 3 * 3      # a range of several windows of 3 starts
+    t0, t1 = case["threshold"]
+    e.contig_build([row[r] for r, _ in case["backbone"]], [p for _, p in case["backbone"]], case["f"])
+    assert e.contig_info()["max_pos"] == case["max_pos"]
+    try:
+        for window in (3, 0):
+            e.set_param("map_window", window)
+            got = _triples(*e.score_reads(q, lo, hi, t0, t1))
+            bad = [i for i in range(n) if got[i] != want[i]]
+            assert not bad, (f"{case['name']} (window {window}): {len(bad)} of {n} queries differ from the reference, first at query {bad[0]} "
+                             f"(the {bad[0] // stride + 1}. of its workgroup): {got[bad[0]]} for {want[bad[0]]}")
+    finally:
+        e.set_param("map_window", 0)
+    return dict(n_cu=n_cu, queries=n, workgroups=stride, placed=placed, distinct_answers=len({tuple(w) for w in want}))

@@ -2,7 +2,7 @@
 answers (tests/golden/score_reads_cases.json, captured by tests/golden/make_golden_score_reads.py from cloud_contig.py's own
 CloudContig.calc_inters_score, map_reads and get_spread_kmers): every golden case through the C ABI with the default window and
 with windows so small that a range takes several, the numpy statement of tests/scorecheck.py pinned to the same answers, queries
-as a shuffled subset, the degenerate reads, every refusal followed by a working call, cf_map_reads unchanged by a score call,
+as a shuffled subset, more queries than the launch has workgroups, the degenerate reads, every refusal followed by a working call, cf_map_reads unchanged by a score call,
 and one fixture on the UBSan build of the emulator."""
 import os
 import subprocess
@@ -112,6 +112,13 @@ def test_queries_as_a_shuffled_subset_with_repeats_and_map_reads_unchanged(src):
     # and the recorded fast answers are the ones compared with
     fast = [tuple(v) if v is not None else (-1, 0, 0) for v in case["fast"].values()]
     assert [tuple(int(a[row[r]]) for a in fast_before) for r in case["read_ids"]] == fast
+
+
+def test_more_queries_than_launched_workgroups(src):
+    """Every workgroup takes three or four queries, one after the other on the same LDS window."""
+    fig = scorecheck.check_past_the_launch_cap(src, _case(scorecheck.STRIDE_CASE))
+    print(fig)
+    assert fig["queries"] == 192 * fig["n_cu"] + 5 > 256
 
 
 def test_reads_without_units_and_with_empty_clouds(src):

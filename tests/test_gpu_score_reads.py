@@ -6,7 +6,9 @@
     positions, so a full range takes several windows of the default 2 048; 300 reads of 1 - 120 units whose clouds hold 0 - 150
     ranks; four ranks that recur with a short period.  Full ranges, overhang ranges, sub-ranges, ranges of one start — which must
     give the score the full-range pass gave that start — and cf_contig_spread, all against the numpy statement of
-    tests/scorecheck.py, with the default window and with one of 64.
+    tests/scorecheck.py, with the default window and with one of 64;
+  * one golden case as 192 x n_cu + 5 queries in one call, past the launch cap of 64 x n_cu workgroups, so that every workgroup
+    scores several queries in turn on its LDS window.
 Nothing here reads the reference tree."""
 import pytest
 
@@ -43,3 +45,11 @@ def test_a_hand_built_contig_of_several_windows(window):
         fig = scorecheck.check_synthetic(e, window)
     print(fig)
     assert fig["max_pos"] > 2 * 2048 and fig["mapped"] > 250 and fig["mapped_elsewhere"] >= 1
+
+
+def test_more_queries_than_launched_workgroups(src):
+    """192 x n_cu + 5 queries in one call (49 157 on 256 compute units): every workgroup takes three or four, one after the other
+    on the same LDS window."""
+    fig = scorecheck.check_past_the_launch_cap(src, next(c for c in CASES["cases"] if c["name"] == scorecheck.STRIDE_CASE))
+    print(fig)
+    assert fig["queries"] == 192 * fig["n_cu"] + 5 > 3 * fig["workgroups"]
