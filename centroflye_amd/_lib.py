@@ -46,6 +46,13 @@ class TandemShape(C.Structure):
         "pos_shift", "n_batches", "n_key_batches", "n_records", "n_reads")] + [("phase_ms", C.c_float * 6)]
 
 
+class ConsensusShape(C.Structure):
+    """Mirror of ``cf_consensus_shape``."""
+    _fields_ = [(n, C.c_int64) for n in (
+        "max_len", "block_small", "block_big", "big_from", "launch_cap", "batch_bytes", "k_ins", "n_pos", "n_reads", "n_iters",
+        "n_batches")] + [("phase_ms", C.c_float * 5)]
+
+
 # every symbol include/cfhip.h declares: name -> (restype, argtypes)
 _P, _I64, _I32, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
 _PI64 = C.POINTER(C.c_int64)
@@ -92,6 +99,9 @@ PROTOTYPES = {
     "cf_tandem_scan": (C.c_int, [_P, _P, _P, _I64, _I32, _I32, _P]),
     "cf_tandem_hook_positions": (C.c_int, [_P, _P, _P, _I64, _PI64]),
     "cf_tandem_info": (C.c_int, [_P, C.POINTER(TandemShape)]),
+    "cf_consensus_run": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, C.POINTER(C.c_float)]),
+    "cf_consensus_get": (C.c_int, [_P, _I32, _P, _P, _P, _P]),
+    "cf_consensus_info": (C.c_int, [_P, C.POINTER(ConsensusShape)]),
     "cf_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "cf_get_times": (C.c_int, [_P, C.POINTER(Times)]),
     "cf_set_param": (C.c_int, [_P, C.c_char_p, _I64]),

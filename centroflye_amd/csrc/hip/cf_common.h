@@ -156,6 +156,13 @@ struct cf_ctx {
     std::vector<int32_t> tandem_hook_pos;
     cf_tandem_shape tandem_last{};
 
+    // outputs of the last cf_consensus_run (cf_consensus.hip), in host memory: per iteration the bytes, their offsets and the
+    // voting / excluded reads of every position; and the run's shape and timings
+    std::vector<std::vector<uint8_t>> cons_bytes;
+    std::vector<std::vector<int64_t>> cons_off;
+    std::vector<std::vector<int32_t>> cons_voting, cons_excluded;
+    cf_consensus_shape cons_last{};
+
     // host <-> device copies of the caller's (pageable) buffers go through pinned staging slots, one per copy thread
     // (cf_api.hip: cf_copy_h2d / cf_copy_d2h)
     static constexpr int kCopyThreads = 16;      // slots; CF_COPY_THREADS (1 .. 16, default 16) picks how many are used
@@ -200,6 +207,7 @@ struct cf_ctx {
     int edit_lds_diags = 0;      // cf_edit: diagonals per wavefront array above which a pair's wavefronts live in HBM, not LDS (0 = 16384; tests force small values)
     int tandem_key_mode = 0;     // cf_tandem: 0 = 64-bit keys where (read in batch, code, position) fit them, 1 = keys or an error, 2 = 16-byte records
     int64_t tandem_batch_windows = 0;   // cf_tandem: windows per batch of whole reads (0 = 2^26; tests force borders inside small inputs)
+    int64_t cons_batch_bytes = 0;       // cf_consensus: bytes of move areas per batch of pairs (0 = 2^30; tests force borders inside one position's reads)
     int count_mode = 1;         // 1: sort and reduce (cf_count2.hip) when it applies; 0: the atomic table of round 1 (cf_count.hip)
     int count_bits = 0;          // bucket bits of the sort-and-reduce path; 0 = from the number of windows (tests force small / large values)
     int count_slots = 4096;

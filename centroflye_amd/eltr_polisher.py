@@ -9,7 +9,12 @@ by a thread pool).  ``run_polishing`` (:99-114) starts the same Flye command per
 device once, one ``cf_hpc`` call compresses them all and one ``cf_edit_distances`` call gives every distance of ``report.txt``
 (DESIGN §16).
 
-Without ``--num-iters``, ``--polish`` or ``--assemble-only`` the script ends with the exported files, as it always did.
+``--polisher consensus`` takes Flye's place with the library's own polisher (``cf_consensus_run``): every position's
+template and reads, as the export wrote them, go to the device in one call, and the ``pos_P/polished_i.fasta`` it writes are
+what ``assemble`` consumes.  It is not Flye's polisher and does not reproduce Flye's output; ``--polisher flye`` stays the default.
+
+Without ``--num-iters``, ``--polish``, ``--assemble-only`` or ``--polisher consensus`` the script ends with the exported files, as
+it always did.
 """
 import argparse
 import math
@@ -21,6 +26,7 @@ import numpy as np
 
 from . import ncrf_parser
 
+DEFAULT_MAX_DIVERGENCE_PERMILLE = 300  # --consensus-max-divergence-permille: a read votes iff 1000 d <= permille x template length
 DEFAULT_MAX_EDIT_DISTANCE = 32768      # --max-edit-distance (65 536 took 2.5 s to give up on two unrelated 1-Mb strings, this 0.64 s)
 
 
@@ -46,6 +52,22 @@ def read_first_record(fn):
     if not inside:
         raise PolishingError(f"{fn}: no FASTA record")
     return "".join(lines).replace(" ", "")
+
+
+def read_records(fn):
+    """The sequences of all records of a FASTA file, in file order (lines joined, like read_first_record)."""
+    try:
+        f = open(fn)
+    except OSError as e:
+        raise PolishingError(f"{fn}: {e.strerror or e}") from None
+    seqs = []
+    with f:
+        for ln in f:
+            if ln[:1] == ">":
+                seqs.append([])
+            elif seqs:
+                seqs[-1].append(ln.strip())
+    return ["".join(x).replace(" ", "") for x in seqs]
 
 
 def alignment_dict(distance, query, target):
@@ -145,6 +167,56 @@ class ELTR_Polisher:
             print(' '.join(cmd))
             subprocess.check_call(cmd)
 
+    def run_consensus(self, read_unit_filenames, num_iters=None, permille=None):
+        """The built-in polisher in Flye's place: the first record of median_read_unit.fasta and the records of read_units.fasta of
+        every position, in file order, one cf_consensus_run, then pos_P/polished_i.fasta (header >consensus_pos_P_iter_i) and
+        consensus_report.tsv.  Nothing is written when a position of min .. max has no reads or a string is beyond the device's
+        limit."""
+        from . import session
+        p = self.params
+        num_iters = int(num_iters if num_iters is not None else (getattr(p, "num_iters", None) or 4))
+        permille = int(permille if permille is not None else getattr(p, "consensus_max_divergence_permille", DEFAULT_MAX_DIVERGENCE_PERMILLE))
+        if num_iters < 1:
+            raise PolishingError("--num-iters must be at least 1")
+        if not read_unit_filenames:
+            raise PolishingError("no position has reads")
+        positions = list(range(min(read_unit_filenames), max(read_unit_filenames) + 1))
+        for pos in positions:
+            if pos not in read_unit_filenames:
+                raise PolishingError(f"position {pos} has no reads")
+        e = session.engine()
+        max_len = e.consensus_info()["max_len"]
+        templates, reads = [], []
+        for pos in positions:
+            units_fn, median_read_unit_fn = read_unit_filenames[pos]
+            templates.append(read_first_record(median_read_unit_fn).encode("latin-1"))
+            reads.append([r.encode("latin-1") for r in read_records(units_fn)])
+            if not reads[-1]:
+                raise PolishingError(f"position {pos} has no reads")
+            longest = max(len(templates[-1]), max(len(r) for r in reads[-1]))
+            if longest > max_len:
+                raise PolishingError(f"position {pos} has a sequence of {longest} bases, more than the {max_len} --polisher consensus takes")
+        t_off = np.zeros(len(positions) + 1, np.int64)
+        np.cumsum([len(t) for t in templates], out=t_off[1:])
+        pos_ptr = np.zeros(len(positions) + 1, np.int64)
+        np.cumsum([len(rs) for rs in reads], out=pos_ptr[1:])
+        flat = [r for rs in reads for r in rs]
+        r_off = np.zeros(len(flat) + 1, np.int64)
+        np.cumsum([len(r) for r in flat], out=r_off[1:])
+        res = e.consensus_run(b"".join(templates), t_off, b"".join(flat), r_off, pos_ptr, num_iters, permille)
+        self.consensus_ms = e.consensus_info()["phase_ms"]
+        files, rows = {}, ["iteration\tposition\ttemplate_length\treads\tvoting\texcluded\toutput_length"]
+        lengths = np.diff(t_off)
+        for i, (b, off, n_voting, n_excluded) in enumerate(res, 1):
+            text = b.tobytes().decode("latin-1")
+            for j, pos in enumerate(positions):
+                files[os.path.join(os.path.dirname(read_unit_filenames[pos][0]), f'polished_{i}.fasta')] = \
+                    f'>consensus_pos_{pos}_iter_{i}\n{text[off[j]:off[j + 1]]}\n'
+                rows.append(f"{i}\t{pos}\t{int(lengths[j])}\t{len(reads[j])}\t{int(n_voting[j])}\t{int(n_excluded[j])}\t{int(off[j + 1] - off[j])}")
+            lengths = np.diff(off)
+        files[os.path.join(p.outdir, 'consensus_report.tsv')] = "".join(r + "\n" for r in rows)
+        _write_atomically(files)
+
     def read_polishing(self, read_unit_filenames, num_iters):
         """{position: [polished sequence of iteration 1 .. num_iters]} (reference :116-126) after the checks that make the
         reference raise: every position of min .. max has reads, every polished_i.fasta is there."""
@@ -226,12 +298,20 @@ class ELTR_Polisher:
         pos2read = self.map_pos2read()
         if getattr(self.params, "assemble_only", False):
             return self.assemble(self.unit_filenames(pos2read))
+        consensus = not export_only and getattr(self.params, "polisher", "flye") == "consensus"
+        if consensus:      # known before anything is written
+            for pos in range(min(pos2read, default=0), max(pos2read, default=-1) + 1):
+                if pos not in pos2read:
+                    raise PolishingError(f"position {pos} has no reads")
         files = self.export_read_units(pos2read)
         if export_only:
             return files
         if not files:
             raise PolishingError("no position has reads")
-        self.run_polishing(files)
+        if consensus:
+            self.run_consensus(files)
+        else:
+            self.run_polishing(files)
         return self.assemble(files)
 
 
@@ -253,10 +333,17 @@ def main():
     parser.add_argument("--max-edit-distance", type=int, default=DEFAULT_MAX_EDIT_DISTANCE,
                         help="distances above this are reported as -1 (the work grows with its square)")
     parser.add_argument("--position-report", action="store_true", help="also write position_changes.csv: iteration position distance")
+    parser.add_argument("--polisher", choices=("flye", "consensus"), default="flye",
+                        help="flye (default): one Flye process per position; consensus: the library's own column-vote polisher, all positions in one "
+                             "device call, no external program (--flye-bin, --error-mode and --num-threads are ignored); not Flye's output")
+    parser.add_argument("--consensus-max-divergence-permille", type=int, default=DEFAULT_MAX_DIVERGENCE_PERMILLE,
+                        help="--polisher consensus: a read votes iff 1000 x its edit distance to the template <= this x the template's length")
     params = parser.parse_args()
     if params.max_edit_distance < 0:
         parser.error("--max-edit-distance must not be negative")
-    full = (params.polish or params.num_iters is not None or params.assemble_only) and not params.export_only
+    if params.consensus_max_divergence_permille < 0:
+        parser.error("--consensus-max-divergence-permille must not be negative")
+    full = (params.polish or params.num_iters is not None or params.assemble_only or params.polisher == "consensus") and not params.export_only
     if params.export_only and (params.polish or params.assemble_only):
         parser.error("--export-only excludes --polish and --assemble-only")
     try:

@@ -503,6 +503,45 @@ class Engine:
         d["phase_ms"] = dict(zip(("records", "sorts", "runs", "windows", "hook", "total"), (float(x) for x in s.phase_ms)))
         return d
 
+    # ------------------------------------------------------------------ the built-in consensus polisher (cf_consensus.hip)
+    def consensus_run(self, templates, t_off, reads, r_off, pos_ptr, n_iters=4, permille=300):
+        """Every position's reads aligned to its template, a vote per column and insertion slot, n_iters passes, all positions in
+        one call (the rule: include/cfhip.h at cf_consensus_run).  templates[t_off[p]:t_off[p + 1]] is the template of position p,
+        reads[r_off[q]:r_off[q + 1]] read q, pos_ptr a CSR over the reads.  Returns [(bytes uint8, off int64[n_pos + 1], n_voting
+        int32[n_pos], n_excluded int32[n_pos]) for iteration 1 .. n_iters]; consensus_info() has the device times."""
+        as_u8 = lambda x: np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else np.ascontiguousarray(x, np.uint8)
+        templates, reads = as_u8(templates), as_u8(reads)
+        t_off = np.ascontiguousarray(t_off, np.int64).reshape(-1)
+        r_off = np.ascontiguousarray(r_off, np.int64).reshape(-1)
+        pos_ptr = np.ascontiguousarray(pos_ptr, np.int64).reshape(-1)
+        if t_off.size < 1 or pos_ptr.size != t_off.size:
+            raise ValueError("t_off and pos_ptr have one entry per position and one more")
+        if r_off.size < 1 or int(pos_ptr[-1]) != r_off.size - 1:
+            raise ValueError("r_off has one entry per read of pos_ptr and one more")
+        if int(t_off.max()) > templates.size or int(r_off.max()) > reads.size:
+            raise ValueError("an offset lies beyond the bytes")
+        n_pos, n_iters = t_off.size - 1, int(n_iters)
+        totals = np.zeros(max(n_iters, 1), np.int64)
+        ms = C.c_float()
+        self._check(self._lib.cf_consensus_run(self._ctx, _ptr(templates) if templates.size else None, _ptr(t_off), _ptr(reads) if reads.size else None,
+                                               _ptr(r_off), _ptr(pos_ptr), n_pos, n_iters, int(permille), _ptr(totals), C.byref(ms)), "cf_consensus_run")
+        out = []
+        for i in range(n_iters):
+            b, off = np.zeros(max(int(totals[i]), 1), np.uint8), np.zeros(n_pos + 1, np.int64)
+            nv, ne = np.zeros(max(n_pos, 1), np.int32), np.zeros(max(n_pos, 1), np.int32)
+            self._check(self._lib.cf_consensus_get(self._ctx, i + 1, _ptr(b), _ptr(off), _ptr(nv), _ptr(ne)), "cf_consensus_get")
+            out.append((b[:int(totals[i])], off, nv[:n_pos], ne[:n_pos]))
+        return out
+
+    def consensus_info(self):
+        """The shape of cf_consensus.hip (max_len, block_small / block_big / big_from, launch_cap, batch_bytes, k_ins), the figures
+        of the last run (n_pos, n_reads, n_iters, n_batches) and its device milliseconds per phase."""
+        s = _lib.ConsensusShape()
+        self._check(self._lib.cf_consensus_info(self._ctx, C.byref(s)), "cf_consensus_info")
+        d = {n: int(getattr(s, n)) for n, _ in s._fields_ if n != "phase_ms"}
+        d["phase_ms"] = dict(zip(("copies", "align", "vote", "compact", "total"), (float(x) for x in s.phase_ms)))
+        return d
+
     # ------------------------------------------------------------------ self tests of primitives
     def selftest_sort(self, keys, bits=64):
         keys = np.ascontiguousarray(keys, np.uint64)

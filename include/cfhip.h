@@ -23,6 +23,8 @@
  *   cf_edit_distances  scripts/eltr_polisher.py:133-146 (compare_polished_sequences: edlib.align in mode NW)
  *   cf_hpc             scripts/utils/bio.py:60-61 (compress_homopolymer), used by eltr_polisher.py:142-143, :151
  *   cf_tandem_scan     scripts/unit_extractor.py:23-89 (get_repetitive_kmers, get_convolution, get_period_info, get_hook_kmer)
+ *   cf_consensus_run   stands in for scripts/eltr_polisher.py:99-114 (run_polishing: one Flye process per position); there is
+ *                      NO reference function behind it: the rule in the comment at its declaration is the specification
  *
  * Conventions: plain pointers and sizes only; every function returns 0 or a negative
  * errno-style code and never throws or aborts; cf_last_error() gives the message; the
@@ -277,6 +279,53 @@ int cf_tandem_scan(cf_ctx* ctx, const uint8_t* reads, const int64_t* read_off, i
 int cf_tandem_hook_positions(cf_ctx* ctx, int64_t* ptr, int32_t* pos, int64_t cap, int64_t* n_out);
 int cf_tandem_info(cf_ctx* ctx, cf_tandem_shape* out);
 
+/* The built-in consensus polisher (cf_consensus.hip).  It stands in for the step of scripts/eltr_polisher.py:99-114 (run_polishing:
+ * one `flye --polish-target` process per contig position) and has NO reference function behind it: it is not Flye's polisher
+ * and does not claim Flye's output.  The rule below is the specification (tests/conscheck.py restates it).
+ * cf_consensus_run: n_pos positions; the template of position p is templates[t_off[p], t_off[p + 1]), its reads are the reads
+ * pos_ptr[p] .. pos_ptr[p + 1] - 1 (a CSR over the reads, pos_ptr[0] = 0), read q is reads[r_off[q], r_off[q + 1]); all three
+ * offset arrays are non-decreasing and >= 0, a string holds at most max_len bytes (cf_consensus_info).  One pass, per position
+ * with template t (length m) and reads r_1 .. r_c:
+ *   1. D = the full unit-cost NW matrix of (t, r) (byte equality, as cf_edit_distances), d = D[m][n]; the alignment is the walk
+ *      back from (m, n) that at (i, j) takes (a) the diagonal if i, j > 0 and D[i-1][j-1] + (t[i-1] != r[j-1]) == D[i][j]: the
+ *      read byte r[j-1] sits on column i - 1; (b) else, if i > 0 and D[i-1][j] + 1 == D[i][j], column i - 1 is deleted in
+ *      this read; (c) else r[j-1] is an inserted byte of slot i (slot s lies before column s, slot m behind the last column).
+ *   2. A read votes iff 1000 d <= permille m; c_v = the voting reads; c_v == 0 leaves t as it is.
+ *   3. Column i: a byte A, C, G or T on the diagonal votes for its base, any other byte casts no vote, a deletion votes
+ *      "deleted".  Slot s: the k-th byte (k = 0 .. 3) of the read's inserted run, in read order, votes for its base at (s, k) if
+ *      it is A, C, G or T; bytes from the fifth on cast no vote (a pass adds at most 4 bases per slot).
+ *   4. For s = 0 .. m: for k = 0 .. 3, with v the sum of the four tallies of (s, k): 2 v > c_v emits the base with the largest
+ *      tally (ties: the first of A < C < G < T), anything else ends the slot.  Then, for s < m, column s: t[s] if all five
+ *      tallies are 0; else the largest tally, a tie going to t[s] if it is one of the tied bases, else to the first of A, C, G,
+ *      T, deleted; "deleted" emits nothing.
+ * Iteration i has the output of iteration i - 1 as its template; all n_iters (>= 1) outputs of all positions are produced by
+ * the one call and stay in the context (host memory) for cf_consensus_get.  total_bytes_out[n_iters] (may be NULL): the bytes
+ * of every iteration's output; *ms_out (may be NULL): device milliseconds of the call, copies included.  Per pair the device
+ * fills the band |j - i| <= w of D by anti-diagonals, w doubling from the distance of the iteration before until D[m][n] <= w
+ * (then the band holds every cell of the walk) or w reaches floor(permille m / 1000) (then the read does not vote), writes
+ * the move of every cell (2 bits) to the pair's area of scratch, and walks back; pairs go through in batches whose areas stay
+ * under the knob "cons_batch_bytes".  Nothing is added to cf_times or cf_stats.  Errors (-22: null pointers, decreasing or negative
+ * offsets, pos_ptr[0] != 0, n_pos < 0, n_iters < 1, a negative permille, a string longer than max_len, given or grown) leave
+ * the context and the results of the call before as they were.
+ * cf_consensus_get: the output of iteration iter (1 .. n_iters) of the last run: out_bytes (room for total_bytes_out[iter - 1]),
+ * out_off[n_pos + 1], n_voting[n_pos] and n_excluded[n_pos] (the reads of that pass that voted / did not); any may be NULL.
+ * cf_consensus_info: the shape the tests straddle and the last run's figures.  phase_ms: copies to and from the device,
+ * alignment (bands, moves, walks), vote and emission, scan and compaction, the whole call; by HIP events, summed over the
+ * iterations of the last run. */
+typedef struct cf_consensus_shape {
+    int64_t max_len;                      /* bytes of the longest template or read taken                              */
+    int64_t block_small, block_big, big_from; /* threads per workgroup; batches with a band of more than big_from diagonals take block_big */
+    int64_t launch_cap;                   /* workgroups of a launch at most                                           */
+    int64_t batch_bytes;                  /* move areas per batch in force (knob "cons_batch_bytes", 0 = 2^30)        */
+    int64_t k_ins;                        /* bases a pass adds per slot at most                                       */
+    int64_t n_pos, n_reads, n_iters, n_batches; /* of the last run (batches summed over its iterations)               */
+    float phase_ms[5];
+} cf_consensus_shape;
+int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off, const uint8_t* reads, const int64_t* r_off,
+                     const int64_t* pos_ptr, int64_t n_pos, int32_t n_iters, int32_t permille, int64_t* total_bytes_out, float* ms_out);
+int cf_consensus_get(cf_ctx* ctx, int32_t iter, uint8_t* out_bytes, int64_t* out_off, int32_t* n_voting, int32_t* n_excluded);
+int cf_consensus_info(cf_ctx* ctx, cf_consensus_shape* out);
+
 int cf_get_stats(cf_ctx* ctx, cf_stats* out);
 int cf_get_times(cf_ctx* ctx, cf_times* out);
 
@@ -315,7 +364,7 @@ int cf_allreduce_unique(cf_ctx* ctx, int64_t* n_unique);
 /* Tuning knobs (defaults are chosen for gfx950): name in {"dist_block" (threads per workgroup, 0 = auto), "dist_wgs"
  * (workgroups per CU the LDS is split between, 0 = auto: by the pair emissions per first k-mer), "dist_slots" (LDS budget of the (b,d) table in 8-byte units, 0 = all that
  * is left), "dist_sketch" (0: every pair goes to the exact table), "dist_fill_pct", "dist_est_pct", "dist_stage", "dist_edge_chunk" (edge rows a workgroup reserves in the output per global atomic, 0 = 8192; tests use small chunks), "dist_int_thr" (0: the dominance test always divides in doubles; 1, the default: the literal 0.8 is tested as 5 cnt >= 4 total, which is the same predicate),
- * "dist_wide", "dist_post_atomics" (1: postings by a histogram and a fill pass of atomics instead of the sort), "dist_hot_cap" (tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan), "dist_sketch_bits" (bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the counters in the same LDS —, else 8; 8 forces bytes), "lut_shift" (the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1, the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0), "dist_hot_entries" (default 32768: first k-mers with more partner entries than this keep no list of hot slots during their inserts — it would overflow — and their filter scans the count fields; -1: always keep it), "dist_regions" (1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long reads take by themselves), "dist_dbits" (5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks need), "place_mode" (2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4; smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the hash-map path of rounds 1-3, cf_place.hip), "place_grid" / "place_block" (workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024), "place_row_words" (32 or 64 words per posting row, 0 = by the longest posting list), "place_slots_per_unit" (score-region slots per unit of a read, 0 = 48; grown automatically when a region fills), "place_l3" / "place_l3_shift" (1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily — built in round 5, measured neutral at 500 000 reads, off by default), "dist_region_bytes" (1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond 128 units do by themselves), "place_long_rescans" (default 2: a run of the region path whose reads average more than this many rescans of reads with more than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is handed to the hash-map path; -1: at the first look, tests), "place_cmap_bits" (log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 = cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load), "place_chunk", "place_fused" (place_mode 1: cloud entries per wave step; 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list and a third kernel per greedy iteration), "count_mode" (1: A1 by sort and reduce, 0: the atomic table), "count_bits" (bucket bits of the former, 0 = auto), "count_slots", "count_tile", "count_skip_exotic" (1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads), "comm_round_bytes" (bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds), "map_window" (candidate starts — LDS score slots — that cf_map_reads covers per pass over a read's cloud entries, 0 = 2048, at most 4096; a read whose hits span more starts takes several passes, tests force that with tiny windows), "edit_lds_diags" (cf_edit_distances: diagonals per wavefront array up to which a pair's wavefronts stay in LDS, 0 = 16384, at most 16384; tests force the HBM path with small values), "comm_self_p2p" (1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a one-GPU box runs the whole p2p path), "tandem_key_mode" and "tandem_batch_windows" (cf_tandem_scan: see there)}.  Results never depend on them (tests/test_gpu_parity.py). */
+ * "dist_wide", "dist_post_atomics" (1: postings by a histogram and a fill pass of atomics instead of the sort), "dist_hot_cap" (tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan), "dist_sketch_bits" (bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the counters in the same LDS —, else 8; 8 forces bytes), "lut_shift" (the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1, the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0), "dist_hot_entries" (default 32768: first k-mers with more partner entries than this keep no list of hot slots during their inserts — it would overflow — and their filter scans the count fields; -1: always keep it), "dist_regions" (1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long reads take by themselves), "dist_dbits" (5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks need), "place_mode" (2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4; smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the hash-map path of rounds 1-3, cf_place.hip), "place_grid" / "place_block" (workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024), "place_row_words" (32 or 64 words per posting row, 0 = by the longest posting list), "place_slots_per_unit" (score-region slots per unit of a read, 0 = 48; grown automatically when a region fills), "place_l3" / "place_l3_shift" (1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily — built in round 5, measured neutral at 500 000 reads, off by default), "dist_region_bytes" (1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond 128 units do by themselves), "place_long_rescans" (default 2: a run of the region path whose reads average more than this many rescans of reads with more than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is handed to the hash-map path; -1: at the first look, tests), "place_cmap_bits" (log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 = cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load), "place_chunk", "place_fused" (place_mode 1: cloud entries per wave step; 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list and a third kernel per greedy iteration), "count_mode" (1: A1 by sort and reduce, 0: the atomic table), "count_bits" (bucket bits of the former, 0 = auto), "count_slots", "count_tile", "count_skip_exotic" (1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads), "comm_round_bytes" (bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds), "map_window" (candidate starts — LDS score slots — that cf_map_reads covers per pass over a read's cloud entries, 0 = 2048, at most 4096; a read whose hits span more starts takes several passes, tests force that with tiny windows), "edit_lds_diags" (cf_edit_distances: diagonals per wavefront array up to which a pair's wavefronts stay in LDS, 0 = 16384, at most 16384; tests force the HBM path with small values), "comm_self_p2p" (1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a one-GPU box runs the whole p2p path), "tandem_key_mode" and "tandem_batch_windows" (cf_tandem_scan: see there), "cons_batch_bytes" (cf_consensus_run: bytes of move areas per batch of pairs, 0 = 2^30, at most 2^36; a batch holds at least one pair; tests force many batches with small values)}.  Results never depend on them (tests/test_gpu_parity.py). */
 int cf_set_param(cf_ctx* ctx, const char* name, int64_t value);
 
 /* Self-tests of the device primitives against host results (used by tests/ only). */
