@@ -526,6 +526,8 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
     } else if (n == "dist_sketch_bits") {
         if (value != 0 && value != 4 && value != 8) return cf_fail(ctx, -22, "dist_sketch_bits must be 0 (by min_cov), 4 or 8");
         ctx->dist_sketch_bits = (int)value;
+    } else if (n == "dist_sketch_tail") {
+        ctx->dist_sketch_tail = value != 0;
     } else if (n == "dist_sketch") {
         ctx->dist_sketch = value != 0;
     } else if (n == "dist_est_pct") {

@@ -45,8 +45,9 @@ __device__ __forceinline__ unsigned long long cf_ballot(bool p) { return __built
 #endif
 
 // One posting (= one unit g holding the first k-mer): its partner entries — the clouds of the units g+min_d ..
-// min(read end, g+max_d) — are ONE contiguous CSR range [e0, e0 + len); ig is the index of g inside its read.
-struct alignas(16) cf_dist_rec { int64_t e0; uint32_t len; uint32_t ig; };
+// min(read end, g+max_d) — are ONE contiguous CSR range [e0, e0 + len); ig is the index of g inside its read, nu the number of
+// those partner units (cf_dist_edges refuses 2^32 cloud entries and more: e0 has 32 bits).
+struct alignas(16) cf_dist_rec { uint32_t e0; uint32_t len; uint32_t ig; uint32_t nu; };
 
 __global__ void __launch_bounds__(256)
 cf_post_hist_kernel(const int32_t* __restrict__ entries, int64_t e0, int64_t e1, uint32_t part, uint32_t n_parts, uint32_t* __restrict__ cnt) {
@@ -161,8 +162,8 @@ cf_unit_rend_kernel(const int64_t* __restrict__ unit_ptr, const int64_t* __restr
         for (int64_t u = a; u < b; ++u) {
             rend[u] = (int32_t)b; rbeg[u] = (int32_t)a;
             const int64_t jlo = u + min_d, jhi = min(b - 1, u + (int64_t)max_d);
-            cf_dist_rec x{0, 0u, (uint32_t)(u - a)};
-            if (jhi >= jlo) { x.e0 = cloud_ptr[jlo]; x.len = (uint32_t)(cloud_ptr[jhi + 1] - x.e0); }
+            cf_dist_rec x{0u, 0u, (uint32_t)(u - a), 0u};
+            if (jhi >= jlo) { const int64_t c0 = cloud_ptr[jlo]; x.e0 = (uint32_t)c0; x.len = (uint32_t)(cloud_ptr[jhi + 1] - c0); x.nu = (uint32_t)(jhi - jlo + 1); }
             urange[u] = x;
         }
     }
@@ -172,16 +173,26 @@ cf_unit_rend_kernel(const int64_t* __restrict__ unit_ptr, const int64_t* __restr
 // layout) or, mod 2^(32 - b_bits), packed above the rank (narrow layouts: one 4-byte load per pair emission)
 __global__ void __launch_bounds__(256)
 cf_entry_unit_kernel(const int64_t* __restrict__ cloud_ptr, const int32_t* __restrict__ rbeg, const int32_t* __restrict__ entries, int64_t n_units,
-                     uint16_t* __restrict__ entry_i, uint32_t* __restrict__ packed, int b_bits, uint8_t* __restrict__ entry_i8) {
+                     uint16_t* __restrict__ entry_i, uint32_t* __restrict__ packed, int b_bits, uint8_t* __restrict__ entry_i8,
+                     unsigned long long* __restrict__ not_a_set) {
+    // not_a_set: raised when a unit's row is not strictly ascending — a rank twice in one cloud (caller-made clouds, cf_set_clouds;
+    // cf_build_clouds makes sets).  cf_items_fill_kernel reads it: the bound behind the tail items of the sketch sweep needs sets.
     const int lane = threadIdx.x & 63;
+    bool bad = false;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     for (int64_t u = wave; u < n_units; u += n_waves) {
         const uint32_t i = (uint32_t)(u - rbeg[u]);
-        if (packed) { for (int64_t e = cloud_ptr[u] + lane; e < cloud_ptr[u + 1]; e += 64) packed[e] = (i << b_bits) | (uint32_t)entries[e]; }      // (the shift drops all but the low 32 - b_bits bits of i)
-        else if (entry_i8) { for (int64_t e = cloud_ptr[u] + lane; e < cloud_ptr[u + 1]; e += 64) entry_i8[e] = (uint8_t)i; }
-        else { for (int64_t e = cloud_ptr[u] + lane; e < cloud_ptr[u + 1]; e += 64) entry_i[e] = (uint16_t)i; }
+        const int64_t c0 = cloud_ptr[u], c1 = cloud_ptr[u + 1];
+        for (int64_t e = c0 + lane; e < c1; e += 64) {
+            const int32_t x = entries[e];
+            if (e > c0) bad = bad || entries[e - 1] >= x;      // (the neighbour's word: the same cache line but for one lane in 32)
+            if (packed) packed[e] = (i << b_bits) | (uint32_t)x;      // (the shift drops all but the low 32 - b_bits bits of i)
+            else if (entry_i8) entry_i8[e] = (uint8_t)i;
+            else entry_i[e] = (uint16_t)i;
+        }
     }
+    if (bad) *not_a_set = 1ull;      // (plain stores of the one value; read by a later kernel of the stream)
 }
 
 // keys (first posting unit << 32 | a) of the first k-mers of this partition that have postings
@@ -240,7 +251,8 @@ struct alignas(8) cf_dist_item { uint32_t e, m; };
 #ifndef CF_DIST_ITEMS_BLOCKED
 #define CF_DIST_ITEMS_BLOCKED 0
 #endif
-struct alignas(16) cf_dist_head { uint32_t a, n_items; unsigned long long ibase; uint32_t n_entries, pad0, pad1, pad2; };   // n_entries: partner entries (capped at 2^30 - 1)
+// Items are numbered useful ones first: the sketch sweep takes the items 0 .. n_useful - 1 only, the table sweep all of them (cf_items_fill_kernel).
+struct alignas(16) cf_dist_head { uint32_t a, n_items; unsigned long long ibase; uint32_t n_entries, n_useful, pad1, pad2; };   // n_entries: partner entries (capped at 2^30 - 1)
 
 struct cf_dist_args {
     const int64_t* post_ptr;
@@ -1065,7 +1077,7 @@ cf_items_count_kernel(const int32_t* __restrict__ order, int64_t n_order, const 
         for (int64_t x0 = 0; x0 < np_max; x0 += 16) {
             const bool hx = p0 + x0 + gl < p1;
             const int32_t ux = hx ? post[p0 + x0 + gl] : 0;
-            cf_dist_rec rx_{0, 0u, 0u};
+            cf_dist_rec rx_{0u, 0u, 0u, 0u};
             if (hx) rx_ = urange[ux];
             const int32_t rx = hx ? ux - (int32_t)rx_.ig : -1;      // first unit of the posting's read (ig = the unit's index in its read): ONE gather per posting
             if (hx) c += (rx_.len + DIST_ITEM - 1u) / DIST_ITEM;
@@ -1100,16 +1112,40 @@ cf_items_count_kernel(const int32_t* __restrict__ order, int64_t n_order, const 
     if ((threadIdx.x & 63) == 0 && self) atomicAdd(self_pairs, self);
 }
 
+// The order of a first k-mer's items.  The sketch sweep only has to find the k-mers b with some cnt(a, b, d) >= min_cov.
+// A cloud row is a set, so inside the partner range of ONE posting every (b, d) occurs at most once: cnt(a, b, d) <= P_d(a), the
+// number of postings of a whose partner range has a unit at distance d.  P_d falls as d grows; with nu_i the partner units of
+// posting i, d* = min_d - 1 + (the min_cov-th largest nu_i) is the largest distance with P_d >= min_cov, and an entry of a unit
+// further away than d* belongs to a pair that cannot reach min_cov: counting it in the sketch only adds collisions and marks.  So the
+// items are numbered USEFUL ones first (0 .. nA - 1), then the TAIL items — those whose first entry lies in a unit beyond d* (an item
+// that straddles the boundary is useful: over-counting is safe); inside each group posting by posting, as before.  The sketch sweep
+// takes the first nA items, the table sweep all n (the totals of the filter need every distance of a marked b).  Item boundaries,
+// their number and the record format are what they were.
+// nA = n (every item useful, and then the numbering is exactly the old one) when
+//   * tail == 0: the knob dist_sketch_tail is 0, or the launch runs without the sketch (min_cov < 2, dist_sketch 0);
+//   * *not_a_set != 0: cf_entry_unit_kernel found a row with a repeated rank in this launch's clouds (cf_set_clouds takes any rows;
+//     the bound needs sets) — read here on the device, no host synchronisation;
+//   * the first k-mer has more than 16 * DIST_SEL_CHUNKS = 64 postings: the selection below keeps the nu_i of a list in registers, four per
+//     lane of the group.  A performance fall-back, not an approximation.
+// If fewer than min_cov postings have a partner unit at all, no pair of a can reach min_cov: nA = 0.
+// -DCF_DIST_DIAG_COUNT: diag[0] += sum of nA, diag[1] += sum of n over the launch (one atomic each per wave, at the kernel's end).
+#define DIST_SEL_CHUNKS 4
 __global__ void __launch_bounds__(256)
 cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
                      const cf_dist_rec* __restrict__ urange, uint32_t nw, const uint32_t* __restrict__ n_items, const int64_t* __restrict__ ibase,
-                     cf_dist_head* __restrict__ heads, cf_dist_item* __restrict__ items, const int64_t* __restrict__ cloud_ptr64, int64_t n_units) {
-    // cloud_ptr64 != null: the 26-bit stream (cf_tab_region26): the item record's low half is [t64 : 9 | unit index mod 128 : 7]
+                     cf_dist_head* __restrict__ heads, cf_dist_item* __restrict__ items, const int64_t* __restrict__ cloud_ptr, int stream26, int64_t n_units,
+                     int32_t min_d, int32_t max_d, uint32_t min_cov, int tail, const unsigned long long* __restrict__ not_a_set, unsigned long long* __restrict__ diag) {
+    // stream26: the 26-bit stream (cf_tab_region26): the item record's low half is [t64 : 9 | unit index mod 128 : 7]
     const int gl = threadIdx.x & 15;
     const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const int64_t n_grp = ((int64_t)gridDim.x * blockDim.x) >> 4;
     const bool nw_pow2 = (nw & (nw - 1u)) == 0u;
     const uint32_t nw_log2 = 31u - (uint32_t)__clz((int)max(nw, 1u));
+    const bool tail_on = tail && min_cov >= 2u && max_d >= min_d && *not_a_set == 0ull;      // (uniform over the launch)
+    const int sel_bits = 32 - __clz((int)(max_d >= min_d ? max_d - min_d + 1 : 1));         // nu <= max_d - min_d + 1 <= 65535
+#if defined(CF_DIST_DIAG_COUNT)
+    unsigned long long dg_a = 0, dg_n = 0;
+#endif
     int32_t a_n = 0; int64_t p0_n = 0, p1_n = 0, ib_n = 0; uint32_t n_n = 0;      // (fetched one iteration ahead, as in cf_items_count_kernel)
     if (grp < n_order) { a_n = order[grp]; p0_n = post_ptr[a_n]; p1_n = post_ptr[a_n + 1]; n_n = n_items[grp]; ib_n = ibase[grp]; }
     for (int64_t i0 = 0; i0 < n_order; i0 += n_grp) {      // (uniform trip count: shuffles inside)
@@ -1124,36 +1160,94 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
         cf_dist_item* out = items + ib;
         int64_t np_max = p1 - p0;
         for (int d = 16; d <= 32; d <<= 1) np_max = max(np_max, __shfl_xor(np_max, d));
-        uint32_t j0 = 0;      // items of the postings before this chunk (group-uniform)
-        unsigned long long ne = 0;
-        for (int64_t q0 = 0; q0 < np_max; q0 += 16) {      // 16 postings at a time, one per lane of the group
-            cf_dist_rec r{0, 0u, 0u};
-            int64_t e64 = 0;      // (26-bit stream) the first partner entry whose unit lies 64 or more behind the posting's
+        // one posting per lane of the group, DIST_SEL_CHUNKS x 16 of them in registers: the partner range, the posting's unit and (26-bit
+        // stream) where, inside the range, the first entry lies whose unit is 64 or more behind the posting's
+        auto fetch = [&](int64_t q0, cf_dist_rec& r, int32_t& ux, uint32_t& rel64) {
+            r = cf_dist_rec{0u, 0u, 0u, 0u}; ux = 0; rel64 = 0u;
             if (p0 + q0 + gl < p1) {
-                const int32_t ux = post[p0 + q0 + gl];
+                ux = post[p0 + q0 + gl];
                 r = urange[ux];
-                if (cloud_ptr64) { const int64_t c64 = (int64_t)ux + 64 <= n_units ? cloud_ptr64[(int64_t)ux + 64] : r.e0 + (int64_t)r.len; e64 = min(max(c64, r.e0), r.e0 + (int64_t)r.len); }
+                if (stream26) { const int64_t c64 = (int64_t)ux + 64 <= n_units ? cloud_ptr[(int64_t)ux + 64] : (int64_t)r.e0 + (int64_t)r.len; rel64 = (uint32_t)(min(max(c64, (int64_t)r.e0), (int64_t)r.e0 + (int64_t)r.len) - (int64_t)r.e0); }
             }
+        };
+        cf_dist_rec rk[DIST_SEL_CHUNKS]; int32_t uk[DIST_SEL_CHUNKS]; uint32_t r64k[DIST_SEL_CHUNKS], ck[DIST_SEL_CHUNKS];
+#pragma unroll
+        for (int q = 0; q < DIST_SEL_CHUNKS; ++q) {
+            rk[q] = cf_dist_rec{0u, 0u, 0u, 0u}; uk[q] = 0; r64k[q] = 0u;
+            if ((int64_t)q * 16 < np_max) fetch((int64_t)q * 16, rk[q], uk[q], r64k[q]);
+            ck[q] = (rk[q].len + DIST_ITEM - 1u) / DIST_ITEM;      // useful items of the posting: all of them, unless the selection below says less
+        }
+        uint32_t nA = n;
+        const bool exact = tail_on && p1 - p0 <= 16 * DIST_SEL_CHUNKS;      // (uniform in the group)
+        if (tail_on) {      // (uniform in the wave: shuffles inside)
+            // the min_cov-th largest nu of the group's postings = the largest t with #{nu_i >= t} >= min_cov, bit by bit from the top (0: there is none)
+            uint32_t nu_star = 0;
+            for (int bit = sel_bits - 1; bit >= 0; --bit) {
+                const uint32_t cand = nu_star | (1u << bit);
+                uint32_t c = 0;
+#pragma unroll
+                for (int q = 0; q < DIST_SEL_CHUNKS; ++q) c += (uint32_t)(rk[q].nu >= cand);
+                for (int d = 8; d >= 1; d >>= 1) c += __shfl_xor(c, d, 16);
+                if (c >= min_cov) nu_star = cand;
+            }
+            uint32_t sA = 0;
+#pragma unroll
+            for (int q = 0; q < DIST_SEL_CHUNKS; ++q) {
+                // a posting with more partner units than nu_star is cut behind its nu_star-th (at most min_cov - 1 postings of a list are): the
+                // unit at distance d* + 1 is the posting's unit + min_d + nu_star, inside its range
+                if (exact && rk[q].nu > nu_star) {
+                    uint32_t useful = 0;
+                    if (nu_star) useful = ((uint32_t)cloud_ptr[(int64_t)uk[q] + min_d + (int64_t)nu_star] - rk[q].e0 + DIST_ITEM - 1u) / DIST_ITEM;
+                    ck[q] = min(ck[q], useful);
+                }
+                sA += ck[q];
+            }
+            for (int d = 8; d >= 1; d >>= 1) sA += __shfl_xor(sA, d, 16);
+            if (exact) nA = sA;
+        }
+        uint32_t jA0 = 0, jT0 = nA;      // useful / tail items of the postings before this chunk (group-uniform)
+        unsigned long long ne = 0;
+        auto emit = [&](const cf_dist_rec& r, uint32_t rel64, uint32_t cA) {
             const uint32_t c = (r.len + DIST_ITEM - 1u) / DIST_ITEM;
-            uint32_t inc = c;
-            for (int d = 1; d < 16; d <<= 1) { const uint32_t o = __shfl_up(inc, (unsigned)d, 16); if (gl >= d) inc += o; }
-            const uint32_t jb = j0 + inc - c;      // the lane's first item
+            uint32_t incA = cA, incT = c - cA;
+            for (int d = 1; d < 16; d <<= 1) { const uint32_t o = __shfl_up(incA, (unsigned)d, 16); if (gl >= d) incA += o; }
+            if (tail_on) for (int d = 1; d < 16; d <<= 1) { const uint32_t o = __shfl_up(incT, (unsigned)d, 16); if (gl >= d) incT += o; }
+            const uint32_t jbA = jA0 + incA - cA, jbT = jT0 + incT - (c - cA) - cA;      // the lane's first useful item; its first tail item less the useful ones before it
             for (uint32_t x = 0; x < c; ++x) {
-                const uint32_t j = jb + x, off = x * DIST_ITEM;
+                const uint32_t j = (x < cA ? jbA : jbT) + x, off = x * DIST_ITEM;
                 uint32_t low = r.ig & 0xFFFFu;
-                if (cloud_ptr64) low = ((uint32_t)min(max(e64 - (r.e0 + (int64_t)off), (int64_t)0), (int64_t)DIST_ITEM) << 7) | (r.ig & 127u);
+                if (stream26) low = ((rel64 > off ? min(rel64 - off, DIST_ITEM) : 0u) << 7) | (r.ig & 127u);
                 // (round 6: the waves of a workgroup are a power of two in every launch shape the library picks — a mask and a shift
                 // instead of two divisions by a run-time number per item record, 6.9e8 of them at 50 000 reads)
                 const uint32_t jw = nw_pow2 ? (j & (nw - 1u)) : j % nw, jq = nw_pow2 ? (j >> nw_log2) : j / nw;
-                out[CF_DIST_ITEMS_BLOCKED ? (size_t)j : (size_t)jw * per + jq] = cf_dist_item{(uint32_t)r.e0 + off, (min(r.len - off, DIST_ITEM) << 16) | low};
+                out[CF_DIST_ITEMS_BLOCKED ? (size_t)j : (size_t)jw * per + jq] = cf_dist_item{r.e0 + off, (min(r.len - off, DIST_ITEM) << 16) | low};
             }
-            j0 += (uint32_t)__shfl((int)inc, 15, 16);
+            jA0 += (uint32_t)__shfl((int)incA, 15, 16);
+            if (tail_on) jT0 += (uint32_t)__shfl((int)incT, 15, 16);
             unsigned long long l = r.len;
             for (int d = 8; d >= 1; d >>= 1) l += __shfl_down(l, (unsigned)d, 16);
             ne += (unsigned long long)__shfl((long long)l, 0, 16);
+        };
+#pragma unroll
+        for (int q = 0; q < DIST_SEL_CHUNKS; ++q) if ((int64_t)q * 16 < np_max) emit(rk[q], r64k[q], ck[q]);
+        for (int64_t q0 = 16 * DIST_SEL_CHUNKS; q0 < np_max; q0 += 16) {      // the rest of a long list (every item useful)
+            cf_dist_rec r; int32_t ux; uint32_t rel64;
+            fetch(q0, r, ux, rel64);
+            emit(r, rel64, (r.len + DIST_ITEM - 1u) / DIST_ITEM);
         }
-        if (on && gl == 0) heads[i] = cf_dist_head{(uint32_t)a, n, (unsigned long long)ib, (uint32_t)min(ne, 0x3FFFFFFFull), 0u, 0u, 0u};
+        if (on && gl == 0) {
+            heads[i] = cf_dist_head{(uint32_t)a, n, (unsigned long long)ib, (uint32_t)min(ne, 0x3FFFFFFFull), nA, 0u, 0u};
+#if defined(CF_DIST_DIAG_COUNT)
+            dg_a += nA; dg_n += n;
+#endif
+        }
     }
+#if defined(CF_DIST_DIAG_COUNT)
+    for (int d = 32; d >= 1; d >>= 1) { dg_a += __shfl_down(dg_a, (unsigned)d); dg_n += __shfl_down(dg_n, (unsigned)d); }
+    if ((threadIdx.x & 63) == 0 && dg_n) { atomicAdd(&diag[0], dg_a); atomicAdd(&diag[1], dg_n); }
+#else
+    (void)diag;
+#endif
 }
 
 // Sweeps one wave's items: recs = the wave's records in HBM, mine = how many, my0 = the first 64 of them already in registers
@@ -1259,7 +1353,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
     // 8-bit counters (sk) lie over ALL of it.  (The item records of the sweeps are in HBM: cf_items_fill_kernel.)
     const int t = threadIdx.x, lane = t & 63, nt = blockDim.x;
     uint32_t* bm = (uint32_t*)cf_lds_at(0u);                          // DIST_BM_BITS bits: hash(b) of the k-mers b that may have a selected edge
-    uint32_t* sh = bm + DIST_BM_BITS / 32;                     // [0] keys in table | DIST_FULL_BIT [1] first k-mer [2] sp [3] P [4] idx [5,6] queue ticket [7] E of pass [8] selected [9,10] edge base [11] hot-list cursor [12] items of the first k-mer [13] a counter of the sketch wrapped [14,15] where its item records start
+    uint32_t* sh = bm + DIST_BM_BITS / 32;                     // [0] keys in table | DIST_FULL_BIT [1] first k-mer [2] sp [3] P [4] idx [5,6] queue ticket [7] E of pass [8] selected [9,10] edge base [11] hot-list cursor [12] items of the first k-mer [13] a counter of the sketch wrapped [14,15] where its item records start [16..22] the next first k-mer's index and head [23] its useful items (the sketch sweep's) [26..29] the workgroup's chunk of the edge output [30] rows staged [31] a byte counter of the sketch wrapped
     unsigned char* lds_tab = cf_lds_at(DIST_LDS_HEAD);
     Tab T;
     T.init(lds_tab, (uint32_t)A.slots);
@@ -1317,7 +1411,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
     // Thread 0 fetches the NEXT first k-mer's head (ticket -> heads[]: two dependent round trips) while the workgroup works on
     // the current one; the values wait in its registers until the loop comes around.
     long long nx_idx = -1;
-    cf_dist_head nx_head{0u, 0u, 0ull, 0u, 0u, 0u, 0u};
+    cf_dist_head nx_head{0u, 0u, 0ull, 0u, 0u, 0u, 0u};      // (a, items, records, partner entries, useful items)
     unsigned long long nx_q = 0;
     if (!cf_lds_base_ok()) { if (t == 0) atomicOr(&A.counters[4], 2ull); return; }      // (cf_common.h: cf_lds_at)
     // Barriers.  A first k-mer whose table needs one pass — nearly all — meets the workgroup SEVEN times: [top] the previous
@@ -1332,6 +1426,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
         sh[16] = (uint32_t)(unsigned long long)nx_idx; sh[17] = (uint32_t)((unsigned long long)nx_idx >> 32);
         sh[18] = nx_head.a; sh[19] = nx_head.n_items; sh[20] = (uint32_t)nx_head.ibase; sh[21] = (uint32_t)(nx_head.ibase >> 32);
         sh[22] = nx_head.n_entries;      // partner entries (sizes the passes when every b is marked)
+        sh[23] = nx_head.n_useful;
     };
     auto pop_pass = [&]() {          // thread 0: the next partition of the stack becomes the pass
         const uint32_t sp = sh[2] - 1; sh[2] = sp; sh[3] = stack[2 * sp]; sh[4] = stack[2 * sp + 1]; sh[0] = 0; sh[7] = 0; sh[8] = 0; sh[11] = 0; sh[30] = 0;
@@ -1347,7 +1442,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
     while (true) {
         const int64_t ai = (int64_t)(((unsigned long long)sh[17] << 32) | sh[16]);
         if (ai < 0) break;
-        const uint32_t a = sh[18], n_items = sh[19], n_ent_a = sh[22];
+        const uint32_t a = sh[18], n_items = sh[19], n_ent_a = sh[22], n_useful = sh[23];
         // Round 6: the list of slots that reach min_cov (one returning LDS add, a wait and a readfirstlane per drain that has one — on
         // cenX-shaped reads every drain has a dozen) is not kept for a first k-mer that would overflow it anyway: its filter scans the count
         // fields, as it did all along once the list was full (12 of 108 ms there)
@@ -1359,6 +1454,8 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
         // this wave's item records: one coalesced load, in flight while the sketch is cleared; both sweeps run on them
         const uint32_t per_w = (n_items + nw - 1u) / nw;
         const uint32_t mine = CF_DIST_ITEMS_BLOCKED ? (n_items > wv * per_w ? min(per_w, n_items - wv * per_w) : 0u) : (wv < n_items ? (n_items - wv + nw - 1u) / nw : 0u);
+        // ... and how many of them the sketch sweep takes: the wave's share of the useful items, which come first in every wave's run
+        const uint32_t mineA = CF_DIST_ITEMS_BLOCKED ? (n_useful > wv * per_w ? min(per_w, n_useful - wv * per_w) : 0u) : (wv < n_useful ? (n_useful - wv + nw - 1u) / nw : 0u);
         const cf_dist_item* recs = A.items + ((((unsigned long long)sh[21] << 32) | sh[20]) + (unsigned long long)wv * per_w);
         cf_dist_item my0 = cf_dist_item{0u, 0u};
         if ((uint32_t)lane < min(mine, 64u)) my0 = recs[lane];
@@ -1401,7 +1498,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
                 __syncthreads();      // [sketch cleared]
             }
             {
-                if (CF_DIST_ABL < 6) cf_dist_sweep<Tab, CF_DIST_PF_A>(A, recs, mine, my0, [](bool) {}, [&](const uint32_t (&bb)[DIST_UNROLL], const uint32_t (&dd_)[DIST_UNROLL], const uint32_t (&qq_)[DIST_UNROLL], const uint32_t (&lo_)[DIST_UNROLL], uint32_t ok, uint32_t len) -> bool {
+                if (CF_DIST_ABL < 6) cf_dist_sweep<Tab, CF_DIST_PF_A>(A, recs, mineA, my0, [](bool) {}, [&](const uint32_t (&bb)[DIST_UNROLL], const uint32_t (&dd_)[DIST_UNROLL], const uint32_t (&qq_)[DIST_UNROLL], const uint32_t (&lo_)[DIST_UNROLL], uint32_t ok, uint32_t len) -> bool {
                     if (CF_DIST_ABL >= 5) { if (bb[0] == 0xFFFFFFF1u && dd_[0] == 77u) sh[13] = 1u; return false; }      // (the loads stay: their data is looked at)
                     // (entries equal to a are counted too: the sketch may only over-count, and the table sweep drops them)
                     uint32_t old_[DIST_UNROLL], sft_[DIST_UNROLL], inc_[DIST_UNROLL];
@@ -2014,7 +2111,7 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     unsigned long long* d_cnt = nullptr;
     int64_t n_post = 0;
     unsigned long long h_cnt[8] = {0};
-    const size_t n_cnt = 8 + 16 * 9;   // counters + 8 queue heads on their own cache lines
+    const size_t n_cnt = 8 + 16 * 9;   // counters + 8 queue heads on their own cache lines; [144] a cloud row is not a set (cf_entry_unit_kernel) [145, 146] diagnostic build: useful items, items
     const int max_blocks = std::max(1, ctx->n_cu) * 8;
     cf_free_edges(ctx);      // (the buffer of this call is allocated below, once the launch shape is known)
     cf_scratch tmp(ctx);
@@ -2121,7 +2218,7 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     else CF_TRY(tmp.get(&d_entry_i, (size_t)v_n_entries + 1, "entry unit indices"));
     if (U && v_n_entries)
         hipLaunchKernelGGL(cf_entry_unit_kernel, dim3((unsigned)cf_grid_for(U * 64, 256, max_blocks)), dim3(256), 0, ctx->stream,
-                           v_cloud_ptr, (const int32_t*)d_rbeg, v_entries, U, d_entry_i, d_packed, region26 ? 26 : 32 - narrow_db, d_entry_i8);
+                           v_cloud_ptr, (const int32_t*)d_rbeg, v_entries, U, d_entry_i, d_packed, region26 ? 26 : 32 - narrow_db, d_entry_i8, d_cnt + 144);
     CF_KERNEL_CHECK("the postings kernels");
     CF_HIP(hipEventRecord(ctx->ev2, ctx->stream));
 
@@ -2224,7 +2321,8 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         CF_TRY(tmp.get(&d_items, (size_t)n_item_slots + 64, "item records"));
         hipLaunchKernelGGL(cf_items_fill_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_order, (const int64_t*)d_post_ptr,
                            (const int32_t*)d_post, (const cf_dist_rec*)d_urange, nw, (const uint32_t*)d_icnt, (const int64_t*)d_ibase, d_heads, d_items,
-                           region26 ? v_cloud_ptr : (const int64_t*)nullptr, U);
+                           v_cloud_ptr, region26 ? 1 : 0, U, min_d_eff, max_d, min_cov, (ctx->dist_sketch_tail && A.sketch) ? 1 : 0,
+                           (const unsigned long long*)(d_cnt + 144), d_cnt + 145);
     }
     A.heads = d_heads; A.items = d_items;
     const int64_t n_a = n_order;
@@ -2260,6 +2358,9 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         unsigned long long st[8];
         if (hipMemcpy(st, d_cnt + 8, 64, hipMemcpyDeviceToHost) == hipSuccess)
             std::fprintf(stderr, "[cf_dist diag] parked-insert loop trips=%llu overflow calls=%llu parked inserts run=%llu drains=%llu inserts drained=%llu cycles(sum over waves): parked runs=%llu drains=%llu table sweeps=%llu; waves=%d passes=%llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], grid * (block / 64), h_cnt[5]);
+        unsigned long long su[3];      // [0] a cloud row is not a set [1] sum of the useful items [2] sum of the items
+        if (hipMemcpy(su, d_cnt + 144, 24, hipMemcpyDeviceToHost) == hipSuccess)
+            std::fprintf(stderr, "[cf_dist diag] sketch items=%llu of items=%llu (rows are sets=%d)\n", su[1], su[2], su[0] ? 0 : 1);
     }
 #endif
 #if defined(CF_DIST_STAMPS)
