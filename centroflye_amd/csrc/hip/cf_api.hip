@@ -259,6 +259,7 @@ void cf_free_clouds(cf_ctx* c) {
     cf_release_t(c, c->d_cloud_ptr, (size_t)c->n_units + 1);
     cf_release_t(c, c->d_entries, (size_t)c->n_entries);
     c->n_entries = 0; c->have_clouds = false;
+    c->cloud_max_entries = -1; c->read_max_entries = -1;
 }
 void cf_free_edges(cf_ctx* c) {
     cf_release_t(c, c->d_edges, (size_t)c->edge_cap * 4);
@@ -441,6 +442,14 @@ int cf_set_clouds(cf_ctx* ctx, const int64_t* cloud_ptr, const int32_t* entries,
     CF_TRY(cf_alloc_t(ctx, &ctx->d_entries, (size_t)n_entries, "cloud entries"));
     CF_TRY(cf_copy_h2d(ctx, ctx->d_cloud_ptr, cloud_ptr, (size_t)(ctx->n_units + 1) * 8));
     CF_TRY(cf_copy_h2d(ctx, ctx->d_entries, entries, (size_t)n_entries * 4));
+    // caller-made clouds are not bounded by the length of their units: the placement's packed counters (cf_place2_fits) go by what
+    // is installed
+    int64_t cloud_max = 0, read_max = 0;
+    for (int64_t u = 0; u < ctx->n_units; ++u) cloud_max = std::max(cloud_max, cloud_ptr[u + 1] - cloud_ptr[u]);
+    if ((int64_t)ctx->h_unit_ptr.size() == ctx->n_reads + 1)
+        for (int64_t r = 0; r < ctx->n_reads; ++r) read_max = std::max(read_max, cloud_ptr[ctx->h_unit_ptr[(size_t)r + 1]] - cloud_ptr[ctx->h_unit_ptr[(size_t)r]]);
+    else read_max = n_entries;
+    ctx->cloud_max_entries = cloud_max; ctx->read_max_entries = read_max;
     ctx->have_clouds = true;
     ctx->stats.n_cloud_entries = n_entries;
     return 0;

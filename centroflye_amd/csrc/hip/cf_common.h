@@ -111,6 +111,11 @@ struct cf_ctx {
     int32_t* d_entries = nullptr;
     int64_t n_entries = 0;
     bool have_clouds = false;
+    // what cf_place2_fits needs of the INSTALLED clouds: the entries of the largest cloud and of the read with most of them.
+    // -1 = not measured: clouds of cf_build_clouds, which hold at most one entry per window of their unit, so max_unit_len bounds
+    // a cloud and units x max_unit_len a read.  cf_set_clouds takes any CSR and measures it; cf_filter_clouds only removes entries,
+    // so either bound stays valid across it; cf_allgather_clouds fills the distance stage's view (g_*) and leaves these clouds alone.
+    int64_t cloud_max_entries = -1, read_max_entries = -1;
 
     // multi-GPU (cf_exchange.hip): the transport, and the all-gathered clouds of every rank's reads — what the distance
     // stage works on when present (units in rank-major order; reads and bases stay those of the local shard)

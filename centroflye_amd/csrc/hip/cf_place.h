@@ -150,6 +150,6 @@ __device__ __forceinline__ cf_key cf_block_best_key(cf_key mine) {
 __device__ __forceinline__ cf_cand cf_block_best(const cf_key& mine) { return cf_cand_of(cf_block_best_key(mine)); }
 
 // cf_place2.hip
-bool cf_place2_fits(const cf_ctx* ctx);
+bool cf_place2_fits(const cf_ctx* ctx, std::string* why = nullptr);
 int cf_place2_run(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, int32_t min_freq, int32_t min_unit, int32_t min_inters, int32_t min_prop,
                   std::vector<int64_t>& o_read, std::vector<int64_t>& o_pos, std::vector<int32_t>& o_s0, std::vector<int32_t>& o_s1);

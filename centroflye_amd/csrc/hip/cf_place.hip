@@ -506,7 +506,14 @@ int cf_place_reads(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, int3
     // placement touches — measured at 10 000 reads, min_inters 1 / 2 / 3 / 5: 2 256 / 619 / 267 / 164 ms against 220 for the hash-map
     // path (35 s with --min-cloud-kmer-freq 1 on top: tools/place_sweep_check.py) — so small thresholds take the rounds 1-3 path.
     // (place_mode 3 forces the regions whatever the threshold: tests.)
-    if ((ctx->place_mode == 3 || (ctx->place_mode == 2 && min_inters >= 4)) && cf_place2_fits(ctx)) {
+    // (the hash-map path below keeps s0 and s1 in 32 bits each — s0 <= units of a read, s1 <= 2 x entries of a read, entry indices
+    // are int32 ranks in arrays of fewer than 2^40 — and the contig's counts in 32 bits <= reads: no read set that loads overflows them)
+    std::string why;
+    const bool regions = ctx->place_mode == 3 || (ctx->place_mode == 2 && min_inters >= 4);
+    const bool fits = regions && cf_place2_fits(ctx, &why);
+    // a read set whose counts do not fit the regions' packed counters takes the hash-map path; place_mode 3 never falls back and says why
+    if (regions && !fits && ctx->place_mode == 3) return cf_fail(ctx, -34, "cf_place_reads: the per-read score regions cannot take this read set: " + why);
+    if (fits) {
         std::vector<int64_t> o_read, o_pos;
         std::vector<int32_t> o_s0, o_s1;
         const int rc2 = cf_place2_run(ctx, cls, id_rank, min_cloud_kmer_freq, min_unit, min_inters, min_prop, o_read, o_pos, o_s0, o_s1);

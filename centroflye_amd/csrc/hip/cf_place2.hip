@@ -1106,16 +1106,29 @@ static int pl2_attempt(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, 
 }
 
 // can this read set take the round-4 path?  (packed postings [read | unit index] in 32 bits, entry offsets in 40 + 24 bits)
-bool cf_place2_fits(const cf_ctx* ctx) {
+// `why` (may be null): the reason when it cannot.
+bool cf_place2_fits(const cf_ctx* ctx, std::string* why) {
+    auto no = [&](const std::string& s) { if (why) *why = s; return false; };
+    if ((int64_t)ctx->h_unit_ptr.size() != ctx->n_reads + 1) return no("no unit table on the host");
     int64_t max_u = 1;
     for (int64_t r = 0; r < ctx->n_reads; ++r) max_u = std::max(max_u, ctx->h_unit_ptr[(size_t)r + 1] - ctx->h_unit_ptr[(size_t)r]);
     int ib = 1; while ((1ll << ib) < max_u) ++ib;
-    // the winner record packs a read's cloud-entry count into 24 bits (ext = e0 << 24 | n): a cloud has at most one entry per
-    // window of its unit, so units x longest unit bounds the entries of any read (such a read — a sequence of
-    // megabases, not a read — takes the hash-map path instead of being truncated)
-    if (max_u * std::max<int64_t>(ctx->max_unit_len, 1) >= (1ll << 24)) return false;
-    // (16-bit cells: a cell counts the events of one unit's k-mers at one offset, at most two per k-mer — seed and threshold)
-    return ib < 32 && 2 * ctx->max_unit_len < 65536 && ctx->n_reads <= (1ll << (32 - ib)) && ctx->n_entries < (1ll << 40) && (int64_t)ctx->h_unit_ptr.size() == ctx->n_reads + 1;
+    // Both bounds below go by the clouds that are INSTALLED.  Clouds of cf_build_clouds (also after cf_filter_clouds, which only
+    // removes entries) have at most one entry per window of their unit: max_unit_len bounds a cloud and units x max_unit_len a read.
+    // Clouds of cf_set_clouds are whatever the caller made of them — a cloud may be larger than its unit is long — and were measured
+    // when they were installed (cf_ctx::cloud_max_entries, read_max_entries).
+    const bool measured = ctx->cloud_max_entries >= 0;
+    const int64_t cloud_max = measured ? ctx->cloud_max_entries : ctx->max_unit_len;
+    const int64_t read_max = measured ? ctx->read_max_entries : max_u * std::max<int64_t>(ctx->max_unit_len, 1);
+    // the winner record packs a read's cloud-entry count into 24 bits (ext = e0 << 24 | n)  (such a read — a
+    // sequence of megabases, not a read — takes the hash-map path instead of being truncated)
+    if (read_max >= (1ll << 24)) return no("a read of " + std::to_string(read_max) + " cloud entries (the winner record counts them in 24 bits)");
+    // 16-bit cells: a cell counts the events of ONE cloud's k-mers at one offset, at most two per k-mer and stage (the seed, and
+    // the pair reaching the threshold later: the reference's seed is over-inclusive) — given that a rank occurs once per cloud
+    if (2 * cloud_max >= 65536) return no("a cloud of " + std::to_string(cloud_max) + " entries (a 16-bit score cell takes two hits per entry: 32 767 at most)");
+    if (ib >= 32 || ctx->n_reads > (1ll << (32 - ib))) return no("read and unit index do not fit the 32 bits of a posting");
+    if (ctx->n_entries >= (1ll << 40)) return no("2^40 cloud entries or more");
+    return true;
 }
 
 int cf_place2_run(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, int32_t min_freq, int32_t min_unit, int32_t min_inters, int32_t min_prop,

@@ -120,7 +120,13 @@ int cf_build_clouds(cf_ctx* ctx, int64_t* n_entries);
 /* A4: keep k-mers present in [min_mult, max_mult] clouds overall (max_mult = 0: no upper bound). */
 int cf_filter_clouds(cf_ctx* ctx, uint32_t min_mult, uint32_t max_mult, int64_t* n_entries);
 int cf_get_clouds(cf_ctx* ctx, int64_t* cloud_ptr /* U+1 */, int32_t* entries, int64_t cap);
-/* Install clouds computed elsewhere (multi-GPU all-gather of per-shard clouds). */
+/* Install clouds computed elsewhere (multi-GPU all-gather of per-shard clouds; hand-built clouds of tests).  Any CSR over the loaded
+ * units is taken as it is and nothing is checked, so the caller has to keep: cloud_ptr (U + 1 values) starts at 0, never decreases
+ * and ends at n_entries; every entry is a rank < n_kmers of the installed k-mer set; a rank occurs at most once per cloud (the
+ * placement's "at most two hits per k-mer and score cell" and "nobody else lays this (k-mer, position) pair down in this launch" and
+ * the distance stage's tail items rest on it; cf_dist_edges notices a repeated rank, cf_place_reads does not).  A cloud MAY hold more
+ * entries than its unit has bases: the call measures the largest cloud and the most entries of one read, and cf_place_reads goes by
+ * those figures (below). */
 int cf_set_clouds(cf_ctx* ctx, const int64_t* cloud_ptr, const int32_t* entries, int64_t n_entries);
 
 /* A5+A6: for first k-mers a with a % n_parts == part: histogram over (b, d) of the reads
@@ -158,7 +164,13 @@ int cf_reset_unique(cf_ctx* ctx);
 
 /* A8+A9: greedy placement.  cls[r]: 0 prefix, 1 internal, 2 suffix; id_rank[r] = rank of the
  * read id in ascending string order (tie-break).  Outputs, in the order the reference writes
- * the file: out_read[i], out_pos[i] (-1 = None), out_s0[i], out_s1[i] for i < R. */
+ * the file: out_read[i], out_pos[i] (-1 = None), out_s0[i], out_s1[i] for i < R.
+ * Counter widths.  The per-read score regions ("place_mode" 2 and 3) count the hits of one (read, offset, unit) in 16 bits — at most
+ * two per entry of the unit's cloud and stage, so clouds of up to 32 767 entries fit — and a read's cloud entries in 24 bits.  Both are
+ * checked against the installed clouds (cf_build_clouds: bounded by the longest unit; cf_set_clouds: measured): a read set beyond them
+ * takes the hash-map path under mode 2, as one with small thresholds does, and returns -34 with the reason under mode 3.  The hash-map
+ * path ("place_mode" 1) keeps s0, s1 and the contig's counts in 32 bits each: s0 <= units of a read, s1 <= 2 x cloud entries of a read,
+ * a count <= reads — nothing that can be loaded overflows them. */
 int cf_place_reads(cf_ctx* ctx, const uint8_t* cls, const int32_t* id_rank, int32_t min_cloud_kmer_freq,
                    int32_t min_unit, int32_t min_inters, int32_t min_prop,
                    int64_t* out_read, int64_t* out_pos, int32_t* out_s0, int32_t* out_s1);
