@@ -87,6 +87,8 @@ def lib():
     L.cfh_write_edges.argtypes = [C.c_char_p, C.c_int, C.c_void_p, i32, C.c_void_p, i64, C.c_char_p, C.c_int]
     L.cfh_read_kmers.argtypes = [C.c_char_p, i32, C.c_void_p, i64, pi64, C.c_char_p, C.c_int]
     L.cfh_export_read_units.argtypes = [P, C.c_void_p, C.c_void_p, i64, i64, i64, C.c_char_p, C.c_int, pi64, pi64, C.c_char_p, C.c_int]
+    L.cfh_write_ualign_report.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, i64, pi64, C.c_char_p, C.c_int]
     _lib = L
     return L
 
@@ -361,6 +363,30 @@ def hw_locate(query, target):
     if rc != 0:
         raise HostError(f"cfh_hw_locate failed ({rc})")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def write_ualign_report(path, header, unit, names, reads, read_off, hits, op_ptr, ops, min_length=500):
+    """The report of the built-in tandem aligner (cfh_write_ualign_report): one record per read whose hit spans at least min_length
+    read bytes, in input order, behind `header`.  names: the reads' ids (bytes); hits / op_ptr / ops: Engine.ualign_run's.  Returns the
+    number of records written."""
+    unit = np.frombuffer(bytes(unit), np.uint8)
+    reads = np.ascontiguousarray(reads, np.uint8)
+    read_off = np.ascontiguousarray(read_off, np.int64)
+    id_off = np.zeros(len(names) + 1, np.int64)
+    np.cumsum([len(x) for x in names], out=id_off[1:])
+    ids = np.frombuffer(b"".join(names) + b"\0", np.uint8)
+    hits = np.ascontiguousarray(hits)
+    op_ptr = np.ascontiguousarray(op_ptr, np.int64)
+    ops = np.ascontiguousarray(ops, np.uint8)
+    if hits.size != len(names) or read_off.size != len(names) + 1 or op_ptr.size != len(names) + 1 or hits.dtype.itemsize != 48:
+        raise ValueError("one name, one hit of 12 int32, one offset and one op pointer per read")
+    n = C.c_int64()
+    err = C.create_string_buffer(512)
+    _check(lib().cfh_write_ualign_report(os.fsencode(path), header.encode() if header else None, unit.ctypes.data, unit.size,
+                                         reads.ctypes.data, read_off.ctypes.data, ids.ctypes.data, id_off.ctypes.data, len(names),
+                                         hits.ctypes.data, op_ptr.ctypes.data, ops.ctypes.data if ops.size else None, int(min_length),
+                                         C.byref(n), err, 512), err)
+    return n.value
 
 
 def write_kmers(path, kmers, k):

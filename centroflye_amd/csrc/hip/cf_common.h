@@ -168,6 +168,13 @@ struct cf_ctx {
     std::vector<std::vector<int32_t>> cons_voting, cons_excluded;
     cf_consensus_shape cons_last{};
 
+    // results of the last cf_ualign_run (cf_ualign.hip), in host memory: the hits, the op strings as a CSR over its reads, and the
+    // run's shape and timings
+    std::vector<cf_ualign_hit> ualign_hits;
+    std::vector<int64_t> ualign_op_ptr;
+    std::vector<uint8_t> ualign_op_bytes;
+    cf_ualign_shape ualign_last{};
+
     // host <-> device copies of the caller's (pageable) buffers go through pinned staging slots, one per copy thread
     // (cf_api.hip: cf_copy_h2d / cf_copy_d2h)
     static constexpr int kCopyThreads = 16;      // slots; CF_COPY_THREADS (1 .. 16, default 16) picks how many are used
@@ -214,6 +221,7 @@ struct cf_ctx {
     int tandem_key_mode = 0;     // cf_tandem: 0 = 64-bit keys where (read in batch, code, position) fit them, 1 = keys or an error, 2 = 16-byte records
     int64_t tandem_batch_windows = 0;   // cf_tandem: windows per batch of whole reads (0 = 2^26; tests force borders inside small inputs)
     int64_t cons_batch_bytes = 0;       // cf_consensus: bytes of move areas per batch of pairs (0 = 2^30; tests force borders inside one position's reads)
+    int64_t ualign_batch_bytes = 0;     // cf_ualign: bytes of move areas per batch of pairs of the moves pass (0 = an eighth of the device's memory, 2^28 .. 2^34; tests force one pair per batch)
     int count_mode = 1;         // 1: sort and reduce (cf_count2.hip) when it applies; 0: the atomic table of round 1 (cf_count.hip)
     int count_bits = 0;          // bucket bits of the sort-and-reduce path; 0 = from the number of windows (tests force small / large values)
     int count_slots = 4096;

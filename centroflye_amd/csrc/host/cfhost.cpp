@@ -1438,6 +1438,81 @@ int cfh_write_edges(const char* path, int append, const uint64_t* rare, int32_t 
 // 2-bit code of A, C, G, T; 4 for every other byte
 static const struct Code2Table { unsigned char t[256]; Code2Table() { for (int i = 0; i < 256; ++i) t[i] = 4; t['A'] = 0; t['C'] = 1; t['G'] = 2; t['T'] = 3; } unsigned char operator[](unsigned char c) const { return t[c]; } } kCode2;
 
+int cfh_write_ualign_report(const char* path, const char* header, const uint8_t* unit, int32_t unit_len, const uint8_t* reads,
+                            const int64_t* read_off, const char* ids, const int64_t* id_off, int64_t n_reads, const int32_t* hits,
+                            const int64_t* op_ptr, const uint8_t* ops, int64_t min_length, int64_t* n_written,
+                            char* err, int errlen) {
+    if (n_written) *n_written = 0;
+    if (!path || !unit || unit_len < 1 || n_reads < 0 || !read_off || !id_off || (n_reads > 0 && (!hits || !op_ptr))) {
+        set_err(err, errlen, "cfh_write_ualign_report: bad arguments");
+        return -22;
+    }
+    // the reads that get a record, checked before anything is written
+    std::vector<int64_t> keep;
+    for (int64_t q = 0; q < n_reads; ++q) {
+        const int32_t* h = hits + 12 * q;
+        if (h[0] != 1) continue;
+        int64_t n_r = 0, n_m = 0;
+        bool ok = h[3] >= 0 && h[3] <= h[4] && h[4] <= read_off[q + 1] - read_off[q] && h[5] >= 0 && h[5] < unit_len && (h[1] == 0 || h[1] == 1) &&
+                  op_ptr[q + 1] - op_ptr[q] == h[7];
+        for (int64_t c = op_ptr[q]; ok && c < op_ptr[q + 1]; ++c) {
+            if (ops[c] > 3) ok = false;
+            n_r += ops[c] != 3;
+            n_m += ops[c] != 2;
+        }
+        if (!ok || n_r != h[4] - h[3] || n_m != h[6]) {
+            set_err(err, errlen, "cfh_write_ualign_report: the ops of read " + std::to_string(q) + " do not add up to its hit");
+            return -22;
+        }
+        if (h[4] - h[3] >= min_length) keep.push_back(q);
+    }
+    std::string fwd((const char*)unit, (size_t)unit_len), rev;
+    rc_copy(fwd.data(), fwd.size(), rev);
+    const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) { set_err(err, errlen, std::string("cannot open ") + path + " for writing"); return -2; }
+    int rc = 0;
+    if (header) {
+        const size_t n = std::strlen(header);
+        for (size_t off = 0; off < n && rc == 0;) {
+            const ssize_t w = ::write(fd, header + off, n - off);
+            if (w < 0) { if (errno == EINTR) continue; rc = -5; } else off += (size_t)w;
+        }
+    }
+    auto render = [&](int64_t lo, int64_t hi, std::vector<char>& out) {
+        char num[64];
+        for (int64_t x = lo; x < hi; ++x) {
+            const int64_t q = keep[(size_t)x];
+            const int32_t* h = hits + 12 * q;
+            const std::string& us = h[1] ? rev : fwd;
+            const uint8_t* r = reads + read_off[q];
+            const int64_t n_cols = op_ptr[q + 1] - op_ptr[q];
+            out.insert(out.end(), ids + id_off[q], ids + id_off[q + 1]);
+            int n = std::snprintf(num, sizeof num, " %lld %lldbp %lld-%lld ", (long long)(read_off[q + 1] - read_off[q]), (long long)(h[4] - h[3]),
+                                  (long long)h[3], (long long)h[4]);
+            out.insert(out.end(), num, num + n);
+            int64_t i = h[3];
+            for (int64_t c = 0; c < n_cols; ++c) out.push_back(ops[op_ptr[q] + c] == 3 ? '-' : (char)r[i++]);
+            out.push_back('\n');
+            out.insert(out.end(), fwd.begin(), fwd.end());
+            n = std::snprintf(num, sizeof num, "%c %lldbp score=%lld ", h[1] ? '-' : '+', (long long)h[6], (long long)h[2]);
+            out.insert(out.end(), num, num + n);
+            int64_t j = h[5];
+            for (int64_t c = 0; c < n_cols; ++c) {
+                if (ops[op_ptr[q] + c] == 2) { out.push_back('-'); continue; }
+                out.push_back(us[(size_t)j]);
+                j = j + 1 == unit_len ? 0 : j + 1;
+            }
+            out.push_back('\n');
+            out.push_back('\n');
+        }
+    };
+    if (rc == 0) rc = write_ordered(fd, (int64_t)keep.size(), 64, render);
+    if (::close(fd) != 0 && rc == 0) rc = -5;
+    if (rc != 0) { set_err(err, errlen, std::string("write to ") + path + " failed"); return rc; }
+    if (n_written) *n_written = (int64_t)keep.size();
+    return 0;
+}
+
 int cfh_read_kmers(const char* path, int32_t k, uint64_t* out, int64_t cap, int64_t* n_out,
                    char* err, int errlen) {
     if (k < 1 || k > 32) { set_err(err, errlen, "cfh_read_kmers: k out of range"); return -22; }

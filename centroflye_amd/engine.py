@@ -542,6 +542,47 @@ class Engine:
         d["phase_ms"] = dict(zip(("copies", "align", "vote", "compact", "total"), (float(x) for x in s.phase_ms)))
         return d
 
+    # ------------------------------------------------------------------ the built-in tandem aligner (cf_ualign.hip)
+    UALIGN_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.UalignHit._fields_])
+
+    def ualign_run(self, unit, reads, read_off, match=10, mismatch=35, gap=33):
+        """Every read reads[read_off[i]:read_off[i + 1]] against the unit read cyclically, both strands, the best stretch per read
+        (the rule: include/cfhip.h at cf_ualign_run).  Returns (hits, op_ptr, ops): a structured array (UALIGN_DTYPE: status, strand,
+        score, r_st, r_en, u_st, m_al_len, n_ops, n_match, n_mismatch, n_ins, n_del), one row per read, and the alignment columns
+        as a CSR over the reads (uint8: 0 match, 1 mismatch, 2 read byte against '-', 3 '-' against unit base)."""
+        unit = np.frombuffer(bytes(unit), dtype=np.uint8)
+        reads = np.frombuffer(reads, np.uint8) if isinstance(reads, (bytes, bytearray, memoryview)) else np.ascontiguousarray(reads, np.uint8)
+        read_off = np.ascontiguousarray(read_off, np.int64).reshape(-1)
+        if read_off.size < 1:
+            raise ValueError("read_off has one entry per read and one more")
+        if int(read_off.max()) > reads.size:
+            raise ValueError("an offset lies beyond the bytes")
+        n = read_off.size - 1
+        hits = np.zeros(n, self.UALIGN_DTYPE)
+        ms = C.c_float()
+        self._check(self._lib.cf_ualign_run(self._ctx, _ptr(unit) if unit.size else None, int(unit.size), _ptr(reads) if reads.size else None,
+                                            _ptr(read_off), n, int(match), int(mismatch), int(gap), _ptr(hits) if n else None, C.byref(ms)), "cf_ualign_run")
+        ptr, ops = self.ualign_ops()
+        return hits, ptr, ops
+
+    def ualign_ops(self):
+        """(ptr int64[n_reads + 1], ops uint8): the alignment columns of every read of the last ualign_run, from r_st on."""
+        n = C.c_int64()
+        self._check(self._lib.cf_ualign_ops(self._ctx, None, None, 0, C.byref(n)), "cf_ualign_ops")
+        ptr = np.zeros(self.ualign_info()["n_reads"] + 1, np.int64)
+        ops = np.zeros(max(n.value, 1), np.uint8)
+        self._check(self._lib.cf_ualign_ops(self._ctx, _ptr(ptr), _ptr(ops), n.value, C.byref(n)), "cf_ualign_ops")
+        return ptr, ops[:n.value]
+
+    def ualign_info(self):
+        """The shape of cf_ualign.hip (max_unit, cols_per_thread, block, row_chunk, launch_cap, batch_bytes), the figures of the last
+        run (n_reads, n_score_pairs, n_move_pairs, n_batches) and its device milliseconds per phase."""
+        s = _lib.UalignShape()
+        self._check(self._lib.cf_ualign_info(self._ctx, C.byref(s)), "cf_ualign_info")
+        d = {n: int(getattr(s, n)) for n, _ in s._fields_ if n != "phase_ms"}
+        d["phase_ms"] = dict(zip(("copies", "score", "moves", "total"), (float(x) for x in s.phase_ms)))
+        return d
+
     # ------------------------------------------------------------------ self tests of primitives
     def selftest_sort(self, keys, bits=64):
         keys = np.ascontiguousarray(keys, np.uint64)

@@ -338,6 +338,61 @@ int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off
 int cf_consensus_get(cf_ctx* ctx, int32_t iter, uint8_t* out_bytes, int64_t* out_off, int32_t* n_voting, int32_t* n_excluded);
 int cf_consensus_info(cf_ctx* ctx, cf_consensus_shape* out);
 
+/* The built-in tandem aligner (cf_ualign.hip): every read against the unit read cyclically, the best stretch per read.  It stands
+ * in for the external NCRF binary the reference starts per chunk of reads (scripts/run_ncrf_parallel.py:49-62) and has NO
+ * reference function behind it: it is not NCRF, does not use NCRF's scoring and does not claim NCRF's output.  The rule below
+ * is the specification (tests/ualigncheck.py restates it).
+ * cf_ualign_run: the unit u of m = unit_len (1 .. max_unit) upper-case A, C, G, T; read q is reads[read_off[q], read_off[q + 1])
+ * (n bytes, any bytes; offsets non-decreasing and >= 0); match M, mismatch X, gap G, all >= 1.
+ *   w(x, y) = +M if (x with bit 5 cleared when it is a letter a .. z, i.e. toupper(x)) == y, else -X: N and every other byte
+ *   that is not A, C, G, T after upper-casing is a mismatch.  The "+" problem aligns r to u, the "-" problem r to RC(u).
+ *   Columns j = 0 .. m - 1 with p(j) = (j - 1) mod m, rows i = 0 .. n, S[0][j] = 0:
+ *     A[i][j] = max(0, S[i-1][p(j)] + w(r[i-1], u[j]), S[i-1][j] - G)
+ *     S[i][j] = max(A[i][j], max over 1 <= t < m of A[i][(j - t) mod m] - t G)
+ *   (local alignment with linear gaps on a cylinder; a horizontal run around the whole unit costs m G and is dominated).
+ *   The end cell is the cell of largest S over both strands; ties go to "+" before "-", then to the smallest i, then to the
+ *   smallest j.  Value 0: the read has no hit.  The walk back from the end cell stops at a cell with S == 0; otherwise it takes
+ *   (a) the diagonal if S[i-1][p(j)] + w(r[i-1], u[j]) == S[i][j]: column (r[i-1], u[j]); (b) else the vertical if
+ *   S[i-1][j] - G == S[i][j]: column (r[i-1], '-'); (c) else the horizontal to (i, p(j)): column ('-', u[j]).
+ * hits[n_reads]: status (CF_UALIGN_NONE / CF_UALIGN_HIT), strand (0 "+", 1 "-"), score (the end cell's value), r_st and r_en
+ * (the stop row and the end row: the read's bytes [r_st, r_en)), u_st (index in u, or in RC(u) for "-", of the unit base of the
+ * first alignment column; the first column is always a diagonal), m_al_len (unit bases on the row), n_ops (alignment columns)
+ * and n_match, n_mismatch, n_ins (rule b: read bytes against '-') and n_del (rule c: unit bases against '-').  A read without
+ * a hit has status 0 and every other field 0.  At most ONE record per read: a read whose array is interrupted gets its best
+ * stretch only.  *ms (may be NULL): device milliseconds of the call, copies included.
+ * The device runs two passes, one workgroup per pair, a thread holding cols_per_thread consecutive columns of the current row
+ * in registers: the score pass over every (read, strand) keeps the best cell and stores nothing per cell; the moves pass fills
+ * the winning strand of every read with a hit again, rows 1 .. r_en only, writes the move of every cell (2 bits) to the pair's
+ * area of scratch and walks back.  Pairs of the moves pass go through in batches whose areas stay under the knob
+ * "ualign_batch_bytes" (a pair that does not fit alone is taken alone).  Scores are int32: a read with n M >= 2^31 is refused.
+ * Nothing is added to cf_times or cf_stats.  Errors (-22: null pointers, decreasing or negative offsets, unit_len outside
+ * 1 .. max_unit, a unit byte that is not upper-case A, C, G, T, a score below 1, n M >= 2^31, n_reads < 0 or >= 2^30) leave the
+ * context and the results of the call before as they were.  n_reads = 0 and empty reads are allowed.
+ * cf_ualign_ops: the alignment columns of the last run as a CSR over its reads, in read order from r_st on: one byte per column,
+ * CF_UALIGN_MATCH, _MISMATCH, _INS, _DEL.  *n_out = the number of bytes; ptr == ops == NULL asks for it alone; otherwise
+ * cap >= *n_out, ptr[n_reads + 1].
+ * cf_ualign_info: the shape the tests straddle and the last run's figures.  phase_ms: copies to and from the device, the score
+ * pass, the moves pass with its walks, the whole call; by HIP events. */
+enum { CF_UALIGN_NONE = 0, CF_UALIGN_HIT = 1 };
+enum { CF_UALIGN_MATCH = 0, CF_UALIGN_MISMATCH = 1, CF_UALIGN_INS = 2, CF_UALIGN_DEL = 3 };
+typedef struct cf_ualign_hit {
+    int32_t status, strand, score, r_st, r_en, u_st, m_al_len, n_ops, n_match, n_mismatch, n_ins, n_del;
+} cf_ualign_hit;
+typedef struct cf_ualign_shape {
+    int64_t max_unit;                     /* bases of the longest unit taken                                          */
+    int64_t cols_per_thread, block;       /* columns of a row per thread; threads per workgroup at most (a launch takes the
+                                             multiple of 64 that holds the unit)                                      */
+    int64_t row_chunk;                    /* read bytes staged in LDS at a time                                       */
+    int64_t launch_cap;                   /* workgroups of a launch at most                                           */
+    int64_t batch_bytes;                  /* move areas per batch in force (knob "ualign_batch_bytes", 0 = an eighth of the device's memory, 2^28 .. 2^34)      */
+    int64_t n_reads, n_score_pairs, n_move_pairs, n_batches; /* of the last run                                       */
+    float phase_ms[4];
+} cf_ualign_shape;
+int cf_ualign_run(cf_ctx* ctx, const uint8_t* unit, int32_t unit_len, const uint8_t* reads, const int64_t* read_off, int64_t n_reads,
+                  int32_t match, int32_t mismatch, int32_t gap, cf_ualign_hit* hits, float* ms);
+int cf_ualign_ops(cf_ctx* ctx, int64_t* ptr, uint8_t* ops, int64_t cap, int64_t* n_out);
+int cf_ualign_info(cf_ctx* ctx, cf_ualign_shape* out);
+
 int cf_get_stats(cf_ctx* ctx, cf_stats* out);
 int cf_get_times(cf_ctx* ctx, cf_times* out);
 
@@ -376,7 +431,7 @@ int cf_allreduce_unique(cf_ctx* ctx, int64_t* n_unique);
 /* Tuning knobs (defaults are chosen for gfx950): name in {"dist_block" (threads per workgroup, 0 = auto), "dist_wgs"
  * (workgroups per CU the LDS is split between, 0 = auto: by the pair emissions per first k-mer), "dist_slots" (LDS budget of the (b,d) table in 8-byte units, 0 = all that
  * is left), "dist_sketch" (0: every pair goes to the exact table), "dist_sketch_tail" (1, the default: the sketch sweep leaves out the items beyond the largest distance at which min_cov postings of the first k-mer still have a partner unit; 0: it takes every item, in the order of the posting list), "dist_fill_pct", "dist_est_pct", "dist_stage", "dist_edge_chunk" (edge rows a workgroup reserves in the output per global atomic, 0 = 8192; tests use small chunks), "dist_int_thr" (0: the dominance test always divides in doubles; 1, the default: the literal 0.8 is tested as 5 cnt >= 4 total, which is the same predicate),
- * "dist_wide", "dist_post_atomics" (1: postings by a histogram and a fill pass of atomics instead of the sort), "dist_hot_cap" (tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan), "dist_sketch_bits" (bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the counters in the same LDS —, else 8; 8 forces bytes), "lut_shift" (the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1, the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0), "dist_hot_entries" (default 32768: first k-mers with more partner entries than this keep no list of hot slots during their inserts — it would overflow — and their filter scans the count fields; -1: always keep it), "dist_regions" (1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long reads take by themselves), "dist_dbits" (5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks need), "place_mode" (2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4; smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the hash-map path of rounds 1-3, cf_place.hip), "place_grid" / "place_block" (workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024), "place_row_words" (32 or 64 words per posting row, 0 = by the longest posting list), "place_slots_per_unit" (score-region slots per unit of a read, 0 = 48; grown automatically when a region fills), "place_l3" / "place_l3_shift" (1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily — built in round 5, measured neutral at 500 000 reads, off by default), "dist_region_bytes" (1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond 128 units do by themselves), "place_long_rescans" (default 2: a run of the region path whose reads average more than this many rescans of reads with more than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is handed to the hash-map path; -1: at the first look, tests), "place_cmap_bits" (log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 = cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load), "place_chunk", "place_fused" (place_mode 1: cloud entries per wave step; 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list and a third kernel per greedy iteration), "count_mode" (1: A1 by sort and reduce, 0: the atomic table), "count_bits" (bucket bits of the former, 0 = auto), "count_slots", "count_tile", "count_skip_exotic" (1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads), "comm_round_bytes" (bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds), "map_window" (candidate starts — LDS score slots — that cf_map_reads covers per pass over a read's cloud entries, 0 = 2048, at most 4096; a read whose hits span more starts takes several passes, tests force that with tiny windows), "edit_lds_diags" (cf_edit_distances: diagonals per wavefront array up to which a pair's wavefronts stay in LDS, 0 = 16384, at most 16384; tests force the HBM path with small values), "comm_self_p2p" (1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a one-GPU box runs the whole p2p path), "tandem_key_mode" and "tandem_batch_windows" (cf_tandem_scan: see there), "cons_batch_bytes" (cf_consensus_run: bytes of move areas per batch of pairs, 0 = 2^30, at most 2^36; a batch holds at least one pair; tests force many batches with small values)}.  Results never depend on them (tests/test_gpu_parity.py). */
+ * "dist_wide", "dist_post_atomics" (1: postings by a histogram and a fill pass of atomics instead of the sort), "dist_hot_cap" (tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan), "dist_sketch_bits" (bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the counters in the same LDS —, else 8; 8 forces bytes), "lut_shift" (the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1, the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0), "dist_hot_entries" (default 32768: first k-mers with more partner entries than this keep no list of hot slots during their inserts — it would overflow — and their filter scans the count fields; -1: always keep it), "dist_regions" (1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long reads take by themselves), "dist_dbits" (5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks need), "place_mode" (2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4; smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the hash-map path of rounds 1-3, cf_place.hip), "place_grid" / "place_block" (workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024), "place_row_words" (32 or 64 words per posting row, 0 = by the longest posting list), "place_slots_per_unit" (score-region slots per unit of a read, 0 = 48; grown automatically when a region fills), "place_l3" / "place_l3_shift" (1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily — built in round 5, measured neutral at 500 000 reads, off by default), "dist_region_bytes" (1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond 128 units do by themselves), "place_long_rescans" (default 2: a run of the region path whose reads average more than this many rescans of reads with more than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is handed to the hash-map path; -1: at the first look, tests), "place_cmap_bits" (log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 = cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load), "place_chunk", "place_fused" (place_mode 1: cloud entries per wave step; 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list and a third kernel per greedy iteration), "count_mode" (1: A1 by sort and reduce, 0: the atomic table), "count_bits" (bucket bits of the former, 0 = auto), "count_slots", "count_tile", "count_skip_exotic" (1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads), "comm_round_bytes" (bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds), "map_window" (candidate starts — LDS score slots — that cf_map_reads covers per pass over a read's cloud entries, 0 = 2048, at most 4096; a read whose hits span more starts takes several passes, tests force that with tiny windows), "edit_lds_diags" (cf_edit_distances: diagonals per wavefront array up to which a pair's wavefronts stay in LDS, 0 = 16384, at most 16384; tests force the HBM path with small values), "comm_self_p2p" (1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a one-GPU box runs the whole p2p path), "tandem_key_mode" and "tandem_batch_windows" (cf_tandem_scan: see there), "cons_batch_bytes" (cf_consensus_run: bytes of move areas per batch of pairs, 0 = 2^30, at most 2^36; a batch holds at least one pair; tests force many batches with small values), "ualign_batch_bytes" (cf_ualign_run: bytes of move areas per batch of pairs of its moves pass, 0 = an eighth of the device's memory between 2^28 and 2^34, at most 2^36; a batch holds at least one pair)}.  Results never depend on them (tests/test_gpu_parity.py). */
 int cf_set_param(cf_ctx* ctx, const char* name, int64_t value);
 
 /* Self-tests of the device primitives against host results (used by tests/ only). */

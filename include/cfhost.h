@@ -151,6 +151,20 @@ int cfh_export_read_units(cfh_pack* p, const int64_t* rec, const int64_t* pos, i
                           int64_t max_pos, const char* outdir, int n_threads, int64_t* n_positions,
                           int64_t* n_units_written, char* err, int errlen);
 
+/* The report of the built-in tandem aligner (cf_ualign_run of cfhip.h; scripts/run_ncrf_parallel.py --aligner builtin): `header`
+ * (may be NULL) first, then one record per read whose hit has r_en - r_st >= min_length, in the order of the reads, in the
+ * two-line format of the NCRF reports this library parses:
+ *   "<id> <read length> <r_en - r_st>bp <r_st>-<r_en> <r_al>" / "<unit><strand> <m_al_len>bp score=<score> <m_al>" / empty line.
+ * unit: unit_len upper-case A, C, G, T; read q = reads[read_off[q], read_off[q + 1]) with the name ids[id_off[q], id_off[q + 1]);
+ * hits: 12 int32 per read (cf_ualign_hit); op_ptr / ops: the alignment columns as a CSR over the reads.  r_al holds the read's
+ * own bytes, m_al the unit's bases (the reverse complement's for a "-" hit) read cyclically from u_st on, '-' in the gaps.
+ * Records are rendered by several threads and written in order.  *n_written (may be NULL): the records written.  -22: a hit
+ * whose ops do not add up to its interval. */
+int cfh_write_ualign_report(const char* path, const char* header, const uint8_t* unit, int32_t unit_len, const uint8_t* reads,
+                            const int64_t* read_off, const char* ids, const int64_t* id_off, int64_t n_reads, const int32_t* hits,
+                            const int64_t* op_ptr, const uint8_t* ops, int64_t min_length, int64_t* n_written,
+                            char* err, int errlen);
+
 /* Read a k-mer text file (one per line) into 2-bit codes; returns count via n_out, fills out
  * if non-NULL (size-query then fill). All k-mers must have length k and be ACGT. */
 int cfh_read_kmers(const char* path, int32_t k, uint64_t* out, int64_t cap, int64_t* n_out,
