@@ -20,6 +20,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "map_reads_cases.json")
 WRONG_RULES = ("seeds_only_where_frequent", "q_gt_i", "p_is_max_pos_plus_1", "smaller_start_on_ties", "s1_before_s0")
+DEFAULT_WINDOW = 2048      # slots of the score table under map_window 0 (CF_MAP_WINDOW_DEFAULT, CF_SCORE_WINDOW_DEFAULT)
 
 
 def _ranges(lo, hi):
@@ -194,5 +195,5 @@ def check_case(src, case, window=0, log=None):
     assert not bad, f"{tag} (window {window}): {len(bad)} reads differ from the reference, first {bad[:3]}"
     if log is not None:
         log.append(dict(case=tag, window=window, P=want["P"], mapped=sum(1 for x in expect if x[0] >= 0), reads=len(expect)))
-    info["multi_window_reads"] = sum(1 for r in query if hit_span(unit_ptr, cloud_ptr, entries, c, r) > (window or 2048))
+    info["multi_window_reads"] = sum(1 for r in query if hit_span(unit_ptr, cloud_ptr, entries, c, r) > (window or DEFAULT_WINDOW))
     return info

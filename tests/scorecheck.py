@@ -20,7 +20,7 @@ import os
 
 import numpy as np
 
-from mapcheck import _ranges
+from mapcheck import DEFAULT_WINDOW, _ranges
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "score_reads_cases.json")
@@ -187,7 +187,7 @@ def check_case(src, case, window=0):
     for m in SPREAD_MAX_NPOS:
         assert np.array_equal(e.contig_spread(m), spread(c, m)), f"{tag}: device spread k-mers, max_npos {m}"
     n_units = (np.asarray(unit_ptr)[q + 1] - np.asarray(unit_ptr)[q])
-    return int(((case["max_pos"] - n_units + 1 - 0 + 1) > (window or 2048)).sum())
+    return int(((case["max_pos"] - n_units + 1 - 0 + 1) > (window or DEFAULT_WINDOW)).sum())
 
 
 # ------------------------------------------------------------------ a hand-built CSR at the kernel's shape borders
@@ -230,7 +230,7 @@ def synthetic_reference(f=2):
     R = unit_ptr.size - 1
     c = contig(unit_ptr, cloud_ptr, entries, b_reads, b_pos, f)
     A = (unit_ptr, cloud_ptr, entries, c)
-    assert c["max_pos"] > 2 * 2048 and int(np.diff(cloud_ptr).max()) > 64
+    assert c["max_pos"] > 2 * DEFAULT_WINDOW and int(np.diff(cloud_ptr).max()) > 64
     rng = np.random.default_rng(3)
     lo = rng.integers(0, c["max_pos"] - 2500, R)
     hi = lo + rng.integers(0, 2500, R)                       # sub-ranges up to more than a window wide
