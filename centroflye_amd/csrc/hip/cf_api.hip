@@ -537,6 +537,11 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
         ctx->dist_sketch_bits = (int)value;
     } else if (n == "dist_sketch_tail") {
         ctx->dist_sketch_tail = value != 0;
+    } else if (n == "dist_classes") {
+        ctx->dist_classes = value != 0;
+    } else if (n == "dist_class_bits") {
+        if (value < 1 || value > 16) return cf_fail(ctx, -22, "dist_class_bits out of range (1 .. 16)");
+        ctx->dist_class_bits = (int)value;
     } else if (n == "dist_sketch") {
         ctx->dist_sketch = value != 0;
     } else if (n == "dist_est_pct") {

@@ -201,7 +201,12 @@ cf_entry_unit_kernel(const int64_t* __restrict__ cloud_ptr, const int32_t* __res
 // emulated rank's 23 ms of set-up (3.7e7 k-mers: 570 000 adds to one address, one after the other).
 __global__ void __launch_bounds__(256)
 cf_order_keys_kernel(const uint32_t* __restrict__ pcnt, const uint32_t* __restrict__ first_unit, int64_t n_kmers, int part, int n_parts, int ab,
-                     unsigned long long* __restrict__ keys, unsigned long long* __restrict__ n_out) {
+                     unsigned long long* __restrict__ keys, unsigned long long* __restrict__ n_out,
+                     int hb, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post, const unsigned long long* __restrict__ not_a_set) {
+    // hb > 0 (classes of first k-mers): hb bits of a hash of the k-mer's posting list stand between the first unit and the
+    // rank, so that the sort puts k-mers with equal lists next to each other (they share their first unit).  The hash only brings candidates
+    // together: cf_class_mark_kernel compares the lists.  Clouds that are not sets (cf_set_clouds) form no classes: the hash bits stay 0.
+    const bool hashed = hb > 0 && *not_a_set == 0ull;
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
@@ -226,7 +231,14 @@ cf_order_keys_kernel(const uint32_t* __restrict__ pcnt, const uint32_t* __restri
             const unsigned long long m = cf_ballot(take);
             if (take) {
                 const int64_t a = s0 + (int64_t)r * 64 + lane;
-                keys[base + (unsigned long long)__popcll(m & lt)] = ((unsigned long long)first_unit[a] << ab) | (unsigned long long)a;
+                unsigned long long h = 0;
+                if (hashed) {
+                    const int64_t p0 = post_ptr[a], p1 = post_ptr[a + 1];
+                    h = (unsigned long long)(p1 - p0);
+                    for (int64_t p = p0; p < p1; ++p) { h = (h ^ (unsigned long long)(uint32_t)post[p]) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; }
+                    h = (h * 0xBF58476D1CE4E5B9ull) >> (64 - hb);
+                }
+                keys[base + (unsigned long long)__popcll(m & lt)] = ((unsigned long long)first_unit[a] << (ab + hb)) | (h << ab) | (unsigned long long)a;
             }
             base += (unsigned long long)__popcll(m);
         }
@@ -236,6 +248,50 @@ __global__ void __launch_bounds__(256)
 cf_order_extract_kernel(const unsigned long long* __restrict__ keys, int64_t n, int ab, int32_t* __restrict__ order) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) order[i] = (int32_t)(keys[i] & ((1ull << ab) - 1ull));
+}
+
+// Classes of first k-mers.  cnt(a, b, d) depends on the first k-mer a only through its posting list, so the k-mers of the
+// launch with EQUAL lists share one sweep of cf_dist_kernel.  The sorted order keys [first unit | hash of the list | a] put candidates
+// next to each other; position i continues the class of i - 1 only when the two keys agree above the rank AND the two lists are equal in
+// length and in every unit (a hash collision may lose a merge — the sort may put a stranger between two equal lists — and never makes one).
+// The thread of a position that does not continue (the head of a run) walks its run and flags the start of every class: the head, and
+// every DIST_CLASS_CAP-th position after it (a longer run simply starts a new class).  flags[] is zeroed before the launch.
+#define DIST_CLASS_CAP 255u
+__device__ __forceinline__ bool cf_same_postings(const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post, uint32_t x, uint32_t y) {
+    const int64_t x0 = post_ptr[x], x1 = post_ptr[x + 1], y0 = post_ptr[y], y1 = post_ptr[y + 1];
+    if (x1 - x0 != y1 - y0) return false;
+    for (int64_t i = 0; i < x1 - x0; ++i) if (post[x0 + i] != post[y0 + i]) return false;
+    return true;
+}
+__global__ void __launch_bounds__(256)
+cf_class_mark_kernel(const unsigned long long* __restrict__ keys, int64_t n, int ab, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
+                     const unsigned long long* __restrict__ not_a_set, uint32_t* __restrict__ flags) {
+    const unsigned long long rank_mask = (1ull << ab) - 1ull;
+    const bool off = *not_a_set != 0ull;      // clouds that are not sets (read on the device, as cf_items_fill_kernel does): every k-mer its own class
+    auto continues = [&](int64_t i) -> bool {      // position i (>= 1) has the posting list of position i - 1
+        const unsigned long long k0 = keys[i - 1], k1 = keys[i];
+        return (k0 >> ab) == (k1 >> ab) && cf_same_postings(post_ptr, post, (uint32_t)(k0 & rank_mask), (uint32_t)(k1 & rank_mask));
+    };
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (off) { flags[i] = 1u; continue; }
+        if (i > 0 && continues(i)) continue;
+        flags[i] = 1u;
+        uint32_t run = 1;
+        for (int64_t j = i + 1; j < n && continues(j); ++j) {
+            if (run == DIST_CLASS_CAP) { flags[j] = 1u; run = 0; }
+            ++run;
+        }
+    }
+}
+// class c starts at position cfirst[c] of the order list; cfirst[n_classes] = n (cidx: the exclusive scan of flags)
+__global__ void __launch_bounds__(256)
+cf_class_first_kernel(const uint32_t* __restrict__ flags, const int64_t* __restrict__ cidx, int64_t n, int64_t n_classes, uint32_t* __restrict__ cfirst) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        if (flags[i]) cfirst[cidx[i]] = (uint32_t)i;
+        if (i == 0) cfirst[n_classes] = (uint32_t)n;
+    }
 }
 
 // One item = up to DIST_ITEM consecutive partner entries of one posting: what one wave takes per step.
@@ -252,7 +308,9 @@ struct alignas(8) cf_dist_item { uint32_t e, m; };
 #define CF_DIST_ITEMS_BLOCKED 0
 #endif
 // Items are numbered useful ones first: the sketch sweep takes the items 0 .. n_useful - 1 only, the table sweep all of them (cf_items_fill_kernel).
-struct alignas(16) cf_dist_head { uint32_t a, n_items; unsigned long long ibase; uint32_t n_entries, n_useful, pad1, pad2; };   // n_entries: partner entries (capped at 2^30 - 1)
+// A head stands for a CLASS of first k-mers with equal posting lists: a is its representative, n_members how many k-mers it has
+// (1 .. DIST_CLASS_CAP) and first_member where they stand, next to each other, in the launch's order list (a = order[first_member]).
+struct alignas(16) cf_dist_head { uint32_t a, n_items; unsigned long long ibase; uint32_t n_entries, n_useful, n_members, first_member; };   // n_entries: partner entries (capped at 2^30 - 1)
 
 struct cf_dist_args {
     const int64_t* post_ptr;
@@ -285,8 +343,8 @@ struct cf_dist_args {
     uint32_t hot_entries;          // first k-mers with more partner entries than this do not keep the list at all (it would overflow: the filter scans)
     uint32_t* edges;
     unsigned long long edge_cap;
-    const int32_t* order;          // first k-mers of this partition, sorted by their first posting (locality)
-    int64_t n_order;
+    const int32_t* order;          // first k-mers of this partition, sorted by their first posting (locality); the members of a class stand next to each other
+    int64_t n_order;               // heads of the launch: classes of first k-mers (every first k-mer of `order` when classes are off)
     unsigned long long edge_chunk; // edge rows a workgroup reserves per global atomic (DIST_EDGE_CHUNK; tests: small)
     unsigned long long* holes;     // (start, rows) of the unused rest of every workgroup's last chunk of the edge output
     unsigned long long* counters;  // [0] edge rows reserved (chunks) [6] selected edges [7] holes [1] partner entries swept [2] spilled a [3] (host: self pairs) [4] error flags [5] passes; [16 + 16 x] queue head x
@@ -463,6 +521,7 @@ struct cf_tab_wide_t {
             if ((v[i] >> kCntBits) & 1ull) f(4u * bk + (uint32_t)i, (uint32_t)(v[i] >> 32), ((uint32_t)v[i] >> kDShift) & kDMask, (uint32_t)v[i] & kCntMask);
     }
     __device__ __forceinline__ void mark(uint32_t s) const { atomicOr(&tab[s], 1ull << kCntBits); }
+    __device__ __forceinline__ void unmark(uint32_t s) const { atomicAnd(&tab[s], ~(1ull << kCntBits)); }      // (between the members of a class: DESIGN.md 24)
 };
 typedef cf_tab_wide_t<8> cf_tab_wide;
 typedef cf_tab_wide_t<16> cf_tab_wide16;
@@ -733,6 +792,7 @@ struct cf_tab_narrow_t {
         }
     }
     __device__ __forceinline__ void mark(uint32_t s) const { atomicOr(&cnt32[s >> 1], 0x8000u << ((s & 1u) * 16u)); }
+    __device__ __forceinline__ void unmark(uint32_t s) const { atomicAnd(&cnt32[s >> 1], ~(0x8000u << ((s & 1u) * 16u))); }
 };
 typedef cf_tab_narrow_t<8> cf_tab_narrow;
 
@@ -946,6 +1006,7 @@ struct cf_tab_region {
         }
     }
     __device__ __forceinline__ void mark(uint32_t s) const { atomicOr(&cnt32[s >> 1], 0x8000u << ((s & 1u) * 16u)); }
+    __device__ __forceinline__ void unmark(uint32_t s) const { atomicAnd(&cnt32[s >> 1], ~(0x8000u << ((s & 1u) * 16u))); }
 };
 
 // The region layout's table behind a FOUR-byte stream, for k-mer sets of 2^24 .. 2^26 ranks whose reads have at most 128 units
@@ -1058,19 +1119,22 @@ __device__ __forceinline__ uint32_t cf_dist_insert(const Tab& T, uint32_t n_buck
 __global__ void __launch_bounds__(256)
 cf_items_count_kernel(const int32_t* __restrict__ order, int64_t n_order, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
                       const cf_dist_rec* __restrict__ urange, const int32_t* __restrict__ rbeg, int32_t min_d, int32_t max_d, uint32_t nw, int sorted_post,
-                      uint32_t* __restrict__ n_items, uint32_t* __restrict__ n_alloc, unsigned long long* __restrict__ self_pairs) {
+                      uint32_t* __restrict__ n_items, uint32_t* __restrict__ n_alloc, unsigned long long* __restrict__ self_pairs, const uint32_t* __restrict__ cfirst) {
+    // cfirst != nullptr: n_order CLASSES; class i is the k-mers order[cfirst[i] .. cfirst[i + 1]) — equal posting lists — and order[cfirst[i]] stands
+    // for them (the self pairs are the same for every member: counted once, times the members).  nullptr: every k-mer of `order` on its own.
     const int gl = threadIdx.x & 15;
     const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const int64_t n_grp = ((int64_t)gridDim.x * blockDim.x) >> 4;
     unsigned long long self = 0;
     // (the first two links of an iteration's chain — order -> post_ptr — are fetched one iteration ahead)
     int64_t p0_n = 0, p1_n = 0;
-    { const int32_t a0 = grp < n_order ? order[grp] : 0; if (grp < n_order) { p0_n = post_ptr[a0]; p1_n = post_ptr[a0 + 1]; } }
+    { const int32_t a0 = grp < n_order ? order[cfirst ? (int64_t)cfirst[grp] : grp] : 0; if (grp < n_order) { p0_n = post_ptr[a0]; p1_n = post_ptr[a0 + 1]; } }
     for (int64_t i0 = 0; i0 < n_order; i0 += n_grp) {      // (uniform trip count: shuffles inside)
         const int64_t i = i0 + grp;
         const bool on = i < n_order;
         const int64_t p0 = p0_n, p1 = p1_n;
-        { const int64_t in = i + n_grp; p0_n = 0; p1_n = 0; if (in < n_order) { const int32_t an = order[in]; p0_n = post_ptr[an]; p1_n = post_ptr[an + 1]; } }
+        { const int64_t in = i + n_grp; p0_n = 0; p1_n = 0; if (in < n_order) { const int32_t an = order[cfirst ? (int64_t)cfirst[in] : in]; p0_n = post_ptr[an]; p1_n = post_ptr[an + 1]; } }
+        const unsigned long long self_before = self, members = (cfirst && on) ? (unsigned long long)(cfirst[i + 1] - cfirst[i]) : 1ull;
         unsigned long long c = 0;
         int64_t np_max = p1 - p0;      // the longest posting list among the wave's four groups bounds the loops
         for (int d = 16; d <= 32; d <<= 1) np_max = max(np_max, __shfl_xor(np_max, d));
@@ -1101,6 +1165,7 @@ cf_items_count_kernel(const int32_t* __restrict__ order, int64_t n_order, const 
                 }
             }
         }
+        self = self_before + (self - self_before) * members;
         for (int d = 8; d >= 1; d >>= 1) c += __shfl_down(c, (unsigned)d, 16);
         if (on && gl == 0) {
             const uint32_t n = (uint32_t)min(c, 0xFFFFFFFFull - 2048ull);
@@ -1134,7 +1199,9 @@ __global__ void __launch_bounds__(256)
 cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
                      const cf_dist_rec* __restrict__ urange, uint32_t nw, const uint32_t* __restrict__ n_items, const int64_t* __restrict__ ibase,
                      cf_dist_head* __restrict__ heads, cf_dist_item* __restrict__ items, const int64_t* __restrict__ cloud_ptr, int stream26, int64_t n_units,
-                     int32_t min_d, int32_t max_d, uint32_t min_cov, int tail, const unsigned long long* __restrict__ not_a_set, unsigned long long* __restrict__ diag) {
+                     int32_t min_d, int32_t max_d, uint32_t min_cov, int tail, const unsigned long long* __restrict__ not_a_set, unsigned long long* __restrict__ diag,
+                     const uint32_t* __restrict__ cfirst) {
+    // cfirst: as in cf_items_count_kernel — n_order classes, the work list of a class made from its representative's postings
     // stream26: the 26-bit stream (cf_tab_region26): the item record's low half is [t64 : 9 | unit index mod 128 : 7]
     const int gl = threadIdx.x & 15;
     const int64_t grp = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
@@ -1147,7 +1214,8 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
     unsigned long long dg_a = 0, dg_n = 0;
 #endif
     int32_t a_n = 0; int64_t p0_n = 0, p1_n = 0, ib_n = 0; uint32_t n_n = 0;      // (fetched one iteration ahead, as in cf_items_count_kernel)
-    if (grp < n_order) { a_n = order[grp]; p0_n = post_ptr[a_n]; p1_n = post_ptr[a_n + 1]; n_n = n_items[grp]; ib_n = ibase[grp]; }
+    uint32_t f_n = 0, m_n = 1;      // the class's first position in `order` and its members
+    if (grp < n_order) { f_n = cfirst ? cfirst[grp] : (uint32_t)grp; m_n = cfirst ? cfirst[grp + 1] - f_n : 1u; a_n = order[f_n]; p0_n = post_ptr[a_n]; p1_n = post_ptr[a_n + 1]; n_n = n_items[grp]; ib_n = ibase[grp]; }
     for (int64_t i0 = 0; i0 < n_order; i0 += n_grp) {      // (uniform trip count: shuffles inside)
         const int64_t i = i0 + grp;
         const bool on = i < n_order;
@@ -1155,8 +1223,9 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
         const int64_t p0 = p0_n, p1 = p1_n;
         const uint32_t n = n_n, per = (n + nw - 1u) / nw;
         const int64_t ib = ib_n;
-        { const int64_t in = i + n_grp; a_n = 0; p0_n = 0; p1_n = 0; n_n = 0; ib_n = 0;
-          if (in < n_order) { a_n = order[in]; p0_n = post_ptr[a_n]; p1_n = post_ptr[a_n + 1]; n_n = n_items[in]; ib_n = ibase[in]; } }
+        const uint32_t c_first = f_n, c_members = m_n;
+        { const int64_t in = i + n_grp; a_n = 0; p0_n = 0; p1_n = 0; n_n = 0; ib_n = 0; f_n = 0; m_n = 1;
+          if (in < n_order) { f_n = cfirst ? cfirst[in] : (uint32_t)in; m_n = cfirst ? cfirst[in + 1] - f_n : 1u; a_n = order[f_n]; p0_n = post_ptr[a_n]; p1_n = post_ptr[a_n + 1]; n_n = n_items[in]; ib_n = ibase[in]; } }
         cf_dist_item* out = items + ib;
         int64_t np_max = p1 - p0;
         for (int d = 16; d <= 32; d <<= 1) np_max = max(np_max, __shfl_xor(np_max, d));
@@ -1236,7 +1305,7 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
             emit(r, rel64, (r.len + DIST_ITEM - 1u) / DIST_ITEM);
         }
         if (on && gl == 0) {
-            heads[i] = cf_dist_head{(uint32_t)a, n, (unsigned long long)ib, (uint32_t)min(ne, 0x3FFFFFFFull), nA, 0u, 0u};
+            heads[i] = cf_dist_head{(uint32_t)a, n, (unsigned long long)ib, (uint32_t)min(ne, 0x3FFFFFFFull), nA, c_members, c_first};
 #if defined(CF_DIST_DIAG_COUNT)
             dg_a += nA; dg_n += n;
 #endif
@@ -1346,14 +1415,18 @@ __device__ __forceinline__ void cf_dist_sweep(const cf_dist_args& A, const cf_di
 #define CF_DIST_LB_THREADS 1024
 #define CF_DIST_LB_BLOCKS 1
 #endif
-template <class Tab>
+// CLS: the launch has classes of first k-mers — the heads' n_members may exceed 1 and the section from the filter to the
+// rows runs once per member.  A launch without classes (knob dist_classes 0, postings from the atomics' fill pass) takes the instance
+// without the member loop: the kernel it had before, instruction for instruction — with the loop in it, a launch of singletons
+// ran 9 ms of 243 behind that kernel (14 registers spilled where there were none).
+template <class Tab, bool CLS>
 __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist_kernel(cf_dist_args A) {
     // LDS: [bitmap | sh] at FIXED offsets (the bitmap at 0: its word address is the hash bits themselves, no base to add), then
     // [table | edge stage | partition stack | insert queues].  The table group is dead while the sketch sweep runs, so its
     // 8-bit counters (sk) lie over ALL of it.  (The item records of the sweeps are in HBM: cf_items_fill_kernel.)
     const int t = threadIdx.x, lane = t & 63, nt = blockDim.x;
     uint32_t* bm = (uint32_t*)cf_lds_at(0u);                          // DIST_BM_BITS bits: hash(b) of the k-mers b that may have a selected edge
-    uint32_t* sh = bm + DIST_BM_BITS / 32;                     // [0] keys in table | DIST_FULL_BIT [1] first k-mer [2] sp [3] P [4] idx [5,6] queue ticket [7] E of pass [8] selected [9,10] edge base [11] hot-list cursor [12] items of the first k-mer [13] a counter of the sketch wrapped [14,15] where its item records start [16..22] the next first k-mer's index and head [23] its useful items (the sketch sweep's) [26..29] the workgroup's chunk of the edge output [30] rows staged [31] a byte counter of the sketch wrapped
+    uint32_t* sh = bm + DIST_BM_BITS / 32;                     // [0] keys in table | DIST_FULL_BIT [1] first k-mer [2] sp [3] P [4] idx [5,6] queue ticket [7] E of pass [8] selected [9,10] edge base [11] hot-list cursor [12] items of the first k-mer [13] a counter of the sketch wrapped [14,15] where its item records start [16..22] the next first k-mer's index and head [23] its useful items (the sketch sweep's) [24, 25] the members of its class and where they start in A.order [26..29] the workgroup's chunk of the edge output [30] rows staged [31] a byte counter of the sketch wrapped
     unsigned char* lds_tab = cf_lds_at(DIST_LDS_HEAD);
     Tab T;
     T.init(lds_tab, (uint32_t)A.slots);
@@ -1376,6 +1449,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
     const uint32_t slots = (uint32_t)A.slots, n_buckets = slots / Tab::kPerBucket;   // slots is a multiple of 8
     unsigned long long acc_E = 0, acc_spill = 0, acc_pass = 0, acc_edges = 0;  // flushed once per workgroup (thread 0)
 #if defined(CF_DIST_DIAG_COUNT)      /* diagnostic build: [0] loop trips of parked inserts [1] overflow calls [2] parked inserts run [3] drains [4] inserts drained */
+    unsigned long long dg_swept = 0;      /* thread 0: partner entries of the passes, once per class (acc_E has them once per member) */
     unsigned long long dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};      /* [5] shader cycles inside the parked-insert runs [6] inside the drains [7] inside the table sweep, per wave (lane 0) */
 #define CF_DG(X) X
 #define CF_DG_PTR (&dg[0])
@@ -1411,7 +1485,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
     // Thread 0 fetches the NEXT first k-mer's head (ticket -> heads[]: two dependent round trips) while the workgroup works on
     // the current one; the values wait in its registers until the loop comes around.
     long long nx_idx = -1;
-    cf_dist_head nx_head{0u, 0u, 0ull, 0u, 0u, 0u, 0u};      // (a, items, records, partner entries, useful items)
+    cf_dist_head nx_head{0u, 0u, 0ull, 0u, 0u, 1u, 0u};      // (a, items, records, partner entries, useful items)
     unsigned long long nx_q = 0;
     if (!cf_lds_base_ok()) { if (t == 0) atomicOr(&A.counters[4], 2ull); return; }      // (cf_common.h: cf_lds_at)
     // Barriers.  A first k-mer whose table needs one pass — nearly all — meets the workgroup SEVEN times: [top] the previous
@@ -1427,6 +1501,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
         sh[18] = nx_head.a; sh[19] = nx_head.n_items; sh[20] = (uint32_t)nx_head.ibase; sh[21] = (uint32_t)(nx_head.ibase >> 32);
         sh[22] = nx_head.n_entries;      // partner entries (sizes the passes when every b is marked)
         sh[23] = nx_head.n_useful;
+        if (CLS) { sh[24] = nx_head.n_members; sh[25] = nx_head.first_member; }
     };
     auto pop_pass = [&]() {          // thread 0: the next partition of the stack becomes the pass
         const uint32_t sp = sh[2] - 1; sh[2] = sp; sh[3] = stack[2 * sp]; sh[4] = stack[2 * sp + 1]; sh[0] = 0; sh[7] = 0; sh[8] = 0; sh[11] = 0; sh[30] = 0;
@@ -1443,6 +1518,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
         const int64_t ai = (int64_t)(((unsigned long long)sh[17] << 32) | sh[16]);
         if (ai < 0) break;
         const uint32_t a = sh[18], n_items = sh[19], n_ent_a = sh[22], n_useful = sh[23];
+        const uint32_t n_mem = CLS ? sh[24] : 1u, m_first = CLS ? sh[25] : 0u;
         // Round 6: the list of slots that reach min_cov (one returning LDS add, a wait and a readfirstlane per drain that has one — on
         // cenX-shaped reads every drain has a dozen) is not kept for a first k-mer that would overflow it anyway: its filter scans the count
         // fields, as it did all along once the list was full (12 of 108 ms there)
@@ -1883,97 +1959,114 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
             // fit the rest of the chunk is marked and staged (count sh[30]); those are written behind a barrier, after thread 0 has
             // reserved the next chunk.  (The first half of round 3 staged EVERY selected slot, met at a barrier for thread 0 to
             // hand out the rows and read the slots again: the write phase was 9 % of the kernel.)
-            const unsigned long long ch_base = ((unsigned long long)sh[29] << 32) | sh[28];
-            const uint32_t ch_rows = sh[27];
-            auto put_row = [&](unsigned long long o, uint32_t b, uint32_t dd, uint32_t cnt) {
-                if (o < A.edge_cap) *(cf_u32x4*)(A.edges + 4 * o) = cf_u32x4{dd, a, b, cnt};
-                const uint32_t bit = 1u << (b & 31);
-                if (!(A.unique_bits[b >> 5] & bit)) atomicOr(&A.unique_bits[b >> 5], bit);
-            };
-            // the same in two halves (round 6): the row is stored and the word of b's unique bit REQUESTED; the bit is looked at — and set
-            // when it is not — a round of the filter later.  A first k-mer of cenX-shaped reads has ~3 500 selected edges: four rounds
-            // of the list per thread, each of which waited for its own round trip to the unique mask (18 % of the kernel by thread 0's stamps).
-            auto set_unique = [&](uint32_t w, uint32_t b) { const uint32_t bit = 1u << (b & 31); if (!(w & bit)) atomicOr(&A.unique_bits[b >> 5], bit); };
-            // called by all lanes of a wave together; true for the lanes whose edge got its row here (the others': behind the barrier below)
-            auto keep = [&](bool sel, uint32_t s, uint32_t b, uint32_t dd, uint32_t cnt) -> bool {
-                const unsigned long long m = cf_ballot(sel);
-                if (!m) return false;
-                uint32_t row0 = 0;
-                if (lane == 0) { const uint32_t n = (uint32_t)__popcll(m); atomicAdd(&sh[8], n); row0 = atomicAdd(&sh[26], n); }
-                const uint32_t row = (uint32_t)__builtin_amdgcn_readfirstlane((int)row0) + (uint32_t)__popcll(m & lt);
-                const bool late = sel && row >= ch_rows;
-                const unsigned long long o = ch_base + row;
-                if (sel && !late && o < A.edge_cap) *(cf_u32x4*)(A.edges + 4 * o) = cf_u32x4{dd, a, b, cnt};
-                const unsigned long long ml = cf_ballot(late);
-                if (ml) {
-                    uint32_t p0 = 0;
-                    if (lane == 0) p0 = atomicAdd(&sh[30], (uint32_t)__popcll(ml));
-                    const uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)p0) + (uint32_t)__popcll(ml & lt);
-                    if (late) { T.mark(s); if (pos < A.stage_cap) stage[pos] = (uint16_t)s; }
-                }
-                return sel && !late;
-            };
-            if (CF_DIST_ABL >= 1) { }
-            else if (n_hot <= hot_cap) {
-                bool p_on = false;      // the previous round's edge of this lane: its unique-mask word is on its way
-                uint32_t p_w = 0, p_b = 0;
-                for (uint32_t i0 = 0; i0 < n_hot; i0 += (uint32_t)nt) {
-                    const uint32_t i = i0 + (uint32_t)t;
-                    bool sel = false;
-                    uint32_t s = 0, eb = 0, ed = 0, ec = 0;
-                    if (i < n_hot && (s = hot[i]) != 0xFFFFu) {      // (0xFFFF: an entry of a wave's block of the list that the wave did not fill)
-                        T.eval_slot(s, n_buckets, A.min_cov, [&](uint32_t, uint32_t b, uint32_t dd, uint32_t cnt, unsigned long long total) { sel = b != a && dominant(cnt, total); eb = b; ed = dd; ec = cnt; });
+            // The table of the pass is the table of EVERY member of the class (cnt(a, b, d) depends on a only through its posting list): from here
+            // to [rows reserved] the pass runs once per member a_j = order[first_member + j] — the same slots, the same totals, `b != a_j` and the
+            // row's first column its own.  sh[8] counts the selected rows of all members so far (nobody resets it between members: a member's
+            // share is the difference); a class of one takes exactly the path and the barriers of a first k-mer without classes.
+            uint32_t sel_prev = 0, sp_left = 0;
+            for (uint32_t mj = 0; mj < n_mem; ++mj) {
+                const uint32_t am = mj ? (uint32_t)A.order[(size_t)m_first + mj] : a;
+                const unsigned long long ch_base = ((unsigned long long)sh[29] << 32) | sh[28];
+                const uint32_t ch_rows = sh[27];
+                auto put_row = [&](unsigned long long o, uint32_t b, uint32_t dd, uint32_t cnt) {
+                    if (o < A.edge_cap) *(cf_u32x4*)(A.edges + 4 * o) = cf_u32x4{dd, am, b, cnt};
+                    const uint32_t bit = 1u << (b & 31);
+                    if (!(A.unique_bits[b >> 5] & bit)) atomicOr(&A.unique_bits[b >> 5], bit);
+                };
+                // the same in two halves (round 6): the row is stored and the word of b's unique bit REQUESTED; the bit is looked at — and set
+                // when it is not — a round of the filter later.  A first k-mer of cenX-shaped reads has ~3 500 selected edges: four rounds
+                // of the list per thread, each of which waited for its own round trip to the unique mask (18 % of the kernel by thread 0's stamps).
+                auto set_unique = [&](uint32_t w, uint32_t b) { const uint32_t bit = 1u << (b & 31); if (!(w & bit)) atomicOr(&A.unique_bits[b >> 5], bit); };
+                // called by all lanes of a wave together; true for the lanes whose edge got its row here (the others': behind the barrier below)
+                auto keep = [&](bool sel, uint32_t s, uint32_t b, uint32_t dd, uint32_t cnt) -> bool {
+                    const unsigned long long m = cf_ballot(sel);
+                    if (!m) return false;
+                    uint32_t row0 = 0;
+                    if (lane == 0) { const uint32_t n = (uint32_t)__popcll(m); atomicAdd(&sh[8], n); row0 = atomicAdd(&sh[26], n); }
+                    const uint32_t row = (uint32_t)__builtin_amdgcn_readfirstlane((int)row0) + (uint32_t)__popcll(m & lt);
+                    const bool late = sel && row >= ch_rows;
+                    const unsigned long long o = ch_base + row;
+                    if (sel && !late && o < A.edge_cap) *(cf_u32x4*)(A.edges + 4 * o) = cf_u32x4{dd, am, b, cnt};
+                    const unsigned long long ml = cf_ballot(late);
+                    if (ml) {
+                        uint32_t p0 = 0;
+                        if (lane == 0) p0 = atomicAdd(&sh[30], (uint32_t)__popcll(ml));
+                        const uint32_t pos = (uint32_t)__builtin_amdgcn_readfirstlane((int)p0) + (uint32_t)__popcll(ml & lt);
+                        if (late) { T.mark(s); if (pos < A.stage_cap) stage[pos] = (uint16_t)s; }
                     }
-                    const bool wrote = keep(sel, s, eb, ed, ec);
-                    uint32_t w_new = 0;
-                    if (wrote) w_new = A.unique_bits[eb >> 5];
-                    if (p_on) set_unique(p_w, p_b);
-                    p_on = wrote; p_w = w_new; p_b = eb;
-                }
-                if (p_on) set_unique(p_w, p_b);
-            } else {        // more than the list holds (never seen with the sketch): evaluate inside the bucket scan, a row per atomic
-                for (uint32_t bk = (uint32_t)t; bk < n_buckets; bk += (uint32_t)nt)
-                    T.for_counts_at_least(bk, n_buckets, A.min_cov, [&](uint32_t s, uint32_t b, uint32_t dd, uint32_t cnt, unsigned long long total) {
-                        if (b != a && dominant(cnt, total)) {
-                            atomicAdd(&sh[8], 1u);
-                            const uint32_t row = atomicAdd(&sh[26], 1u);
-                            if (row < ch_rows) put_row(ch_base + row, b, dd, cnt);
-                            else {
-                                T.mark(s);
-                                const uint32_t pos = atomicAdd(&sh[30], 1u);
-                                if (pos < A.stage_cap) stage[pos] = (uint16_t)s;
-                            }
+                    return sel && !late;
+                };
+                if (CF_DIST_ABL >= 1) { }
+                else if (n_hot <= hot_cap) {
+                    bool p_on = false;      // the previous round's edge of this lane: its unique-mask word is on its way
+                    uint32_t p_w = 0, p_b = 0;
+                    for (uint32_t i0 = 0; i0 < n_hot; i0 += (uint32_t)nt) {
+                        const uint32_t i = i0 + (uint32_t)t;
+                        bool sel = false;
+                        uint32_t s = 0, eb = 0, ed = 0, ec = 0;
+                        if (i < n_hot && (s = hot[i]) != 0xFFFFu) {      // (0xFFFF: an entry of a wave's block of the list that the wave did not fill)
+                            T.eval_slot(s, n_buckets, A.min_cov, [&](uint32_t, uint32_t b, uint32_t dd, uint32_t cnt, unsigned long long total) { sel = b != am && dominant(cnt, total); eb = b; ed = dd; ec = cnt; });
                         }
-                    });
-            }
-            __syncthreads();      // [filtered]
-            CF_STAMP(4);   // filter
-            const uint32_t n_sel = sh[8], n_late = sh[30];
-            const uint32_t sp_left = sh[2];      // partitions still on the stack (thread 0 changes the word only behind the next barrier)
-            if (t == 0) {
-                acc_E += sh[7]; ++acc_pass;
-                if (n_sel) { acc_edges += n_sel; atomicOr(&A.unique_bits[a >> 5], 1u << (a & 31)); }      // (fire and forget: a load to test the bit first would stall thread 0)
-            }
-            if (n_late) {      // (uniform; once per DIST_EDGE_CHUNK rows) the chunk is full: the late rows open the next one
-                __syncthreads();      // everyone has read the chunk and the counts
-                if (t == 0) {
-                    const unsigned long long take = ((unsigned long long)n_late + A.edge_chunk - 1ull) / A.edge_chunk * A.edge_chunk;
-                    const unsigned long long nb = atomicAdd(&A.counters[0], take);
-                    sh[28] = (uint32_t)nb; sh[29] = (uint32_t)(nb >> 32); sh[27] = (uint32_t)take; sh[26] = n_late;
-                    sh[30] = 0; sh[13] = 0;      // ([13]: cursor of the marked-slot sweep below; the sketch's flag is long read)
-                }
-                __syncthreads();      // [rows reserved]
-                const unsigned long long nbase = ((unsigned long long)sh[29] << 32) | sh[28];
-                if (n_late <= A.stage_cap) {           // the staged slot list
-                    for (uint32_t i = (uint32_t)t; i < n_late; i += (uint32_t)nt) {
-                        uint32_t b, dd, cnt;
-                        if (T.get(stage[i], b, dd, cnt)) put_row(nbase + i, b, dd, cnt);
+                        const bool wrote = keep(sel, s, eb, ed, ec);
+                        uint32_t w_new = 0;
+                        if (wrote) w_new = A.unique_bits[eb >> 5];
+                        if (p_on) set_unique(p_w, p_b);
+                        p_on = wrote; p_w = w_new; p_b = eb;
                     }
-                } else {                               // more late edges than the stage holds: sweep the marked slots, a bucket per thread
+                    if (p_on) set_unique(p_w, p_b);
+                } else {        // more than the list holds (never seen with the sketch): evaluate inside the bucket scan, a row per atomic
                     for (uint32_t bk = (uint32_t)t; bk < n_buckets; bk += (uint32_t)nt)
-                        T.for_marked(bk, [&](uint32_t, uint32_t b, uint32_t dd, uint32_t cnt) { put_row(nbase + atomicAdd(&sh[13], 1u), b, dd, cnt); });
+                        T.for_counts_at_least(bk, n_buckets, A.min_cov, [&](uint32_t s, uint32_t b, uint32_t dd, uint32_t cnt, unsigned long long total) {
+                            if (b != am && dominant(cnt, total)) {
+                                atomicAdd(&sh[8], 1u);
+                                const uint32_t row = atomicAdd(&sh[26], 1u);
+                                if (row < ch_rows) put_row(ch_base + row, b, dd, cnt);
+                                else {
+                                    T.mark(s);
+                                    const uint32_t pos = atomicAdd(&sh[30], 1u);
+                                    if (pos < A.stage_cap) stage[pos] = (uint16_t)s;
+                                }
+                            }
+                        });
                 }
-            }
+                __syncthreads();      // [filtered]
+                CF_STAMP(4);   // filter
+                const uint32_t n_sel = sh[8] - sel_prev, n_late = sh[30];
+                sel_prev += n_sel;
+                sp_left = sh[2];      // partitions still on the stack (thread 0 changes the word only behind the next barrier)
+                if (t == 0) {
+                    acc_E += sh[7];      // (the reference sweeps the pass's entries once per member)
+                    if (mj == 0u) { ++acc_pass; CF_DG(dg_swept += sh[7];) }
+                    if (n_sel) { acc_edges += n_sel; atomicOr(&A.unique_bits[am >> 5], 1u << (am & 31)); }      // (fire and forget: a load to test the bit first would stall thread 0)
+                }
+                if (n_late) {      // (uniform; once per DIST_EDGE_CHUNK rows) the chunk is full: the late rows open the next one
+                    __syncthreads();      // everyone has read the chunk and the counts
+                    if (t == 0) {
+                        const unsigned long long take = ((unsigned long long)n_late + A.edge_chunk - 1ull) / A.edge_chunk * A.edge_chunk;
+                        const unsigned long long nb = atomicAdd(&A.counters[0], take);
+                        sh[28] = (uint32_t)nb; sh[29] = (uint32_t)(nb >> 32); sh[27] = (uint32_t)take; sh[26] = n_late;
+                        sh[30] = 0; sh[13] = 0;      // ([13]: cursor of the marked-slot sweep below; the sketch's flag is long read)
+                    }
+                    __syncthreads();      // [rows reserved]
+                    const unsigned long long nbase = ((unsigned long long)sh[29] << 32) | sh[28];
+                    if (n_late <= A.stage_cap) {           // the staged slot list
+                        for (uint32_t i = (uint32_t)t; i < n_late; i += (uint32_t)nt) {
+                            uint32_t b, dd, cnt;
+                            if (T.get(stage[i], b, dd, cnt)) put_row(nbase + i, b, dd, cnt);
+                        }
+                    } else {                               // more late edges than the stage holds: sweep the marked slots, a bucket per thread
+                        for (uint32_t bk = (uint32_t)t; bk < n_buckets; bk += (uint32_t)nt)
+                            T.for_marked(bk, [&](uint32_t, uint32_t b, uint32_t dd, uint32_t cnt) { put_row(nbase + atomicAdd(&sh[13], 1u), b, dd, cnt); });
+                    }
+                }
+                if (mj + 1u < n_mem) {      // (uniform) the next member filters the same table
+                    __syncthreads();      // everyone has read this member's counts and chunk, and its late rows are out of the table
+                    if (n_late) {         // (uniform) its marks go: the next member's marked-slot sweep must find its own only
+                        for (uint32_t bk = (uint32_t)t; bk < n_buckets; bk += (uint32_t)nt) T.for_marked(bk, [&](uint32_t s, uint32_t, uint32_t, uint32_t) { T.unmark(s); });
+                        __syncthreads();
+                    }
+                }
+            }      // (members)
             CF_STAMP(5);   // reserve + write edges
             if (sp_left == 0u) break;
             __syncthreads();      // (more partitions) the rows are out of the table before it is cleared for the next one
@@ -1998,6 +2091,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
     }
 #if defined(CF_DIST_DIAG_COUNT)
     for (int i = 0; i < 8; ++i) if (dg[i]) atomicAdd(&A.counters[8 + i], dg[i]);
+    if (t == 0 && dg_swept) atomicAdd(&A.counters[147], dg_swept);
 #endif
 }
 
@@ -2111,7 +2205,7 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     unsigned long long* d_cnt = nullptr;
     int64_t n_post = 0;
     unsigned long long h_cnt[8] = {0};
-    const size_t n_cnt = 8 + 16 * 9;   // counters + 8 queue heads on their own cache lines; [144] a cloud row is not a set (cf_entry_unit_kernel) [145, 146] diagnostic build: useful items, items
+    const size_t n_cnt = 8 + 16 * 9;   // counters + 8 queue heads on their own cache lines; [144] a cloud row is not a set (cf_entry_unit_kernel) [145, 146] diagnostic build: useful items, items [147] entries swept once per class
     const int max_blocks = std::max(1, ctx->n_cu) * 8;
     cf_free_edges(ctx);      // (the buffer of this call is allocated below, once the launch shape is known)
     cf_scratch tmp(ctx);
@@ -2295,43 +2389,66 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     int ab = 1, ub = 1;      // bits of a rank, bits of a unit number
     while (ab < 32 && ((int64_t)1 << ab) < K) ++ab;
     while (ub < 32 && ((int64_t)1 << ub) < std::max<int64_t>(U, 2)) ++ub;
+    // classes of first k-mers with equal posting lists: knob dist_classes; off when the postings came from the atomics'
+    // fill pass (unordered lists) and — decided on the device — when a cloud row is not a set
+    const bool classes = ctx->dist_classes && by_sort;
+    const int hb = classes ? std::min(ctx->dist_class_bits, 64 - ab - ub) : 0;      // hash bits of the order key (16: two more radix passes)
+    int64_t n_heads = 0;
+    uint32_t *d_cflag = nullptr, *d_cfirst = nullptr;
     if (K) {
         hipLaunchKernelGGL(cf_order_keys_kernel, dim3((unsigned)cf_grid_for(K, 256, max_blocks)), dim3(256), 0, ctx->stream,
-                           (const uint32_t*)d_pcnt, (const uint32_t*)d_first, K, (int)part, (int)n_parts, ab, d_okeys, d_cnt + 6);
+                           (const uint32_t*)d_pcnt, (const uint32_t*)d_first, K, (int)part, (int)n_parts, ab, d_okeys, d_cnt + 6,
+                           hb, (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144));
         unsigned long long h_n = 0;
         CF_HIP(hipMemcpy(&h_n, d_cnt + 6, 8, hipMemcpyDeviceToHost));
         n_order = (int64_t)h_n;
-        CF_TRY(cf_radix_sort_u64(ctx, d_okeys, d_otmp, n_order, ab + ub));      // (round 6: the key's own bits — 6 radix passes at 50 000 reads; rounds 2-5 sorted all 64)
+        CF_TRY(cf_radix_sort_u64(ctx, d_okeys, d_otmp, n_order, ab + hb + ub));      // (round 6: the key's own bits — 6 radix passes at 50 000 reads; rounds 2-5 sorted all 64)
         if (n_order)
             hipLaunchKernelGGL(cf_order_extract_kernel, dim3((unsigned)cf_grid_for(n_order, 256, max_blocks)), dim3(256), 0, ctx->stream,
                                (const unsigned long long*)d_okeys, n_order, ab, d_order);
     }
-    A.order = d_order; A.n_order = n_order;
+    n_heads = n_order;
+    if (classes && n_order) {
+        const unsigned g_cls = (unsigned)cf_grid_for(n_order, 256, max_blocks);
+        int64_t* d_cidx = (int64_t*)d_otmp;      // (the sort's scratch: free again, and as large)
+        CF_TRY(tmp.get(&d_cflag, (size_t)n_order + 1, "class flags"));
+        CF_TRY(tmp.get(&d_cfirst, (size_t)n_order + 1, "class starts"));
+        CF_HIP(hipMemsetAsync(d_cflag, 0, (size_t)(n_order + 1) * 4, ctx->stream));
+        hipLaunchKernelGGL(cf_class_mark_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const unsigned long long*)d_okeys, n_order, ab,
+                           (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), d_cflag);
+        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_cflag, d_cidx, n_order, &n_heads));
+        hipLaunchKernelGGL(cf_class_first_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const uint32_t*)d_cflag, (const int64_t*)d_cidx, n_order, n_heads, d_cfirst);
+        CF_KERNEL_CHECK("the class kernels");
+    }
+    A.order = d_order; A.n_order = n_heads;
     // the work lists of the sweeps (heads + item records, laid out for workgroups of `block` threads): count, scan, fill
-    if (n_order) {
+    if (n_heads) {
         const uint32_t nw = (uint32_t)block / 64u;
-        const int g_items = cf_grid_for(n_order * 16, 256, max_blocks);
-        CF_TRY(tmp.get(&d_icnt, (size_t)n_order + 1, "item counts"));
-        CF_TRY(tmp.get(&d_ialloc, (size_t)n_order + 1, "item slots"));
-        CF_TRY(tmp.get(&d_ibase, (size_t)n_order + 1, "item bases"));
-        CF_TRY(tmp.get(&d_heads, (size_t)n_order, "first k-mer heads"));
-        hipLaunchKernelGGL(cf_items_count_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_order, (const int64_t*)d_post_ptr,
-                           (const int32_t*)d_post, (const cf_dist_rec*)d_urange, (const int32_t*)d_rbeg, min_d_eff, max_d, nw, by_sort ? 1 : 0, d_icnt, d_ialloc, d_cnt + 3);
-        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_ialloc, d_ibase, n_order, &n_item_slots));
+        const int g_items = cf_grid_for(n_heads * 16, 256, max_blocks);
+        CF_TRY(tmp.get(&d_icnt, (size_t)n_heads + 1, "item counts"));
+        CF_TRY(tmp.get(&d_ialloc, (size_t)n_heads + 1, "item slots"));
+        CF_TRY(tmp.get(&d_ibase, (size_t)n_heads + 1, "item bases"));
+        CF_TRY(tmp.get(&d_heads, (size_t)n_heads, "first k-mer heads"));
+        hipLaunchKernelGGL(cf_items_count_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_heads, (const int64_t*)d_post_ptr,
+                           (const int32_t*)d_post, (const cf_dist_rec*)d_urange, (const int32_t*)d_rbeg, min_d_eff, max_d, nw, by_sort ? 1 : 0, d_icnt, d_ialloc, d_cnt + 3,
+                           (const uint32_t*)d_cfirst);
+        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_ialloc, d_ibase, n_heads, &n_item_slots));
         CF_TRY(tmp.get(&d_items, (size_t)n_item_slots + 64, "item records"));
-        hipLaunchKernelGGL(cf_items_fill_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_order, (const int64_t*)d_post_ptr,
+        hipLaunchKernelGGL(cf_items_fill_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_heads, (const int64_t*)d_post_ptr,
                            (const int32_t*)d_post, (const cf_dist_rec*)d_urange, nw, (const uint32_t*)d_icnt, (const int64_t*)d_ibase, d_heads, d_items,
                            v_cloud_ptr, region26 ? 1 : 0, U, min_d_eff, max_d, min_cov, (ctx->dist_sketch_tail && A.sketch) ? 1 : 0,
-                           (const unsigned long long*)(d_cnt + 144), d_cnt + 145);
+                           (const unsigned long long*)(d_cnt + 144), d_cnt + 145, (const uint32_t*)d_cfirst);
     }
     A.heads = d_heads; A.items = d_items;
-    const int64_t n_a = n_order;
+    const int64_t n_a = n_heads;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n_a, (int64_t)std::max(1, ctx->n_cu) * per_cu));
     CF_KERNEL_CHECK("the work-list kernels");
     CF_HIP(hipEventRecord(ctx->ev2, ctx->stream));
-    void (*kern)(cf_dist_args) = region26 ? cf_dist_kernel<cf_tab_region26> : region ? cf_dist_kernel<cf_tab_region> : !narrow ? (wide16 ? cf_dist_kernel<cf_tab_wide16> : cf_dist_kernel<cf_tab_wide>)
-                               : narrow_db == 8 ? cf_dist_kernel<cf_tab_narrow_t<8>> : narrow_db == 7 ? cf_dist_kernel<cf_tab_narrow_t<7>>
-                               : narrow_db == 6 ? cf_dist_kernel<cf_tab_narrow_t<6>> : cf_dist_kernel<cf_tab_narrow_t<5>>;
+#define CF_DIST_KERN(CLS) (region26 ? cf_dist_kernel<cf_tab_region26, CLS> : region ? cf_dist_kernel<cf_tab_region, CLS> : !narrow ? (wide16 ? cf_dist_kernel<cf_tab_wide16, CLS> : cf_dist_kernel<cf_tab_wide, CLS>) \
+                               : narrow_db == 8 ? cf_dist_kernel<cf_tab_narrow_t<8>, CLS> : narrow_db == 7 ? cf_dist_kernel<cf_tab_narrow_t<7>, CLS>                                               \
+                               : narrow_db == 6 ? cf_dist_kernel<cf_tab_narrow_t<6>, CLS> : cf_dist_kernel<cf_tab_narrow_t<5>, CLS>)
+    void (*kern)(cf_dist_args) = classes ? CF_DIST_KERN(true) : CF_DIST_KERN(false);      // (without classes: the kernel without the member loop)
+#undef CF_DIST_KERN
     CF_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // the edge output: edge_cap rows + the unused rest of one chunk per workgroup (the holes; closed below), so that every
     // selected edge is in memory whenever edge_cap >= their number
@@ -2358,9 +2475,9 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         unsigned long long st[8];
         if (hipMemcpy(st, d_cnt + 8, 64, hipMemcpyDeviceToHost) == hipSuccess)
             std::fprintf(stderr, "[cf_dist diag] parked-insert loop trips=%llu overflow calls=%llu parked inserts run=%llu drains=%llu inserts drained=%llu cycles(sum over waves): parked runs=%llu drains=%llu table sweeps=%llu; waves=%d passes=%llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], grid * (block / 64), h_cnt[5]);
-        unsigned long long su[3];      // [0] a cloud row is not a set [1] sum of the useful items [2] sum of the items
-        if (hipMemcpy(su, d_cnt + 144, 24, hipMemcpyDeviceToHost) == hipSuccess)
-            std::fprintf(stderr, "[cf_dist diag] sketch items=%llu of items=%llu (rows are sets=%d)\n", su[1], su[2], su[0] ? 0 : 1);
+        unsigned long long su[4];      // [0] a cloud row is not a set [1] sum of the useful items [2] sum of the items [3] partner entries swept, once per class
+        if (hipMemcpy(su, d_cnt + 144, 32, hipMemcpyDeviceToHost) == hipSuccess)
+            std::fprintf(stderr, "[cf_dist diag] sketch items=%llu of items=%llu (rows are sets=%d) classes=%lld members=%lld entries swept=%llu of %llu per member\n", su[1], su[2], su[0] ? 0 : 1, (long long)n_heads, (long long)n_order, su[3], h_cnt[1]);
     }
 #endif
 #if defined(CF_DIST_STAMPS)
