@@ -542,6 +542,11 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
     } else if (n == "dist_class_bits") {
         if (value < 1 || value > 16) return cf_fail(ctx, -22, "dist_class_bits out of range (1 .. 16)");
         ctx->dist_class_bits = (int)value;
+    } else if (n == "dist_groups") {
+        ctx->dist_groups = value != 0;
+    } else if (n == "dist_group_cap") {
+        if (value < 1 || value > 32) return cf_fail(ctx, -22, "dist_group_cap out of range (1 .. 32)");
+        ctx->dist_group_cap = (int)value;
     } else if (n == "dist_sketch") {
         ctx->dist_sketch = value != 0;
     } else if (n == "dist_est_pct") {

@@ -202,7 +202,10 @@ cf_entry_unit_kernel(const int64_t* __restrict__ cloud_ptr, const int32_t* __res
 __global__ void __launch_bounds__(256)
 cf_order_keys_kernel(const uint32_t* __restrict__ pcnt, const uint32_t* __restrict__ first_unit, int64_t n_kmers, int part, int n_parts, int ab,
                      unsigned long long* __restrict__ keys, unsigned long long* __restrict__ n_out,
-                     int hb, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post, const unsigned long long* __restrict__ not_a_set) {
+                     int hb, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post, const unsigned long long* __restrict__ not_a_set, int by_second) {
+    // by_second (groups): the hb bits are the low bits of the k-mer's SECOND posting unit instead of a hash of the list — the k-mers of
+    // one first unit whose lists go on alike stand together, and the greedy cut of cf_group_mark_kernel finds small unions (in hash order the
+    // unions of the bench's reads sweep 0.70 of the classes' entries, in this order 0.44: tools/dist_groups_cpu.py --order)
     // hb > 0 (classes of first k-mers): hb bits of a hash of the k-mer's posting list stand between the first unit and the
     // rank, so that the sort puts k-mers with equal lists next to each other (they share their first unit).  The hash only brings candidates
     // together: cf_class_mark_kernel compares the lists.  Clouds that are not sets (cf_set_clouds) form no classes: the hash bits stay 0.
@@ -234,9 +237,12 @@ cf_order_keys_kernel(const uint32_t* __restrict__ pcnt, const uint32_t* __restri
                 unsigned long long h = 0;
                 if (hashed) {
                     const int64_t p0 = post_ptr[a], p1 = post_ptr[a + 1];
+                    if (by_second) h = (unsigned long long)(uint32_t)post[p1 - p0 > 1 ? p0 + 1 : p0] & ((1ull << hb) - 1ull);
+                    else {
                     h = (unsigned long long)(p1 - p0);
                     for (int64_t p = p0; p < p1; ++p) { h = (h ^ (unsigned long long)(uint32_t)post[p]) * 0x9E3779B97F4A7C15ull; h ^= h >> 29; }
                     h = (h * 0xBF58476D1CE4E5B9ull) >> (64 - hb);
+                    }
                 }
                 keys[base + (unsigned long long)__popcll(m & lt)] = ((unsigned long long)first_unit[a] << (ab + hb)) | (h << ab) | (unsigned long long)a;
             }
@@ -294,6 +300,168 @@ cf_class_first_kernel(const uint32_t* __restrict__ flags, const int64_t* __restr
     }
 }
 
+// Groups of first k-mers.  The first k-mers of a launch that share their FIRST posting unit come from one place of the array:
+// their lists are subsets of one column of read units.  A group is a run of such k-mers, next to each other in the sorted order keys, whose
+// lists have a UNION of at most `cap` (<= 32) postings; cf_dist_kernel sweeps the union once into a table of 32-bit masks (cf_tab_mask) and
+// every member reads its own counts out of it through the mask of its postings among the union's.  Equal lists are equal masks: a group
+// holds what a class held.  The thread at the head of a run of equal first units walks the run and cuts it greedily: a group is closed when
+// the next list would bring the union above cap or the members to DIST_CLASS_CAP.  A first k-mer with more than cap postings is a group
+// of its own, and when a cloud row is not a set every first k-mer is: such a group COUNTS in its table (an `or` would lose the second
+// occurrence of a pair under one posting).  flags[] is zeroed before the launch; the scan that numbered the classes numbers the groups.
+#define DIST_GROUP_MAX 32u
+// One WAVE walks a run of equal first units (the runs that start among its 64 positions; a thread per run with the union in a private array
+// took 100 ms at 50 000 reads: every step of its merges was a round trip to scratch memory).  The union lives in the lanes — lane i holds
+// its i-th posting, in the order they joined — and a member's list in the lanes too: membership is nu broadcasts and compares, and the
+// member's mask falls out of the same loop in scalar registers.  Per position of the sorted keys the kernel writes the start flag, the
+// member's mask over its group's union, and which of its own postings were NEW to the union (cf_group_fill_kernel strings those together:
+// the union's order is the order of joining, not ascending — the place of a posting in the union only names its bit).
+__device__ __forceinline__ unsigned long long cf_readlane64(unsigned long long v, int l) {
+    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) | (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
+}
+__global__ void __launch_bounds__(256)
+cf_group_mark_kernel(const unsigned long long* __restrict__ keys, int64_t n, int kb, int ab, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
+                     const unsigned long long* __restrict__ not_a_set, uint32_t cap, uint32_t* __restrict__ flags, uint32_t* __restrict__ member_mask, uint32_t* __restrict__ new_mask) {
+    // kb: the key's bits below the first unit (rank and order bits); ab: bits of the rank
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const unsigned long long rank_mask = (1ull << ab) - 1ull;
+    const bool off = *not_a_set != 0ull;
+    for (int64_t c0 = wave * 64; c0 < n; c0 += n_waves * 64) {      // (wave-uniform)
+        // a window of 64 positions: first unit, start and length of the list (lane l: position wb + l)
+        int64_t wb = c0, w_p0 = 0;
+        unsigned long long w_fu = ~0ull;
+        uint32_t w_len = 0;
+        auto load_window = [&](int64_t b) {
+            wb = b; w_fu = ~0ull; w_p0 = 0; w_len = 0;
+            const int64_t i = b + (int64_t)lane;
+            if (i < n) { const unsigned long long k = keys[i]; const uint32_t x = (uint32_t)(k & rank_mask); w_fu = k >> kb; w_p0 = post_ptr[x]; w_len = (uint32_t)(post_ptr[x + 1] - w_p0); }
+        };
+        load_window(c0);
+        const int64_t i_me = c0 + (int64_t)lane;
+        if (off) { if (i_me < n) { flags[i_me] = 1u; member_mask[i_me] = 0u; new_mask[i_me] = 0u; } continue; }
+        bool head = i_me < n;
+        if (head && i_me > 0) head = (keys[i_me - 1] >> kb) != w_fu;
+        unsigned long long hm = cf_ballot(head);
+        while (hm) {      // the runs that start in this chunk, one after the other
+            const int s = __ffsll((long long)hm) - 1;
+            hm &= hm - 1ull;
+            if (wb != c0) load_window(c0);      // (the run before went on beyond the chunk)
+            const unsigned long long fu = cf_readlane64(w_fu, s);
+            uint32_t un = 0xFFFFFFFFu, nu = 0, members = 0;
+            for (int64_t j = c0 + s; j < n; ++j) {
+                if (j - wb == 64) load_window(j);
+                const int sl = (int)(j - wb);
+                if (cf_readlane64(w_fu, sl) != fu) break;
+                const int64_t p0 = (int64_t)cf_readlane64((unsigned long long)w_p0, sl);
+                const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)w_len, sl);
+                if (len > cap) {      // a group of its own (it counts); the next k-mer starts one too
+                    if (lane == 0u) { flags[j] = 1u; member_mask[j] = 0u; new_mask[j] = 0u; }
+                    nu = 0; members = 0;
+                    continue;
+                }
+                const uint32_t L = lane < len ? (uint32_t)post[p0 + lane] : 0xFFFFFFFFu;
+                uint32_t mask = 0;
+                unsigned long long found = 0;
+                for (uint32_t i = 0; i < nu; ++i) {
+                    const unsigned long long h = cf_ballot(L == (uint32_t)__builtin_amdgcn_readlane((int)un, (int)i));
+                    if (h) { mask |= 1u << i; found |= h; }
+                }
+                const unsigned long long mine = cf_ballot(lane < len);
+                unsigned long long nm = mine & ~found;
+                const bool start = members == 0u || members == DIST_CLASS_CAP || nu + (uint32_t)__popcll(nm) > cap;
+                if (start) { nu = 0; members = 0; mask = 0; nm = mine; }
+                const uint32_t fresh = (uint32_t)nm;      // (len <= 32: the list's lanes)
+                while (nm) {
+                    const int t = __ffsll((long long)nm) - 1;
+                    nm &= nm - 1ull;
+                    const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)L, t);
+                    if (lane == nu) un = x;
+                    mask |= 1u << nu;
+                    ++nu;
+                }
+                ++members;
+                if (lane == 0u) { if (start) flags[j] = 1u; member_mask[j] = mask; new_mask[j] = fresh; }
+            }
+        }
+    }
+}
+// Per group g (the k-mers order[gfirst[g] .. gfirst[g + 1])): the union of the members' lists at upost[32 g ..] — every member's new postings, in
+// the order of joining — and its size in ulen[g] (bit 31: a counting group — no union, the sweep takes the k-mer's own list).
+__global__ void __launch_bounds__(256)
+cf_group_fill_kernel(const int32_t* __restrict__ order, const uint32_t* __restrict__ gfirst, int64_t n_groups, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
+                     const unsigned long long* __restrict__ not_a_set, uint32_t cap, const uint32_t* __restrict__ new_mask, const uint32_t* __restrict__ member_mask,
+                     int32_t* __restrict__ upost, uint32_t* __restrict__ ulen, unsigned long long* __restrict__ diag, unsigned long long* __restrict__ err) {
+    const bool off = *not_a_set != 0ull;
+    unsigned long long dg_u = 0, dg_c = 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n_groups; g += stride) {
+        const uint32_t f = gfirst[g], e = gfirst[g + 1];
+        bool counting = off;
+        if (e - f == 1u) { const int32_t x = order[f]; counting = counting || (uint32_t)(post_ptr[x + 1] - post_ptr[x]) > cap; }
+        uint32_t k = 0;
+        if (!counting)
+            for (uint32_t j = f; j < e; ++j) {
+                uint32_t nm = new_mask[j];
+                if (!nm) continue;
+                const int64_t p0 = post_ptr[order[j]];
+                while (nm) {
+                    const int t = __ffs((int)nm) - 1;
+                    nm &= nm - 1u;
+                    if (k < DIST_GROUP_MAX) upost[(size_t)DIST_GROUP_MAX * (size_t)g + k] = post[p0 + t];
+                    ++k;
+                }
+            }
+        if (k > DIST_GROUP_MAX) { atomicOr(err, 4ull); k = DIST_GROUP_MAX; }      // (cf_group_mark_kernel cut the run so that this cannot be: the launch fails)
+        ulen[g] = counting ? 0x80000000u : k;
+        dg_u += k;
+#if defined(CF_DIST_DIAG_COUNT)      /* the group's classes: its distinct member masks (equal lists in one group have equal masks) */
+        for (uint32_t j = f; j < e; ++j) {
+            bool seen = false;
+            for (uint32_t q = f; q < j && !seen; ++q) seen = member_mask[q] == member_mask[j];
+            dg_c += (unsigned long long)!seen;
+        }
+#endif
+    }
+#if defined(CF_DIST_DIAG_COUNT)
+    for (int d = 32; d >= 1; d >>= 1) { dg_u += __shfl_down(dg_u, (unsigned)d); dg_c += __shfl_down(dg_c, (unsigned)d); }
+    if ((threadIdx.x & 63) == 0 && dg_c) { atomicAdd(diag, dg_u); atomicAdd(diag + 1, dg_c); }
+#else
+    (void)diag; (void)dg_u; (void)dg_c; (void)member_mask;
+#endif
+}
+// Summed over the launch's first k-mers (one thread each): their OWN partner entries and self pairs (postings (u, v) of one k-mer in one read
+// with min_d <= v - u <= max_d: entries that are the first k-mer itself) — with groups a pass sweeps the union's entries, and n_emissions
+// stays what it was.  The lists are ascending (postings by sort), so the postings of one read stand next to each other.
+__global__ void __launch_bounds__(256)
+cf_member_emissions_kernel(const int32_t* __restrict__ order, int64_t n_order, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
+                           const cf_dist_rec* __restrict__ urange, const int32_t* __restrict__ rend, int32_t min_d, int32_t max_d,
+                           unsigned long long* __restrict__ entries_out, unsigned long long* __restrict__ self_out) {
+    unsigned long long ent = 0, self = 0;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_order; i += stride) {
+        const int32_t x = order[i];
+        const int64_t p0 = post_ptr[x], p1 = post_ptr[x + 1];
+        int32_t u = p0 < p1 ? post[p0] : 0;
+        for (int64_t p = p0; p < p1; ++p) {
+            ent += urange[u].len;
+            const int32_t u_next = p + 1 < p1 ? post[p + 1] : 0x7FFFFFFF;
+            if (u_next < rend[u]) {      // (rare: the k-mer twice in one read)
+                for (int64_t q = p + 1; q < p1; ++q) {
+                    const int32_t v = post[q];
+                    if (v >= rend[u] || v - u > max_d) break;
+                    self += (unsigned long long)(v - u >= min_d);
+                }
+            }
+            u = u_next;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) { ent += __shfl_down(ent, (unsigned)d); self += __shfl_down(self, (unsigned)d); }
+    if ((threadIdx.x & 63) == 0) {
+        if (ent) atomicAdd(entries_out, ent);
+        if (self) atomicAdd(self_out, self);
+    }
+}
+
 // One item = up to DIST_ITEM consecutive partner entries of one posting: what one wave takes per step.
 //   e  index of its first entry in the cloud-entry arrays (32 bits: cf_dist_edges refuses more than 2^32 - DIST_ITEM entries)
 //   m  [entries of the item (1 .. DIST_ITEM) : 16 | unit index of the posting inside its read, mod 65536 : 16]
@@ -343,6 +511,7 @@ struct cf_dist_args {
     uint32_t hot_entries;          // first k-mers with more partner entries than this do not keep the list at all (it would overflow: the filter scans)
     uint32_t* edges;
     unsigned long long edge_cap;
+    const uint32_t* member_mask;   // groups: per position of `order`, which postings of its group's union the k-mer has
     const int32_t* order;          // first k-mers of this partition, sorted by their first posting (locality); the members of a class stand next to each other
     int64_t n_order;               // heads of the launch: classes of first k-mers (every first k-mer of `order` when classes are off)
     unsigned long long edge_chunk; // edge rows a workgroup reserves per global atomic (DIST_EDGE_CHUNK; tests: small)
@@ -395,6 +564,7 @@ template <int DB>
 struct cf_tab_wide_t {
     static constexpr uint32_t kCntBits = 31 - DB, kCntMask = (1u << kCntBits) - 1u, kDMask = (1u << DB) - 1u, kDShift = 32 - DB;
     static constexpr uint32_t kSlotBytes = 8, kPerBucket = 4;
+    static constexpr bool kMaskTab = false;      // (cf_tab_mask: a mask of the union's postings per slot)
     struct bucket { cf_u64x2 lo, hi; };
     struct raw { uint32_t b, i; };
     typedef unsigned long long qitem;   // deferred insert: [b:32 | d:8 | bucket to look at next:24]
@@ -592,6 +762,7 @@ struct cf_tab_narrow_t {
     static_assert(PB == 4 || PB == 8, "a bucket is one or two 16-byte reads of keys");
     static constexpr uint32_t kBBits = 32 - DB, kBMask = (1u << kBBits) - 1u;
     static constexpr uint32_t kSlotBytes = 6, kPerBucket = PB, kAll = (1u << PB) - 1u;
+    static constexpr bool kMaskTab = false;
     static constexpr uint32_t kEmpty = 0xFFFFFFFFu;
     struct bucket { uint32_t k[PB]; };
     struct counts { uint32_t w[PB / 2]; };      // PB x 16-bit [sel:1 | count - 1 : 15]
@@ -796,6 +967,162 @@ struct cf_tab_narrow_t {
 };
 typedef cf_tab_narrow_t<8> cf_tab_narrow;
 
+// The table of a GROUP of first k-mers: the 4-byte stream, the keys [d : DB | b : 32 - DB], the 4-key buckets and the hashes of
+// the 6-byte layout, but a slot's second half is a 32-bit MASK of the postings of the group's union U that brought the pair (b, d): an
+// insert is a returning `or` of the posting's bit, and for the member a_j with the list mask M_j
+//     cnt(a_j, b, d) = popcount(mask & M_j),     sum_d cnt(a_j, b, .) = the same sum over the keys of b.
+// Exact because a cloud row is a set (a posting brings a pair at most once).  A group that cannot take masks — ONE first k-mer with more
+// postings than the mask has bits, or any first k-mer of clouds that are not sets — is `counting`: the same word is a plain 32-bit count
+// (add 1 per occurrence), which is what the other layouts keep.  The selection marks of late rows (cf_dist_kernel) have no bit left in a
+// slot: they stand in a bitmap of their own behind the masks.  8 bytes + 1 bit per slot.
+#define CF_DIST_HAS_GROUPS (CF_DIST_DRAIN2 && !CF_DIST_OLD_DRAIN)      /* (the mask table has the two-probe drain only) */
+template <int DB>
+struct cf_tab_mask : cf_tab_narrow_t<DB, 4> {
+    typedef cf_tab_narrow_t<DB, 4> N;
+    typedef typename N::bucket bucket;
+    static constexpr uint32_t kSlotBytes = 8, kEmpty = N::kEmpty, kBMask = N::kBMask, kBBits = N::kBBits;
+    static constexpr bool kMaskTab = true;
+    uint32_t* msk;      // slots x 32-bit mask (or count)
+    uint32_t* mk;       // slots x 1 bit: selected, row not yet written
+    uint32_t mm;        // the list mask of the member whose rows are made
+    bool counting;      // (uniform over a head) the word is a count
+    static __host__ __device__ __forceinline__ uint32_t extra_bytes(uint32_t slots) { return ((slots + 127u) >> 7) * 16u; }
+    __device__ __forceinline__ void init(unsigned char* lds, uint32_t slots) { this->keys = (uint32_t*)lds; this->cnt32 = nullptr; msk = this->keys + slots; mk = msk + slots; mm = 0xFFFFFFFFu; counting = false; }
+    __device__ __forceinline__ void set_member(uint32_t m, bool c) { mm = m; counting = c; }
+    __device__ __forceinline__ void clear(uint32_t slots, uint32_t t, uint32_t nt) const {
+        const cf_u32x4 e{kEmpty, kEmpty, kEmpty, kEmpty}, z{0u, 0u, 0u, 0u};
+        for (uint32_t s = t; s < (slots >> 2); s += nt) { ((cf_u32x4*)this->keys)[s] = e; ((cf_u32x4*)msk)[s] = z; }
+        for (uint32_t s = t; s < ((slots + 127u) >> 7); s += nt) ((cf_u32x4*)mk)[s] = z;
+    }
+    struct masks { uint32_t w[4]; };
+    __device__ __forceinline__ masks read_masks(uint32_t bk) const { const cf_u32x4 v = *(const cf_u32x4*)&msk[4 * bk]; masks m; m.w[0] = v.x; m.w[1] = v.y; m.w[2] = v.z; m.w[3] = v.w; return m; }
+    __device__ __forceinline__ uint32_t cnt_of(uint32_t w) const { return counting ? w : (uint32_t)__popc(w & mm); }      // the member's count
+    __device__ __forceinline__ uint32_t all_of(uint32_t w) const { return counting ? w : (uint32_t)__popc(w); }          // the union's
+    // one more occurrence, brought by posting `bit` of the union: the count of the union after it — or all ones when the posting was there already
+    // (it then moved nothing: no count is "reached")
+    __device__ __forceinline__ uint32_t add(uint32_t bk, int i, uint32_t bit) const {
+        const uint32_t s = 4u * bk + (uint32_t)i;
+        if (counting) return atomicAdd(&msk[s], 1u) + 1u;
+        const uint32_t was = atomicOr(&msk[s], 1u << bit);
+        return ((was >> bit) & 1u) ? 0xFFFFFFFFu : (uint32_t)__popc(was) + 1u;
+    }
+    __device__ __forceinline__ int claim_finish(uint32_t old, uint32_t bk, int i, uint32_t b, uint32_t dd, uint32_t& cnt, uint32_t bit) const {
+        cnt = 0xFFFFFFFFu;
+        if (old != kEmpty && old != N::key_of(b, dd)) return 2;
+        cnt = add(bk, i, bit);      // (a fresh slot's mask is empty: the claim does not count by itself)
+        return old == kEmpty ? 0 : 1;
+    }
+    // cf_probe2 with masks: two queued inserts per lane side by side, ONE probe of the home bucket each in straight-line code
+    __device__ __forceinline__ void probe2m(bool act0, uint32_t bk0, uint32_t key0, uint32_t bit0, bool act1, uint32_t bk1, uint32_t key1, uint32_t bit1, uint32_t min_cov,
+                                            bool& made0, bool& park0, uint32_t& hot0, bool& made1, bool& park1, uint32_t& hot1) const {
+        const bucket k0 = this->read(bk0), k1 = this->read(bk1);
+        uint32_t em0 = 4u, em1 = 4u;
+#pragma unroll
+        for (int j = 3; j >= 0; --j) { em0 = k0.k[j] == kEmpty ? (uint32_t)j : em0; em1 = k1.k[j] == kEmpty ? (uint32_t)j : em1; }
+        uint32_t sl0 = em0, sl1 = em1;
+        bool mt0 = false, mt1 = false;
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {
+            const bool e0 = k0.k[j] == key0, e1 = k1.k[j] == key1;
+            sl0 = e0 ? (uint32_t)j : sl0; mt0 |= e0; sl1 = e1 ? (uint32_t)j : sl1; mt1 |= e1;
+        }
+        mt0 &= act0; mt1 &= act1;
+        const bool claim0 = act0 && !mt0 && em0 < 4u, claim1 = act1 && !mt1 && em1 < 4u;
+        const uint32_t s0 = 4u * bk0 + (sl0 & 3u), s1 = 4u * bk1 + (sl1 & 3u);
+        uint32_t old0 = key0, old1 = key1;
+        if (claim0) old0 = atomicCAS(&this->keys[s0], kEmpty, key0);
+        if (claim1) old1 = atomicCAS(&this->keys[s1], kEmpty, key1);
+        const bool fresh0 = claim0 && old0 == kEmpty, fresh1 = claim1 && old1 == kEmpty;
+        const bool in0 = mt0 || (claim0 && old0 == key0) || fresh0, in1 = mt1 || (claim1 && old1 == key1) || fresh1;
+        uint32_t now0, now1;
+        bool new0 = in0, new1 = in1;
+        if (counting) {
+            now0 = atomicAdd(&msk[s0], in0 ? 1u : 0u) + 1u;
+            now1 = atomicAdd(&msk[s1], in1 ? 1u : 0u) + 1u;
+        } else {
+            const uint32_t was0 = atomicOr(&msk[s0], in0 ? 1u << bit0 : 0u);
+            const uint32_t was1 = atomicOr(&msk[s1], in1 ? 1u << bit1 : 0u);
+            new0 = in0 && !((was0 >> bit0) & 1u); new1 = in1 && !((was1 >> bit1) & 1u);
+            now0 = (uint32_t)__popc(was0) + 1u; now1 = (uint32_t)__popc(was1) + 1u;
+        }
+        made0 = fresh0; park0 = act0 && !in0; hot0 = (new0 && now0 == min_cov) ? s0 : 0xFFFFFFFFu;
+        made1 = fresh1; park1 = act1 && !in1; hot1 = (new1 && now1 == min_cov) ? s1 : 0xFFFFFFFFu;
+    }
+    __device__ __forceinline__ bool get(uint32_t s, uint32_t& b, uint32_t& dd, uint32_t& cnt) const {
+        const uint32_t q = this->keys[s];
+        b = q & kBMask; dd = q >> kBBits; cnt = cnt_of(msk[s]);
+        return q != kEmpty;
+    }
+    __device__ __forceinline__ uint32_t sum_of(const bucket& k, const masks& m, uint32_t b) const {
+        uint32_t total = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if ((k.k[j] & kBMask) == b && k.k[j] != kEmpty) total += cnt_of(m.w[j]);
+        return total;
+    }
+    __device__ __forceinline__ unsigned long long total_of(uint32_t b, uint32_t n_buckets) const {
+        unsigned long long total = 0;
+        uint32_t bk = N::home(N::hash(b), n_buckets);
+        for (uint32_t probe = 0; probe < n_buckets; ++probe) {
+            const bucket k = this->read(bk);
+            total += sum_of(k, read_masks(bk), b);
+            if (k.k[3] == kEmpty) break;
+            bk = bk + 1 == n_buckets ? 0u : bk + 1;
+        }
+        return total;
+    }
+    // (a slot whose MEMBER count stays below min_cov is dropped before the chain walk)
+    template <class F>
+    __device__ __forceinline__ void for_counts_at_least(uint32_t bk, uint32_t n_buckets, uint32_t min_cov, F&& f) const {
+        const masks m = read_masks(bk);
+        if (!(m.w[0] | m.w[1] | m.w[2] | m.w[3])) return;
+        const bucket k = this->read(bk);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const uint32_t cnt = cnt_of(m.w[i]);
+            if (cnt >= min_cov && k.k[i] != kEmpty) {
+                const uint32_t b = k.k[i] & kBMask;
+                const unsigned long long total = (k.k[3] == kEmpty && N::home(N::hash(b), n_buckets) == bk) ? (unsigned long long)sum_of(k, m, b) : total_of(b, n_buckets);
+                f(4u * bk + (uint32_t)i, b, k.k[i] >> kBBits, cnt, total);
+            }
+        }
+    }
+    // the scan that replaces the hot list looks at the UNION's counts: one list for every member
+    static constexpr uint32_t kScanGroup = 4;
+    static __device__ __forceinline__ uint32_t slot_of_bit(uint32_t bit) { return bit; }
+    __device__ __forceinline__ uint32_t hot_mask(uint32_t g, uint32_t min_cov) const {
+        const masks m = read_masks(g);
+        const uint32_t need = max(min_cov, 1u);      // (an empty slot has no bit and no count)
+        return (uint32_t)(all_of(m.w[0]) >= need) | ((uint32_t)(all_of(m.w[1]) >= need) << 1) | ((uint32_t)(all_of(m.w[2]) >= need) << 2) | ((uint32_t)(all_of(m.w[3]) >= need) << 3);
+    }
+    template <class F>
+    __device__ __forceinline__ void eval_slot(uint32_t s, uint32_t n_buckets, uint32_t min_cov, F&& f) const {
+        const uint32_t bk = s >> 2, i = s & 3u;
+        const bucket k = this->read(bk);
+        const masks m = read_masks(bk);
+        uint32_t mine = k.k[0], mine_m = m.w[0];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) { if (i == (uint32_t)j) { mine = k.k[j]; mine_m = m.w[j]; } }
+        const uint32_t cnt = cnt_of(mine_m);
+        if (mine == kEmpty || cnt < min_cov) return;
+        const uint32_t b = mine & kBMask;
+        const unsigned long long total = (k.k[3] == kEmpty && N::home(N::hash(b), n_buckets) == bk) ? (unsigned long long)sum_of(k, m, b) : total_of(b, n_buckets);
+        f(s, b, mine >> kBBits, cnt, total);
+    }
+    template <class F>
+    __device__ __forceinline__ void for_marked(uint32_t bk, F&& f) const {
+        const uint32_t w = (mk[bk >> 3] >> ((bk & 7u) * 4u)) & 15u;
+        if (!w) return;
+        const bucket k = this->read(bk);
+        const masks m = read_masks(bk);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if ((w >> i) & 1u) f(4u * bk + (uint32_t)i, k.k[i] & kBMask, k.k[i] >> kBBits, cnt_of(m.w[i]));
+    }
+    __device__ __forceinline__ void mark(uint32_t s) const { atomicOr(&mk[s >> 5], 1u << (s & 31u)); }
+    __device__ __forceinline__ void unmark(uint32_t s) const { atomicAnd(&mk[s >> 5], ~(1u << (s & 31u))); }
+};
+
 // The 6-byte slots for k-mer sets of up to 2^27 - 16 k-mers whatever the reads' lengths (distances up to 255): the 32-bit key
 // [d : 8 | b >> S : 24] leaves out the low S <= 3 bits of the rank, and the table is cut into 2^S REGIONS of equal size —
 // a key lives in the region of its rank's low bits (home bucket, probe chain and the chain walk for the totals all stay
@@ -806,6 +1133,7 @@ struct cf_tab_region {
     static constexpr int PB = 4;
     static constexpr uint32_t kBBits = 24, kBMask = (1u << kBBits) - 1u;
     static constexpr uint32_t kSlotBytes = 6, kPerBucket = PB, kAll = (1u << PB) - 1u;
+    static constexpr bool kMaskTab = false;
     static constexpr uint32_t kEmpty = 0xFFFFFFFFu;
     struct bucket { uint32_t k[PB]; };
     struct counts { uint32_t w[PB / 2]; };
@@ -1076,16 +1404,22 @@ __device__ __forceinline__ uint32_t cf_rank_in(unsigned long long m) { return __
 // general insert: walk buckets from bk; claims the first empty slot with a CAS when the key is absent.
 // Returns 1 when a new key was created; hot := the slot when this occurrence brought its count to exactly min_cov.
 template <class Tab>
-__device__ __forceinline__ uint32_t cf_dist_insert(const Tab& T, uint32_t n_buckets, uint32_t bk, uint32_t b, uint32_t dd, uint32_t* sh, uint32_t min_cov, uint32_t& hot, unsigned long long* trips = nullptr) {
+__device__ __forceinline__ uint32_t cf_dist_insert(const Tab& T, uint32_t n_buckets, uint32_t bk, uint32_t b, uint32_t dd, uint32_t* sh, uint32_t min_cov, uint32_t& hot, unsigned long long* trips = nullptr, uint32_t bit = 0u) {      // (bit: the posting's place in the union, cf_tab_mask only)
     for (uint32_t tries = 0; tries < 9 * n_buckets; ++tries) {
         if (trips) ++*trips;
         const typename Tab::bucket k = T.read(bk);
         const int m = T.match(k, b, dd);
-        if (m >= 0) { if (T.add(bk, m) == min_cov) hot = Tab::kSlotsPerBucket * bk + (uint32_t)m; return 0u; }
+        if (m >= 0) {
+            uint32_t now;
+            if constexpr (Tab::kMaskTab) now = T.add(bk, m, bit); else now = T.add(bk, m);
+            if (now == min_cov) hot = Tab::kSlotsPerBucket * bk + (uint32_t)m;
+            return 0u;
+        }
         const int e = Tab::empty(k);
         if (e >= 0) {
             uint32_t cnt;
-            const int st = T.claim_finish(T.claim_issue(bk, e, b, dd), bk, e, b, dd, cnt);
+            int st;
+            if constexpr (Tab::kMaskTab) st = T.claim_finish(T.claim_issue(bk, e, b, dd), bk, e, b, dd, cnt, bit); else st = T.claim_finish(T.claim_issue(bk, e, b, dd), bk, e, b, dd, cnt);
             if (st != 2 && cnt == min_cov) hot = Tab::kSlotsPerBucket * bk + (uint32_t)e;
             if (st == 0) return 1u;
             if (st == 1) return 0u;
@@ -1116,10 +1450,14 @@ __device__ __forceinline__ uint32_t cf_dist_insert(const Tab& T, uint32_t n_buck
 // cf_items_count_kernel also counts the partner entries that are the first k-mer itself: the pairs of its postings (u, v) in one
 // read with min_d <= v - u <= max_d (the reference skips a == b, distance_based_kmer_recruitment.py:118; the sweeps count such an
 // entry like any other and the host subtracts this sum).
+// GRP (groups): the list of head i is the UNION of its group, upost[32 i .. 32 i + ulen[i]) — or, ulen[i] bit 31, the k-mer's own
+// list (a counting group of one); the self pairs are not counted here (cf_member_emissions_kernel counts every member's own)
+template <bool GRP>
 __global__ void __launch_bounds__(256)
 cf_items_count_kernel(const int32_t* __restrict__ order, int64_t n_order, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
                       const cf_dist_rec* __restrict__ urange, const int32_t* __restrict__ rbeg, int32_t min_d, int32_t max_d, uint32_t nw, int sorted_post,
-                      uint32_t* __restrict__ n_items, uint32_t* __restrict__ n_alloc, unsigned long long* __restrict__ self_pairs, const uint32_t* __restrict__ cfirst) {
+                      uint32_t* __restrict__ n_items, uint32_t* __restrict__ n_alloc, unsigned long long* __restrict__ self_pairs, const uint32_t* __restrict__ cfirst,
+                      const int32_t* __restrict__ upost, const uint32_t* __restrict__ ulen) {
     // cfirst != nullptr: n_order CLASSES; class i is the k-mers order[cfirst[i] .. cfirst[i + 1]) — equal posting lists — and order[cfirst[i]] stands
     // for them (the self pairs are the same for every member: counted once, times the members).  nullptr: every k-mer of `order` on its own.
     const int gl = threadIdx.x & 15;
@@ -1128,24 +1466,31 @@ cf_items_count_kernel(const int32_t* __restrict__ order, int64_t n_order, const 
     unsigned long long self = 0;
     // (the first two links of an iteration's chain — order -> post_ptr — are fetched one iteration ahead)
     int64_t p0_n = 0, p1_n = 0;
-    { const int32_t a0 = grp < n_order ? order[cfirst ? (int64_t)cfirst[grp] : grp] : 0; if (grp < n_order) { p0_n = post_ptr[a0]; p1_n = post_ptr[a0 + 1]; } }
+    const int32_t* lp_n = post;      // the list that p0 / p1 index: post[], or (GRP) the unions
+    auto list_of = [&](int64_t i, const int32_t*& lp, int64_t& q0, int64_t& q1) {
+        if constexpr (GRP) { const uint32_t n = ulen[i]; if (!(n >> 31)) { lp = upost; q0 = (int64_t)DIST_GROUP_MAX * i; q1 = q0 + (int64_t)n; return; } }
+        const int32_t a0 = order[cfirst ? (int64_t)cfirst[i] : i];
+        lp = post; q0 = post_ptr[a0]; q1 = post_ptr[a0 + 1];
+    };
+    if (grp < n_order) list_of(grp, lp_n, p0_n, p1_n);
     for (int64_t i0 = 0; i0 < n_order; i0 += n_grp) {      // (uniform trip count: shuffles inside)
         const int64_t i = i0 + grp;
         const bool on = i < n_order;
         const int64_t p0 = p0_n, p1 = p1_n;
-        { const int64_t in = i + n_grp; p0_n = 0; p1_n = 0; if (in < n_order) { const int32_t an = order[cfirst ? (int64_t)cfirst[in] : in]; p0_n = post_ptr[an]; p1_n = post_ptr[an + 1]; } }
+        const int32_t* lp = lp_n;
+        { const int64_t in = i + n_grp; p0_n = 0; p1_n = 0; if (in < n_order) list_of(in, lp_n, p0_n, p1_n); }
         const unsigned long long self_before = self, members = (cfirst && on) ? (unsigned long long)(cfirst[i + 1] - cfirst[i]) : 1ull;
         unsigned long long c = 0;
         int64_t np_max = p1 - p0;      // the longest posting list among the wave's four groups bounds the loops
         for (int d = 16; d <= 32; d <<= 1) np_max = max(np_max, __shfl_xor(np_max, d));
         for (int64_t x0 = 0; x0 < np_max; x0 += 16) {
             const bool hx = p0 + x0 + gl < p1;
-            const int32_t ux = hx ? post[p0 + x0 + gl] : 0;
+            const int32_t ux = hx ? lp[p0 + x0 + gl] : 0;
             cf_dist_rec rx_{0u, 0u, 0u, 0u};
             if (hx) rx_ = urange[ux];
             const int32_t rx = hx ? ux - (int32_t)rx_.ig : -1;      // first unit of the posting's read (ig = the unit's index in its read): ONE gather per posting
             if (hx) c += (rx_.len + DIST_ITEM - 1u) / DIST_ITEM;
-            if (np_max < 2) continue;
+            if (GRP || np_max < 2) continue;
             if (sorted_post && np_max <= 16) {
                 // (round 6) the postings of a k-mer are in ascending unit order (when they were made by the sort: not by the atomics' fill pass), so two of them in ONE read stand next to each other: when
                 // no posting of the wave's four first k-mers has its successor in its own read — the usual case: a rare k-mer occurs once per
@@ -1157,7 +1502,7 @@ cf_items_count_kernel(const int32_t* __restrict__ order, int64_t n_order, const 
             for (int64_t y0 = 0; y0 < np_max; y0 += 16) {
                 const bool hy = p0 + y0 + gl < p1;
                 int32_t uy_l = ux, ry_l = hx ? rx : -2;      // (the same 16 postings: nearly every first k-mer has at most 16)
-                if (y0 != x0) { uy_l = hy ? post[p0 + y0 + gl] : 0; ry_l = hy ? uy_l - (int32_t)urange[uy_l].ig : -2; }
+                if (y0 != x0) { uy_l = hy ? lp[p0 + y0 + gl] : 0; ry_l = hy ? uy_l - (int32_t)urange[uy_l].ig : -2; }
                 for (int j = 0; j < 16; ++j) {
                     const int32_t uy = __shfl(uy_l, j, 16), ry = __shfl(ry_l, j, 16);
                     const int32_t d = uy - ux;
@@ -1195,12 +1540,13 @@ cf_items_count_kernel(const int32_t* __restrict__ order, int64_t n_order, const 
 // If fewer than min_cov postings have a partner unit at all, no pair of a can reach min_cov: nA = 0.
 // -DCF_DIST_DIAG_COUNT: diag[0] += sum of nA, diag[1] += sum of n over the launch (one atomic each per wave, at the kernel's end).
 #define DIST_SEL_CHUNKS 4
+template <bool GRP>      // (as in cf_items_count_kernel; the item records then carry the posting's place in the union, the head whether the group counts)
 __global__ void __launch_bounds__(256)
 cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
                      const cf_dist_rec* __restrict__ urange, uint32_t nw, const uint32_t* __restrict__ n_items, const int64_t* __restrict__ ibase,
                      cf_dist_head* __restrict__ heads, cf_dist_item* __restrict__ items, const int64_t* __restrict__ cloud_ptr, int stream26, int64_t n_units,
                      int32_t min_d, int32_t max_d, uint32_t min_cov, int tail, const unsigned long long* __restrict__ not_a_set, unsigned long long* __restrict__ diag,
-                     const uint32_t* __restrict__ cfirst) {
+                     const uint32_t* __restrict__ cfirst, const int32_t* __restrict__ upost, const uint32_t* __restrict__ ulen) {
     // cfirst: as in cf_items_count_kernel — n_order classes, the work list of a class made from its representative's postings
     // stream26: the 26-bit stream (cf_tab_region26): the item record's low half is [t64 : 9 | unit index mod 128 : 7]
     const int gl = threadIdx.x & 15;
@@ -1215,7 +1561,15 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
 #endif
     int32_t a_n = 0; int64_t p0_n = 0, p1_n = 0, ib_n = 0; uint32_t n_n = 0;      // (fetched one iteration ahead, as in cf_items_count_kernel)
     uint32_t f_n = 0, m_n = 1;      // the class's first position in `order` and its members
-    if (grp < n_order) { f_n = cfirst ? cfirst[grp] : (uint32_t)grp; m_n = cfirst ? cfirst[grp + 1] - f_n : 1u; a_n = order[f_n]; p0_n = post_ptr[a_n]; p1_n = post_ptr[a_n + 1]; n_n = n_items[grp]; ib_n = ibase[grp]; }
+    const int32_t* lp_n = post;      // the list that p0 / p1 index: post[], or (GRP) the unions
+    uint32_t cnt_n = 0;              // GRP: bit 31 = a counting group
+    auto head_of = [&](int64_t i) {
+        f_n = cfirst ? cfirst[i] : (uint32_t)i; m_n = cfirst ? cfirst[i + 1] - f_n : 1u; a_n = order[f_n]; n_n = n_items[i]; ib_n = ibase[i];
+        lp_n = post; cnt_n = 0;
+        if constexpr (GRP) { cnt_n = ulen[i]; if (!(cnt_n >> 31)) { lp_n = upost; p0_n = (int64_t)DIST_GROUP_MAX * i; p1_n = p0_n + (int64_t)cnt_n; return; } }
+        p0_n = post_ptr[a_n]; p1_n = post_ptr[a_n + 1];
+    };
+    if (grp < n_order) head_of(grp);
     for (int64_t i0 = 0; i0 < n_order; i0 += n_grp) {      // (uniform trip count: shuffles inside)
         const int64_t i = i0 + grp;
         const bool on = i < n_order;
@@ -1223,9 +1577,10 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
         const int64_t p0 = p0_n, p1 = p1_n;
         const uint32_t n = n_n, per = (n + nw - 1u) / nw;
         const int64_t ib = ib_n;
-        const uint32_t c_first = f_n, c_members = m_n;
+        const uint32_t c_first = f_n, c_members = GRP ? (m_n | (cnt_n & 0x80000000u)) : m_n;
+        const int32_t* lp = lp_n;
         { const int64_t in = i + n_grp; a_n = 0; p0_n = 0; p1_n = 0; n_n = 0; ib_n = 0; f_n = 0; m_n = 1;
-          if (in < n_order) { f_n = cfirst ? cfirst[in] : (uint32_t)in; m_n = cfirst ? cfirst[in + 1] - f_n : 1u; a_n = order[f_n]; p0_n = post_ptr[a_n]; p1_n = post_ptr[a_n + 1]; n_n = n_items[in]; ib_n = ibase[in]; } }
+          if (in < n_order) head_of(in); }
         cf_dist_item* out = items + ib;
         int64_t np_max = p1 - p0;
         for (int d = 16; d <= 32; d <<= 1) np_max = max(np_max, __shfl_xor(np_max, d));
@@ -1234,7 +1589,7 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
         auto fetch = [&](int64_t q0, cf_dist_rec& r, int32_t& ux, uint32_t& rel64) {
             r = cf_dist_rec{0u, 0u, 0u, 0u}; ux = 0; rel64 = 0u;
             if (p0 + q0 + gl < p1) {
-                ux = post[p0 + q0 + gl];
+                ux = lp[p0 + q0 + gl];
                 r = urange[ux];
                 if (stream26) { const int64_t c64 = (int64_t)ux + 64 <= n_units ? cloud_ptr[(int64_t)ux + 64] : (int64_t)r.e0 + (int64_t)r.len; rel64 = (uint32_t)(min(max(c64, (int64_t)r.e0), (int64_t)r.e0 + (int64_t)r.len) - (int64_t)r.e0); }
             }
@@ -1276,7 +1631,7 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
         }
         uint32_t jA0 = 0, jT0 = nA;      // useful / tail items of the postings before this chunk (group-uniform)
         unsigned long long ne = 0;
-        auto emit = [&](const cf_dist_rec& r, uint32_t rel64, uint32_t cA) {
+        auto emit = [&](const cf_dist_rec& r, uint32_t rel64, uint32_t cA, uint32_t q0) {      // (q0 + gl: the posting's place in its list)
             const uint32_t c = (r.len + DIST_ITEM - 1u) / DIST_ITEM;
             uint32_t incA = cA, incT = c - cA;
             for (int d = 1; d < 16; d <<= 1) { const uint32_t o = __shfl_up(incA, (unsigned)d, 16); if (gl >= d) incA += o; }
@@ -1289,7 +1644,9 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
                 // (round 6: the waves of a workgroup are a power of two in every launch shape the library picks — a mask and a shift
                 // instead of two divisions by a run-time number per item record, 6.9e8 of them at 50 000 reads)
                 const uint32_t jw = nw_pow2 ? (j & (nw - 1u)) : j % nw, jq = nw_pow2 ? (j >> nw_log2) : j / nw;
-                out[CF_DIST_ITEMS_BLOCKED ? (size_t)j : (size_t)jw * per + jq] = cf_dist_item{r.e0 + off, (min(r.len - off, DIST_ITEM) << 16) | low};
+                uint32_t high = min(r.len - off, DIST_ITEM);
+                if constexpr (GRP) high |= ((q0 + (uint32_t)gl) & 31u) << 11;      // [place in the union : 5 | 0 : 2 | entries : 9]
+                out[CF_DIST_ITEMS_BLOCKED ? (size_t)j : (size_t)jw * per + jq] = cf_dist_item{r.e0 + off, (high << 16) | low};
             }
             jA0 += (uint32_t)__shfl((int)incA, 15, 16);
             if (tail_on) jT0 += (uint32_t)__shfl((int)incT, 15, 16);
@@ -1298,11 +1655,11 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
             ne += (unsigned long long)__shfl((long long)l, 0, 16);
         };
 #pragma unroll
-        for (int q = 0; q < DIST_SEL_CHUNKS; ++q) if ((int64_t)q * 16 < np_max) emit(rk[q], r64k[q], ck[q]);
+        for (int q = 0; q < DIST_SEL_CHUNKS; ++q) if ((int64_t)q * 16 < np_max) emit(rk[q], r64k[q], ck[q], (uint32_t)q * 16u);
         for (int64_t q0 = 16 * DIST_SEL_CHUNKS; q0 < np_max; q0 += 16) {      // the rest of a long list (every item useful)
             cf_dist_rec r; int32_t ux; uint32_t rel64;
             fetch(q0, r, ux, rel64);
-            emit(r, rel64, (r.len + DIST_ITEM - 1u) / DIST_ITEM);
+            emit(r, rel64, (r.len + DIST_ITEM - 1u) / DIST_ITEM, (uint32_t)q0);
         }
         if (on && gl == 0) {
             heads[i] = cf_dist_head{(uint32_t)a, n, (unsigned long long)ib, (uint32_t)min(ne, 0x3FFFFFFFull), nA, c_members, c_first};
@@ -1336,12 +1693,15 @@ cf_items_fill_kernel(const int32_t* __restrict__ order, int64_t n_order, const i
 template <class Tab, int D, class Pre, class Body>
 __device__ __forceinline__ void cf_dist_sweep(const cf_dist_args& A, const cf_dist_item* recs, uint32_t mine, const cf_dist_item& my0, Pre&& pre, Body&& body) {
     const uint32_t lane = threadIdx.x & 63u, l4 = lane * DIST_UNROLL;
+    // entries of an item: the record's high half — in a launch with groups (cf_tab_mask) its low 9 bits, under the posting's
+    // place in the group's union [bit : 5 | 0 : 2 | entries : 9]
+    auto len_of = [](uint32_t m) -> uint32_t { return Tab::kMaskTab ? (m >> 16) & 0x1FFu : m >> 16; };
     auto ok_of = [&](uint32_t m) -> uint32_t {      // per-lane mask of the entries of an item that exist
         uint32_t ok = (1u << DIST_UNROLL) - 1u;
-        if ((m >> 16) < DIST_ITEM) {      // (wave-uniform) the last item of a posting
+        if (len_of(m) < DIST_ITEM) {      // (wave-uniform) the last item of a posting
             ok = 0;
 #pragma unroll
-            for (int u = 0; u < DIST_UNROLL; ++u) ok |= (uint32_t)(l4 + (uint32_t)u < (m >> 16)) << u;
+            for (int u = 0; u < DIST_UNROLL; ++u) ok |= (uint32_t)(l4 + (uint32_t)u < len_of(m)) << u;
         }
         return ok;
     };
@@ -1387,8 +1747,8 @@ __device__ __forceinline__ void cf_dist_sweep(const cf_dist_args& A, const cf_di
                     uint32_t bb[DIST_UNROLL], dd_[DIST_UNROLL], qq_[DIST_UNROLL], lo_[DIST_UNROLL];
 #pragma unroll
                     for (int u = 0; u < DIST_UNROLL; ++u) Tab::decode(ring[p][u], cm & 0xFFFFu, l4 + (uint32_t)u, bb[u], dd_[u], qq_[u], lo_[u]);
-                    const uint32_t len = cm >> 16;      // entries of the item (wave-uniform); < DIST_ITEM only for the last item of a posting
-                    if (body(bb, dd_, qq_, lo_, len < DIST_ITEM ? ok_of(cm) : (1u << DIST_UNROLL) - 1u, len)) return true;
+                    const uint32_t len = len_of(cm);      // entries of the item (wave-uniform); < DIST_ITEM only for the last item of a posting
+                    if (body(bb, dd_, qq_, lo_, len < DIST_ITEM ? ok_of(cm) : (1u << DIST_UNROLL) - 1u, len, Tab::kMaskTab ? cm >> 27 : 0u)) return true;
                     ++j;
                 }
             }
@@ -1432,7 +1792,9 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
     T.init(lds_tab, (uint32_t)A.slots);
     T.configure(A, (uint32_t)A.slots / Tab::kPerBucket);
     uint32_t* sk = (uint32_t*)lds_tab;
-    uint16_t* stage = (uint16_t*)(lds_tab + (size_t)A.slots * Tab::kSlotBytes);   // slot indices of the selected edges of a pass
+    size_t tab_bytes = (size_t)A.slots * Tab::kSlotBytes;
+    if constexpr (Tab::kMaskTab) tab_bytes += Tab::extra_bytes((uint32_t)A.slots);      // (the bitmap of the selection marks)
+    uint16_t* stage = (uint16_t*)(lds_tab + tab_bytes);   // slot indices of the selected edges of a pass
     // per-wave queue of pending inserts: candidates are compacted here and inserted 64 at a time by a full wave.
     // Only its own wave touches it: LDS operations of one wave execute in order, and wavefront-scope fences (no
     // instructions) keep the compiler from moving the queue accesses across the drain; a volatile pointer would turn
@@ -1446,6 +1808,9 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
     // one or two of their 64 lanes)
     typename Tab::qitem* ovq = wq0 + (size_t)(nt >> 6) * DIST_QSTRIDE + (size_t)wv * DIST_OVQ;
     uint16_t* hotl = (uint16_t*)(wq0 + (size_t)(nt >> 6) * (DIST_QSTRIDE + DIST_OVQ));      // DIST_HOT_CAP slots whose count reached min_cov during the inserts of the pass
+    // cf_tab_mask: a byte per queued / parked insert next to its 32-bit word — the place, in the group's union, of the posting that brought it
+    uint8_t* wqb = (uint8_t*)(hotl + DIST_HOT_CAP) + (size_t)wv * (DIST_QSTRIDE + DIST_OVQ);
+    uint8_t* ovqb = wqb + DIST_QSTRIDE;
     const uint32_t slots = (uint32_t)A.slots, n_buckets = slots / Tab::kPerBucket;   // slots is a multiple of 8
     unsigned long long acc_E = 0, acc_spill = 0, acc_pass = 0, acc_edges = 0;  // flushed once per workgroup (thread 0)
 #if defined(CF_DIST_DIAG_COUNT)      /* diagnostic build: [0] loop trips of parked inserts [1] overflow calls [2] parked inserts run [3] drains [4] inserts drained */
@@ -1518,7 +1883,8 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
         const int64_t ai = (int64_t)(((unsigned long long)sh[17] << 32) | sh[16]);
         if (ai < 0) break;
         const uint32_t a = sh[18], n_items = sh[19], n_ent_a = sh[22], n_useful = sh[23];
-        const uint32_t n_mem = CLS ? sh[24] : 1u, m_first = CLS ? sh[25] : 0u;
+        const uint32_t n_mem = CLS ? (Tab::kMaskTab ? sh[24] & 0xFFFFu : sh[24]) : 1u, m_first = CLS ? sh[25] : 0u;
+        if constexpr (Tab::kMaskTab) T.set_member(0xFFFFFFFFu, (sh[24] >> 31) != 0u);      // (a head of groups says in bit 31 of its members whether its words are counts: cf_items_fill_kernel)
         // Round 6: the list of slots that reach min_cov (one returning LDS add, a wait and a readfirstlane per drain that has one — on
         // cenX-shaped reads every drain has a dozen) is not kept for a first k-mer that would overflow it anyway: its filter scans the count
         // fields, as it did all along once the list was full (12 of 108 ms there)
@@ -1574,7 +1940,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
                 __syncthreads();      // [sketch cleared]
             }
             {
-                if (CF_DIST_ABL < 6) cf_dist_sweep<Tab, CF_DIST_PF_A>(A, recs, mineA, my0, [](bool) {}, [&](const uint32_t (&bb)[DIST_UNROLL], const uint32_t (&dd_)[DIST_UNROLL], const uint32_t (&qq_)[DIST_UNROLL], const uint32_t (&lo_)[DIST_UNROLL], uint32_t ok, uint32_t len) -> bool {
+                if (CF_DIST_ABL < 6) cf_dist_sweep<Tab, CF_DIST_PF_A>(A, recs, mineA, my0, [](bool) {}, [&](const uint32_t (&bb)[DIST_UNROLL], const uint32_t (&dd_)[DIST_UNROLL], const uint32_t (&qq_)[DIST_UNROLL], const uint32_t (&lo_)[DIST_UNROLL], uint32_t ok, uint32_t len, uint32_t) -> bool {
                     if (CF_DIST_ABL >= 5) { if (bb[0] == 0xFFFFFFF1u && dd_[0] == 77u) sh[13] = 1u; return false; }      // (the loads stay: their data is looked at)
                     // (entries equal to a are counted too: the sketch may only over-count, and the table sweep drops them)
                     uint32_t old_[DIST_UNROLL], sft_[DIST_UNROLL], inc_[DIST_UNROLL];
@@ -1711,7 +2077,9 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
                     if ((uint32_t)lane < m_) {                                                                \
                         uint32_t xb, xd, xk;                                                                  \
                         T.q_take(ovq[otail + (uint32_t)lane], n_buckets, xb, xd, xk);                        \
-                        omade_ = cf_dist_insert(T, n_buckets, xk, xb, xd, sh, A.min_cov, ohot_, CF_DG_PTR);   \
+                        uint32_t obit_ = 0u;                                                                  \
+                        if constexpr (Tab::kMaskTab) obit_ = ovqb[otail + (uint32_t)lane] & 31u;              \
+                        omade_ = cf_dist_insert(T, n_buckets, xk, xb, xd, sh, A.min_cov, ohot_, CF_DG_PTR, obit_); \
                     }                                                                                         \
                     const uint32_t onew_ = (uint32_t)__popcll(cf_ballot(omade_ != 0u));                        \
                     if (onew_ && lane == 0) atomicAdd(&sh[0], onew_);                                         \
@@ -1741,14 +2109,19 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
                         const typename Tab::qitem it2_ = wq[qtail + 64u + (uint32_t)lane];                    \
                         T.q_take(it_, n_buckets, xb, xd, xk);                                                 \
                         T.q_take(it2_, n_buckets, yb, yd, yk);                                                \
+                        uint32_t xbit_ = 0u, ybit_ = 0u;      /* cf_tab_mask: the postings that brought the two pairs */ \
+                        if constexpr (Tab::kMaskTab) {                                                        \
+                            xbit_ = wqb[qtail + (uint32_t)lane] & 31u; ybit_ = wqb[qtail + 64u + (uint32_t)lane] & 31u; \
+                            T.probe2m((uint32_t)lane < n_, xk, T.key_of(xb, xd), xbit_, (uint32_t)lane + 64u < n_, yk, T.key_of(yb, yd), ybit_, A.min_cov, made_, park_, hot_, made2_, park2_, hot2_); \
+                        } else                                                                                \
                         T.probe2((uint32_t)lane < n_, xk, T.key_of(xb, xd), xb, (uint32_t)lane + 64u < n_, yk, T.key_of(yb, yd), yb, n_buckets, A.min_cov, made_, park_, hot_, made2_, park2_, hot2_); \
                         const uint32_t new_ = (uint32_t)__popcll(cf_ballot(made_)) + (uint32_t)__popcll(cf_ballot(made2_)); \
                         if (new_ && lane == 0) atomicAdd(&sh[0], new_);                                       \
                         const unsigned long long pm_ = cf_ballot(park_), pm2_ = cf_ballot(park2_);              \
                         if (pm_ | pm2_) {                                                                     \
-                            if (park_) ovq[otail + cf_rank_in(pm_)] = it_;                                    \
+                            if (park_) { ovq[otail + cf_rank_in(pm_)] = it_; if constexpr (Tab::kMaskTab) ovqb[otail + cf_rank_in(pm_)] = (uint8_t)xbit_; } \
                             otail += (uint32_t)__popcll(pm_);                                                 \
-                            if (park2_) ovq[otail + cf_rank_in(pm2_)] = it2_;                                 \
+                            if (park2_) { ovq[otail + cf_rank_in(pm2_)] = it2_; if constexpr (Tab::kMaskTab) ovqb[otail + cf_rank_in(pm2_)] = (uint8_t)ybit_; } \
                             otail += (uint32_t)__popcll(pm2_);                                                \
                         }                                                                                     \
                         CF_DIST_HOT(hot_)                                                                     \
@@ -1811,8 +2184,8 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
 #endif
                         while (otail >= 32u || (final && qtail == 0u && otail > 0u)) { CF_DG(const unsigned long long t0_ = __builtin_amdgcn_s_memtime();) CF_DIST_OVERFLOW(min(otail, 64u)) CF_DG(if (lane == 0) dg[5] += __builtin_amdgcn_s_memtime() - t0_;) }
                     }
-                }, [&](const uint32_t (&bb)[DIST_UNROLL], const uint32_t (&dd_)[DIST_UNROLL], const uint32_t (&qq_)[DIST_UNROLL], const uint32_t (&lo_)[DIST_UNROLL], uint32_t ok, uint32_t len) -> bool {
-                    if (too_full) return true;     // (wave-uniform, set by the drains: the fill only changes there) the pass will be split
+                }, [&](const uint32_t (&bb)[DIST_UNROLL], const uint32_t (&dd_)[DIST_UNROLL], const uint32_t (&qq_)[DIST_UNROLL], const uint32_t (&lo_)[DIST_UNROLL], uint32_t ok, uint32_t len, uint32_t ib) -> bool {      // (ib: the posting's place in the group's union, wave-uniform; cf_tab_mask only)
+                    if (too_full) return true;    // (wave-uniform, set by the drains: the fill only changes there) the pass will be split
                     // Entries equal to a itself are NOT told apart here (round 2 spent 13 vector instructions per step on it): they are
                     // rare (a k-mer twice in one read), the filter never selects a slot whose b is a, and the emission count of the
                     // launch has them subtracted on the host (cf_self_pairs_kernel counts them from the posting lists).
@@ -1849,7 +2222,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
                         const unsigned long long cm = cf_ballot(c_[u]);
                         const uint32_t at = qtail + cf_rank_in(cm);
                         const typename Tab::qitem qv = T.q_push(bb[u], dd_[u], qq_[u], n_buckets);
-                        if (c_[u]) wq[at] = qv;
+                        if (c_[u]) { wq[at] = qv; if constexpr (Tab::kMaskTab) wqb[at] = (uint8_t)ib; }
                         qtail += (uint32_t)__popcll(cm);
                     }
 #else
@@ -1857,7 +2230,11 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
                     for (int u = 0; u < DIST_UNROLL; ++u) {
                         const unsigned long long cm = cf_ballot(c_[u]);
                         if (cm) {
-                            if (c_[u]) wq[qtail + cf_rank_in(cm)] = T.q_push(bb[u], dd_[u], qq_[u], n_buckets);
+                            if (c_[u]) {
+                                const uint32_t at = qtail + cf_rank_in(cm);
+                                wq[at] = T.q_push(bb[u], dd_[u], qq_[u], n_buckets);
+                                if constexpr (Tab::kMaskTab) wqb[at] = (uint8_t)ib;      // (the parallel byte queue: which posting of the union brought the pair)
+                            }
                             qtail += (uint32_t)__popcll(cm);
                         }
                     }
@@ -1966,6 +2343,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
             uint32_t sel_prev = 0, sp_left = 0;
             for (uint32_t mj = 0; mj < n_mem; ++mj) {
                 const uint32_t am = mj ? (uint32_t)A.order[(size_t)m_first + mj] : a;
+                if constexpr (Tab::kMaskTab) T.set_member(A.member_mask[(size_t)m_first + mj], T.counting);      // the member's own postings among the union's
                 const unsigned long long ch_base = ((unsigned long long)sh[29] << 32) | sh[28];
                 const uint32_t ch_rows = sh[27];
                 auto put_row = [&](unsigned long long o, uint32_t b, uint32_t dd, uint32_t cnt) {
@@ -2077,7 +2455,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
         if (spilled && t == 0) ++acc_spill;
     }
     if (t == 0) {
-        if (acc_E) atomicAdd(&A.counters[1], acc_E);
+        if (acc_E && !Tab::kMaskTab) atomicAdd(&A.counters[1], acc_E);      // (groups: the members' own partner entries were summed by cf_member_emissions_kernel; what a pass sweeps is the union's)
         if (acc_spill) atomicAdd(&A.counters[2], acc_spill);
         if (acc_pass) atomicAdd(&A.counters[5], acc_pass);
         if (acc_edges) atomicAdd(&A.counters[6], acc_edges);
@@ -2205,7 +2583,7 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     unsigned long long* d_cnt = nullptr;
     int64_t n_post = 0;
     unsigned long long h_cnt[8] = {0};
-    const size_t n_cnt = 8 + 16 * 9;   // counters + 8 queue heads on their own cache lines; [144] a cloud row is not a set (cf_entry_unit_kernel) [145, 146] diagnostic build: useful items, items [147] entries swept once per class
+    const size_t n_cnt = 8 + 16 * 9;   // counters + 8 queue heads on their own cache lines; [144] a cloud row is not a set (cf_entry_unit_kernel) [145, 146] diagnostic build: useful items, items [147] entries swept once per class [148] postings of the groups' unions [149] classes inside the groups
     const int max_blocks = std::max(1, ctx->n_cu) * 8;
     cf_free_edges(ctx);      // (the buffer of this call is allocated below, once the launch shape is known)
     cf_scratch tmp(ctx);
@@ -2306,6 +2684,11 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         // up to 2^26 ranks and distances up to 127: the region table behind the 4-byte stream [unit index mod 64 : 6 | rank : 26]
         region26 = region && !ctx->dist_region_bytes && K <= ((int64_t)1 << 26) && d_need <= 127 && stream4_ok;
     }
+    // groups of first k-mers: knob dist_groups, on top of the classes' conditions; the 6-byte layout's stream and keys only
+    // (the wide, region and 26-bit-stream layouts keep the classes), and only in a launch that runs the sketch first: without it every partner entry of
+    // the union needs a slot of a table that has fewer of them (8 bytes each), and the unions' tables split where the members' own did not.
+    // Decided on the device: clouds that are not sets form groups of one that count.
+    const bool groups_fit = CF_DIST_HAS_GROUPS && ctx->dist_groups && ctx->dist_classes && by_sort && narrow && ctx->dist_sketch && min_cov >= 2 && min_cov <= 200;
     if (max_post >= (1u << 23) || (wide16 && max_post > 32767u)) return cf_fail(ctx, -34, wide16 ? "cf_dist_edges: distances above 255 with a k-mer of more than 32767 postings" : "cf_dist_edges: a k-mer has more than 2^23 postings");
     if (narrow || region26) { CF_TRY(tmp.get(&d_packed, (size_t)v_n_entries + DIST_ITEM, "packed cloud entries")); }
     else if (region) { CF_TRY(tmp.get(&d_entry_i8, (size_t)v_n_entries + 4 * DIST_ITEM, "entry unit indices (bytes)")); }
@@ -2323,7 +2706,6 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     A.stage_cap = (uint32_t)std::min(ctx->dist_stage, DIST_STAGE_CAP);
     A.hot_cap = ctx->dist_hot_cap > 0 ? (uint32_t)ctx->dist_hot_cap : 0xFFFFFFFFu;
     A.hot_entries = ctx->dist_hot_entries >= 0 ? (uint32_t)ctx->dist_hot_entries : 0xFFFFFFFFu;
-    const uint32_t slot_bytes = (narrow || region) ? cf_tab_narrow::kSlotBytes : cf_tab_wide::kSlotBytes;
     // launch shape: two 512-thread workgroups per CU (80 KiB of LDS each) overlap each other's latency-bound phases
     // and win when a first k-mer has few pair emissions; with many (long reads, high coverage) the halved table and
     // sketch cost more than the overlap gains, and one 1024-thread workgroup with the whole LDS wins (measured:
@@ -2346,17 +2728,28 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         const double cloud = (double)(e1 - e0) / (double)(u1 - u0), post_per_unit = (double)n_post / (double)(u1 - u0);
         per_first = (double)partner_units * cloud * post_per_unit / (double)std::max<int64_t>(1, (K - part + n_parts - 1) / n_parts);
     }
+    // ... and only where a first k-mer has few pair emissions, the regime of the two-workgroup launch shape below.  Measured on cenX-shaped reads
+    // (60 000 emissions per first k-mer, var_len 8): one first k-mer brings 7 - 8 000 keys to a mask table whose fill limit is about
+    // 9 000, the union of a group more — the tables split and are streamed again: 119.9 ms per step against 89.2 with classes.
+    const bool groups = groups_fit && per_first <= 32768.0;
+    const uint32_t slot_bytes = groups ? cf_tab_mask<8>::kSlotBytes : (narrow || region) ? cf_tab_narrow::kSlotBytes : cf_tab_wide::kSlotBytes;
     int wgs = ctx->dist_wgs, block = ctx->dist_block;
     if (wgs == 0) wgs = (block > 512 || per_first > 32768.0) ? 1 : 2;
     if (block == 0) block = wgs == 1 ? 1024 : 512;
     // LDS: everything but the table is fixed; dist_slots (the table budget in 8-byte units) defaults to all the rest
     const size_t qitem_bytes = narrow ? sizeof(cf_tab_narrow::qitem) : sizeof(cf_tab_wide::qitem);      // (the region layouts queue 64-bit items, like the wide one)
-    const size_t lds_fixed = DIST_LDS_HEAD + (size_t)(2 * DIST_STACK) * 4 + DIST_STAGE_CAP * 2 + 16 + (size_t)(block / 64) * (DIST_QSTRIDE + DIST_OVQ) * qitem_bytes + DIST_HOT_CAP * 2;
+    const size_t lds_fixed = DIST_LDS_HEAD + (size_t)(2 * DIST_STACK) * 4 + DIST_STAGE_CAP * 2 + 16 + (size_t)(block / 64) * (DIST_QSTRIDE + DIST_OVQ) * qitem_bytes + DIST_HOT_CAP * 2
+                             + (groups ? (((size_t)(block / 64) * (DIST_QSTRIDE + DIST_OVQ) + 15) & ~(size_t)15) : 0);      // (groups: a byte per queued insert)
     const int64_t budget8 = ((int64_t)160 * 1024 / wgs - (int64_t)lds_fixed) / 8;
     if (budget8 < 256) return cf_fail(ctx, -22, "cf_dist_edges: dist_wgs leaves no LDS for the table");
     if (ctx->dist_slots > budget8) return cf_fail(ctx, -22, "cf_dist_edges: dist_slots does not fit the 160 KiB LDS next to the work lists");
     const int64_t slots8 = ctx->dist_slots ? ctx->dist_slots : budget8;
     A.slots = (int32_t)((slots8 * 8 / slot_bytes) & ~(region ? (int64_t)(32 << reg_shift) - 1 : 7ll));      // (regions: equal parts of whole 8-slot groups)
+    if (groups) {      // 8 bytes per slot and the bitmap of the marks (16 bytes per 128 slots or part of them) inside the same budget
+        A.slots = (int32_t)((slots8 * 8 / cf_tab_mask<8>::kSlotBytes) & ~7ll);
+        while (A.slots > 8 && (int64_t)A.slots * cf_tab_mask<8>::kSlotBytes + cf_tab_mask<8>::extra_bytes((uint32_t)A.slots) > slots8 * 8) A.slots -= 8;
+    }
+    const size_t tab_extra = groups ? cf_tab_mask<8>::extra_bytes((uint32_t)A.slots) : 0;
     if (A.slots >= 0xFFFF) return cf_fail(ctx, -22, "cf_dist_edges: more than 65534 table slots (16-bit slot indices; 0xFFFF marks an unused entry of the hot list)");
     A.fill_limit = (uint32_t)((int64_t)A.slots * ctx->dist_fill_pct / 100);   // checked once per wave step: leave slack below the physical size
     {   //  the fill level a drain looks at lags by one drain: every wave may put 2 x 128 fresh keys behind the limit before it
@@ -2368,7 +2761,7 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     }
     A.est_limit = (uint32_t)((int64_t)A.fill_limit * 100 / ctx->dist_est_pct);
     A.counters = d_cnt; A.unique_bits = ctx->d_unique_bits;
-    const size_t lds = (size_t)A.slots * slot_bytes + lds_fixed;
+    const size_t lds = (size_t)A.slots * slot_bytes + tab_extra + lds_fixed;
     A.sketch = (ctx->dist_sketch && min_cov >= 2 && min_cov <= 200) ? 1 : 0;
     A.sk_shift = 32; A.sk_counters = 1;
     const size_t sk_room = (size_t)A.slots * slot_bytes + DIST_STAGE_CAP * 2 + 16 + (size_t)(block / 64) * (DIST_QSTRIDE + DIST_OVQ) * qitem_bytes + 2 * DIST_STACK * 4 + DIST_HOT_CAP * 2;   // table + stage + stack + queues + hot list: all dead while the sketch runs
@@ -2392,13 +2785,14 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     // classes of first k-mers with equal posting lists: knob dist_classes; off when the postings came from the atomics'
     // fill pass (unordered lists) and — decided on the device — when a cloud row is not a set
     const bool classes = ctx->dist_classes && by_sort;
-    const int hb = classes ? std::min(ctx->dist_class_bits, 64 - ab - ub) : 0;      // hash bits of the order key (16: two more radix passes)
+    const int hb = classes ? std::min(ctx->dist_class_bits, 64 - ab - ub) : 0;      // hash bits of the order key (16: two more radix passes); with groups: bits of the second posting unit
     int64_t n_heads = 0;
-    uint32_t *d_cflag = nullptr, *d_cfirst = nullptr;
+    uint32_t *d_cflag = nullptr, *d_cfirst = nullptr, *d_ulen = nullptr, *d_mmask = nullptr, *d_newm = nullptr;
+    int32_t* d_upost = nullptr;
     if (K) {
         hipLaunchKernelGGL(cf_order_keys_kernel, dim3((unsigned)cf_grid_for(K, 256, max_blocks)), dim3(256), 0, ctx->stream,
                            (const uint32_t*)d_pcnt, (const uint32_t*)d_first, K, (int)part, (int)n_parts, ab, d_okeys, d_cnt + 6,
-                           hb, (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144));
+                           hb, (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), groups ? 1 : 0);
         unsigned long long h_n = 0;
         CF_HIP(hipMemcpy(&h_n, d_cnt + 6, 8, hipMemcpyDeviceToHost));
         n_order = (int64_t)h_n;
@@ -2414,13 +2808,27 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         CF_TRY(tmp.get(&d_cflag, (size_t)n_order + 1, "class flags"));
         CF_TRY(tmp.get(&d_cfirst, (size_t)n_order + 1, "class starts"));
         CF_HIP(hipMemsetAsync(d_cflag, 0, (size_t)(n_order + 1) * 4, ctx->stream));
+        if (groups) { CF_TRY(tmp.get(&d_mmask, (size_t)n_order + 1, "member masks")); CF_TRY(tmp.get(&d_newm, (size_t)n_order + 1, "members' new postings")); }
+        if (groups)
+            hipLaunchKernelGGL(cf_group_mark_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const unsigned long long*)d_okeys, n_order, ab + hb, ab,
+                               (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), (uint32_t)ctx->dist_group_cap, d_cflag, d_mmask, d_newm);
+        else
         hipLaunchKernelGGL(cf_class_mark_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const unsigned long long*)d_okeys, n_order, ab,
                            (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), d_cflag);
         CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_cflag, d_cidx, n_order, &n_heads));
         hipLaunchKernelGGL(cf_class_first_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const uint32_t*)d_cflag, (const int64_t*)d_cidx, n_order, n_heads, d_cfirst);
+        if (groups) {      // the unions, and the members' own emissions
+            CF_TRY(tmp.get(&d_upost, (size_t)n_heads * DIST_GROUP_MAX + 1, "group unions"));
+            CF_TRY(tmp.get(&d_ulen, (size_t)n_heads + 1, "group union sizes"));
+            hipLaunchKernelGGL(cf_group_fill_kernel, dim3((unsigned)cf_grid_for(n_heads, 256, max_blocks)), dim3(256), 0, ctx->stream, (const int32_t*)d_order, (const uint32_t*)d_cfirst, n_heads,
+                               (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), (uint32_t)ctx->dist_group_cap, (const uint32_t*)d_newm, (const uint32_t*)d_mmask,
+                               d_upost, d_ulen, d_cnt + 148, d_cnt + 4);
+            hipLaunchKernelGGL(cf_member_emissions_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_order, (const int64_t*)d_post_ptr, (const int32_t*)d_post,
+                               (const cf_dist_rec*)d_urange, (const int32_t*)d_rend, min_d_eff, max_d, d_cnt + 1, d_cnt + 3);
+        }
         CF_KERNEL_CHECK("the class kernels");
     }
-    A.order = d_order; A.n_order = n_heads;
+    A.order = d_order; A.n_order = n_heads; A.member_mask = d_mmask;
     // the work lists of the sweeps (heads + item records, laid out for workgroups of `block` threads): count, scan, fill
     if (n_heads) {
         const uint32_t nw = (uint32_t)block / 64u;
@@ -2429,15 +2837,15 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         CF_TRY(tmp.get(&d_ialloc, (size_t)n_heads + 1, "item slots"));
         CF_TRY(tmp.get(&d_ibase, (size_t)n_heads + 1, "item bases"));
         CF_TRY(tmp.get(&d_heads, (size_t)n_heads, "first k-mer heads"));
-        hipLaunchKernelGGL(cf_items_count_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_heads, (const int64_t*)d_post_ptr,
+        hipLaunchKernelGGL(groups ? cf_items_count_kernel<true> : cf_items_count_kernel<false>, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_heads, (const int64_t*)d_post_ptr,
                            (const int32_t*)d_post, (const cf_dist_rec*)d_urange, (const int32_t*)d_rbeg, min_d_eff, max_d, nw, by_sort ? 1 : 0, d_icnt, d_ialloc, d_cnt + 3,
-                           (const uint32_t*)d_cfirst);
+                           (const uint32_t*)d_cfirst, (const int32_t*)d_upost, (const uint32_t*)d_ulen);
         CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_ialloc, d_ibase, n_heads, &n_item_slots));
         CF_TRY(tmp.get(&d_items, (size_t)n_item_slots + 64, "item records"));
-        hipLaunchKernelGGL(cf_items_fill_kernel, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_heads, (const int64_t*)d_post_ptr,
+        hipLaunchKernelGGL(groups ? cf_items_fill_kernel<true> : cf_items_fill_kernel<false>, dim3((unsigned)g_items), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_heads, (const int64_t*)d_post_ptr,
                            (const int32_t*)d_post, (const cf_dist_rec*)d_urange, nw, (const uint32_t*)d_icnt, (const int64_t*)d_ibase, d_heads, d_items,
                            v_cloud_ptr, region26 ? 1 : 0, U, min_d_eff, max_d, min_cov, (ctx->dist_sketch_tail && A.sketch) ? 1 : 0,
-                           (const unsigned long long*)(d_cnt + 144), d_cnt + 145, (const uint32_t*)d_cfirst);
+                           (const unsigned long long*)(d_cnt + 144), d_cnt + 145, (const uint32_t*)d_cfirst, (const int32_t*)d_upost, (const uint32_t*)d_ulen);
     }
     A.heads = d_heads; A.items = d_items;
     const int64_t n_a = n_heads;
@@ -2448,6 +2856,9 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
                                : narrow_db == 8 ? cf_dist_kernel<cf_tab_narrow_t<8>, CLS> : narrow_db == 7 ? cf_dist_kernel<cf_tab_narrow_t<7>, CLS>                                               \
                                : narrow_db == 6 ? cf_dist_kernel<cf_tab_narrow_t<6>, CLS> : cf_dist_kernel<cf_tab_narrow_t<5>, CLS>)
     void (*kern)(cf_dist_args) = classes ? CF_DIST_KERN(true) : CF_DIST_KERN(false);      // (without classes: the kernel without the member loop)
+#if CF_DIST_HAS_GROUPS
+    if (groups) kern = narrow_db == 8 ? cf_dist_kernel<cf_tab_mask<8>, true> : narrow_db == 7 ? cf_dist_kernel<cf_tab_mask<7>, true> : narrow_db == 6 ? cf_dist_kernel<cf_tab_mask<6>, true> : cf_dist_kernel<cf_tab_mask<5>, true>;
+#endif
 #undef CF_DIST_KERN
     CF_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     // the edge output: edge_cap rows + the unused rest of one chunk per workgroup (the holes; closed below), so that every
@@ -2475,9 +2886,12 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         unsigned long long st[8];
         if (hipMemcpy(st, d_cnt + 8, 64, hipMemcpyDeviceToHost) == hipSuccess)
             std::fprintf(stderr, "[cf_dist diag] parked-insert loop trips=%llu overflow calls=%llu parked inserts run=%llu drains=%llu inserts drained=%llu cycles(sum over waves): parked runs=%llu drains=%llu table sweeps=%llu; waves=%d passes=%llu\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7], grid * (block / 64), h_cnt[5]);
-        unsigned long long su[4];      // [0] a cloud row is not a set [1] sum of the useful items [2] sum of the items [3] partner entries swept, once per class
+        unsigned long long su[4], up[2] = {0, 0};      // [0] a cloud row is not a set [1] sum of the useful items [2] sum of the items [3] partner entries swept, once per class; up: postings of the groups' unions, classes inside the groups
+        const bool have_up = groups && hipMemcpy(up, d_cnt + 148, 16, hipMemcpyDeviceToHost) == hipSuccess;
         if (hipMemcpy(su, d_cnt + 144, 32, hipMemcpyDeviceToHost) == hipSuccess)
-            std::fprintf(stderr, "[cf_dist diag] sketch items=%llu of items=%llu (rows are sets=%d) classes=%lld members=%lld entries swept=%llu of %llu per member\n", su[1], su[2], su[0] ? 0 : 1, (long long)n_heads, (long long)n_order, su[3], h_cnt[1]);
+            std::fprintf(stderr, "[cf_dist diag] sketch items=%llu of items=%llu (rows are sets=%d) classes=%lld members=%lld entries swept=%llu of %llu per member\n", su[1], su[2], su[0] ? 0 : 1, have_up ? (long long)up[1] : (long long)n_heads, (long long)n_order, su[3], h_cnt[1]);      // (with groups: the distinct lists inside the groups)
+        if (have_up)
+            std::fprintf(stderr, "[cf_dist diag] groups=%lld members=%lld union postings=%llu slots=%d split groups=%llu\n", (long long)n_heads, (long long)n_order, up[0], (int)A.slots, h_cnt[2]);
     }
 #endif
 #if defined(CF_DIST_STAMPS)
@@ -2488,6 +2902,7 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
                          st[0], st[1], st[6], st[2], st[3], st[4], st[5], st[7], grid, h_cnt[5]);
     }
 #endif
+    if (h_cnt[4] & 4ull) return cf_fail(ctx, -5, "cf_dist_edges: internal error, a group's union has more postings than its mask has bits");
     if (h_cnt[4] & 2ull) return cf_fail(ctx, -5, "cf_dist_edges: the kernel's dynamic LDS does not begin at address 0");
     if (h_cnt[4]) return cf_fail(ctx, -34, "cf_dist_edges: (b,d) table could not be partitioned far enough");
     // close the holes of the chunked edge output: the valid rows at or above n_valid move into the holes below it

@@ -1,0 +1,146 @@
+"""First k-mers of one first posting unit swept together over the union of their lists (knob dist_groups) on the host-emulated
+kernels: the cases of tests/groupcheck.py, each with the knob at 1 and at 0, against the plain restatement; and, on the
+-DCF_DIST_DIAG_COUNT build, the groups, members and union postings that the launch reports.  tests/test_gpu_dist_groups.py runs the same
+cases on an MI355X."""
+import os
+import re
+import subprocess
+import sys
+
+import pytest
+
+import classcheck as cc
+import groupcheck as gc
+import sketchtailcheck as stc
+from centroflye_amd.engine import Engine
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BASE = dict(dist_slots=2048, dist_block=128)      # (a small distance kernel: the emulator's time per launch goes with its threads and LDS)
+
+
+@pytest.fixture(scope="module")
+def engine(emu_lib):
+    e = Engine(0, emu_lib)
+    for name, value in BASE.items():
+        e.set_param(name, value)
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("min_cov", [1, 2, 4])
+def test_subset_disjoint_and_equal_members_and_pairs_that_only_the_union_or_one_member_reaches(engine, min_cov):
+    c = gc.case("core", min_cov=min_cov)
+    st = gc.run(engine, c)
+    if min_cov >= 2:      # (min_cov 1 runs without the sketch: the launch keeps the classes, the fall-back)
+        gc.check_ran_in_groups(c, st)
+
+
+@pytest.mark.parametrize("params", [dict(min_d=2), dict(max_d=3), dict(min_d=2, max_d=5, min_cov=2)])
+def test_min_d_and_a_max_d_below_one_read(engine, params):
+    gc.run(engine, gc.case("core", **params))
+
+
+@pytest.mark.parametrize("name", ["u32", "u33"])
+def test_unions_of_32_and_33_postings_and_a_list_of_33_on_its_own(engine, name):
+    for c in (gc.case(name), gc.case(name, min_cov=2)):
+        gc.check_ran_in_groups(c, gc.run(engine, c))
+
+
+@pytest.mark.parametrize("cap", [2, 5])
+def test_a_small_cap_closes_the_groups_early(engine, cap):
+    for c in (gc.case("core"), gc.case("u32")):
+        gc.check_ran_in_groups(c, gc.run(engine, c, dict(dist_group_cap=(cap, 32))), cap)
+
+
+@pytest.mark.parametrize("layout", list(gc.LAYOUTS))
+def test_core_reads_in_the_other_layouts(engine, layout):
+    """wide, region and 26-bit-stream layouts keep the classes (the fall-back); one workgroup per CU runs the groups."""
+    gc.run(engine, gc.case("core"), gc.LAYOUTS[layout])
+
+
+def test_a_union_table_that_splits(engine):
+    st = gc.run(engine, cc.case("big", min_cov=2), dict(dist_slots=(256, BASE["dist_slots"])))
+    assert st["n_spilled"] > 0
+    gc.check_ran_in_groups(cc.case("big", min_cov=2), st)      # (groups whose members differ, from the naive clouds; the passes are not pinned when a table split)
+
+
+@pytest.mark.parametrize("min_cov", [2, 4])
+def test_rows_across_edge_chunks_with_a_hot_list_and_a_stage_that_overflow(engine, min_cov):
+    for c in (cc.case("rows", min_cov=min_cov), gc.case("core", min_cov=min_cov)):
+        gc.check_ran_in_groups(c, gc.run(engine, c, gc.TIGHT))
+
+
+def test_edge_cap_below_the_rows(engine):
+    c = cc.case("rows")
+    gc.check_ran_in_groups(c, gc.run(engine, c, edge_cap=50))
+    gc.check_ran_in_groups(c, gc.run(engine, c, gc.TIGHT, edge_cap=50))
+
+
+def test_tail_items_beyond_d_star_of_the_union(engine):
+    """sketchtailcheck's reads: A shares unit 0 of read 0 with other k-mers of other lists — a group whose sketch sweep stops at d*(U), not d*(A)."""
+    c = stc.case("core")
+    (a,) = stc._ranks(c["naive"], stc.reads_of(stc.core_layout()[0], 500, 21)[2], [stc.A])
+    assert [g for g in gc.mixed_groups(c) if a in g[0]], "A in a group with k-mers of other lists"
+    gc.check_ran_in_groups(c, gc.run(engine, c))
+    gc.check_ran_in_groups(c, gc.run(engine, c, dict(dist_sketch_tail=(0, 1))))
+
+
+def test_two_partitions(engine):
+    c = gc.case("core")
+    planted = max(c["groups"], key=lambda g: len(g[0]))[0]
+    assert len(planted) >= 8 and len({x % 2 for x in planted}) == 2, "the members of the planted group fall into both partitions"
+    assert gc.expected_passes(c, part=0, n_parts=2) + gc.expected_passes(c, part=1, n_parts=2) < len({us for us in cc.posting_lists(c["naive"]).values()})
+    gc.run(engine, c, n_parts=2)
+    gc.run(engine, gc.case("u32"), n_parts=2)
+
+
+@pytest.mark.parametrize("doubled", [True, False])
+def test_a_repeated_rank_in_a_row_makes_every_first_kmer_count_alone(engine, doubled):
+    gc.run_repeated_rank(engine, doubled)
+
+
+def test_generator_reads_through_the_exchange_path(emu_lib, tmp_path):
+    gc.run_exchange(emu_lib, str(tmp_path / "rdv"), BASE)
+
+
+DIAG = r"""
+import sys
+root, lib_path, what, on = sys.argv[1], sys.argv[2], sys.argv[3], int(sys.argv[4])
+sys.path[:0] = [root, root + "/tests"]
+import classcheck as cc, groupcheck as gc
+from centroflye_amd import _lib
+from centroflye_amd.engine import Engine
+e = Engine(0, _lib.load(lib_path))
+e.set_param("dist_slots", 2048); e.set_param("dist_block", 128); e.set_param("dist_groups", on)
+if what in ("repeated", "repeated_as_sets"):
+    e.set_param("dist_groups", on)
+    cc.run_repeated_rank(e, what == "repeated")
+else:
+    gc.run(e, gc.case(what), groups=(on,))
+print("DIAG-OK")
+"""
+
+
+@pytest.fixture(scope="module")
+def diag_lib(emu_lib):
+    subprocess.check_call(["bash", os.path.join(ROOT, "tests", "emu", "build_emu.sh"), "diag_count", "-DCF_DIST_DIAG_COUNT"])
+    return os.path.join(ROOT, "tests", "emu", "libcfhip_emu_diag_count.so")
+
+
+def _counts(diag_lib, what, on):
+    r = subprocess.run([sys.executable, "-c", DIAG, ROOT, diag_lib, what, str(on)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "DIAG-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+    return [tuple(int(x) for x in m) for m in re.findall(r"groups=(\d+) members=(\d+) union postings=(\d+)", r.stderr)]
+
+
+def test_the_launch_reports_the_groups_the_rule_gives(diag_lib):
+    for what in ("core", "u32", "u33"):
+        groups = gc.case(what)["groups"]
+        want = (len(groups), sum(len(g[0]) for g in groups), sum(len(g[1]) for g in groups))
+        assert _counts(diag_lib, what, 1) == [want], what
+        assert _counts(diag_lib, what, 0) == [], "knob 0: no groups"
+    # cf_set_clouds: as sets the clouds form groups; with a rank twice in a row every first k-mer is a group of its own (and counts)
+    (as_sets,) = _counts(diag_lib, "repeated_as_sets", 1)
+    assert as_sets[0] < as_sets[1]
+    (doubled,) = _counts(diag_lib, "repeated", 1)
+    assert doubled[0] == doubled[1] == as_sets[1] and doubled[2] == 0
