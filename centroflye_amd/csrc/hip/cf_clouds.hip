@@ -258,16 +258,18 @@ cf_mult_filter_kernel(const int64_t* __restrict__ cloud_ptr, const int32_t* __re
     }
 }
 
+// out[i] = bit i of bits  /  bits |= in (only a bit that is not set yet takes the atomic): the unique mask leaves the device, and
+// travels between ranks, as one byte per k-mer (ncclMax on u8 = OR)
 __global__ void __launch_bounds__(256)
 cf_bits_expand_kernel(const uint32_t* __restrict__ bits, int64_t n, uint8_t* __restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (bits[i >> 5] >> (i & 31)) & 1u;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (uint8_t)((bits[i >> 5] >> (i & 31)) & 1u);
 }
 __global__ void __launch_bounds__(256)
 cf_bits_or_kernel(uint32_t* __restrict__ bits, int64_t n, const uint8_t* __restrict__ in) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        if (in[i]) atomicOr(&bits[i >> 5], 1u << (i & 31));
+        if (in[i] && !((bits[i >> 5] >> (i & 31)) & 1u)) atomicOr(&bits[i >> 5], 1u << (i & 31));
 }
 __global__ void __launch_bounds__(256)
 cf_bits_count_kernel(const uint32_t* __restrict__ bits, int64_t words, unsigned long long* __restrict__ out) {
@@ -329,6 +331,25 @@ int cf_refresh_unique_count(cf_ctx* ctx) {
                        ctx->stream, (const uint32_t*)ctx->d_unique_bits, ctx->unique_words, d_u);
     CF_HIP(hipMemcpy(&hu, d_u, 8, hipMemcpyDeviceToHost));
     ctx->stats.n_unique = (int64_t)hu;
+    return 0;
+}
+
+// The unique bitmap of the installed set as n_kmers bytes of 0 / 1, and such bytes OR-ed into it: device pointers, on the context's
+// stream, no wait (cf_get_unique_mask, cf_or_unique_mask; cf_allreduce_unique of cf_exchange.hip around its all-reduce)
+int cf_unique_bits_to_bytes(cf_ctx* ctx, uint8_t* d_bytes) {
+    const int64_t n = ctx->n_kmers;
+    if (!n) return 0;
+    const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
+    hipLaunchKernelGGL(cf_bits_expand_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_unique_bits, n, d_bytes);
+    CF_KERNEL_CHECK("cf_bits_expand_kernel");
+    return 0;
+}
+int cf_unique_or_bytes(cf_ctx* ctx, const uint8_t* d_bytes) {
+    const int64_t n = ctx->n_kmers;
+    if (!n) return 0;
+    const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
+    hipLaunchKernelGGL(cf_bits_or_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, ctx->d_unique_bits, n, d_bytes);
+    CF_KERNEL_CHECK("cf_bits_or_kernel");
     return 0;
 }
 
@@ -492,8 +513,7 @@ int cf_get_unique_mask(cf_ctx* ctx, uint8_t* mask) {
     cf_scratch tmp(ctx);
     uint8_t* d_tmp = nullptr;
     CF_TRY(tmp.get(&d_tmp, (size_t)n, "unique mask bytes"));
-    const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
-    hipLaunchKernelGGL(cf_bits_expand_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_unique_bits, n, d_tmp);
+    CF_TRY(cf_unique_bits_to_bytes(ctx, d_tmp));
     CF_HIP(hipStreamSynchronize(ctx->stream));
     CF_HIP(hipMemcpy(mask, d_tmp, (size_t)n, hipMemcpyDefault));
     return 0;
@@ -513,8 +533,8 @@ int cf_or_unique_mask(cf_ctx* ctx, const uint8_t* mask) {
     unsigned long long h = 0;
     CF_HIP(hipMemcpy(d_tmp, mask, (size_t)n, hipMemcpyDefault));
     CF_HIP(hipMemsetAsync(d_cnt, 0, 16, ctx->stream));
+    CF_TRY(cf_unique_or_bytes(ctx, d_tmp));
     const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
-    hipLaunchKernelGGL(cf_bits_or_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, ctx->d_unique_bits, n, (const uint8_t*)d_tmp);
     hipLaunchKernelGGL(cf_bits_count_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_unique_bits,
                        ctx->unique_words, d_cnt);
     CF_HIP(hipMemcpy(&h, d_cnt, 8, hipMemcpyDeviceToHost));

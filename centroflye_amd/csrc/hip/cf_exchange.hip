@@ -19,6 +19,8 @@ void cf_free_kmers(cf_ctx* c);
 void cf_free_gview(cf_ctx* c);
 int cf_install_kmers(cf_ctx* ctx, int32_t k);          // cf_clouds.hip
 int cf_refresh_unique_count(cf_ctx* ctx);               // cf_clouds.hip
+int cf_unique_bits_to_bytes(cf_ctx* ctx, uint8_t* d_bytes);         // cf_clouds.hip
+int cf_unique_or_bytes(cf_ctx* ctx, const uint8_t* d_bytes);        // cf_clouds.hip
 int cf_table_ensure(cf_ctx* ctx, uint64_t want_cap);    // cf_count.hip
 
 struct alignas(16) cf_pair { unsigned long long key, val; };
@@ -98,19 +100,6 @@ cf_xch_diff_kernel(const int64_t* __restrict__ ptr, int64_t n, int64_t* __restri
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = ptr[i + 1] - ptr[i];
 }
 
-// out[i] = bytes[i] | bits (bit i)  /  bits |= bytes : the unique mask travels as bytes (ncclMax on u8 = OR)
-__global__ void __launch_bounds__(256)
-cf_xch_bits_to_bytes_kernel(const uint32_t* __restrict__ bits, int64_t n, uint8_t* __restrict__ out) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = (uint8_t)((bits[i >> 5] >> (i & 31)) & 1u);
-}
-__global__ void __launch_bounds__(256)
-cf_xch_bytes_to_bits_kernel(uint32_t* __restrict__ bits, int64_t n, const uint8_t* __restrict__ in) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        if (in[i] && !((bits[i >> 5] >> (i & 31)) & 1u)) atomicOr(&bits[i >> 5], 1u << (i & 31));
-}
-
 void cf_free_gview(cf_ctx* c) {
     cf_release_t(c, c->g_unit_ptr, (size_t)c->g_reads + 1);
     cf_release_t(c, c->g_cloud_ptr, (size_t)c->g_units + 1);
@@ -154,6 +143,54 @@ int allgatherv(cf_ctx* ctx, cf_scratch& keep, const void* d_mine, int64_t my_byt
     std::string err;
     int rc = cm->alltoallv(d_mine, soff.data(), sb.data(), *d_out, roff.data(), bytes.data(), ctx->stream, err);
     if (rc) return comm_fail(ctx, rc, err);
+    return 0;
+}
+
+// Step 1 of cf_exchange_table: the context's table bucketed by owner for a world of W ranks.  Owner histogram per workgroup, scan
+// (owner-major), scatter: *d_send (taken from `keep`) holds start[W] records, those of owner o at start[o] .. start[o + 1]
+int bucket_by_owner(cf_ctx* ctx, cf_scratch& keep, uint32_t W, cf_pair** d_send, std::vector<int64_t>& start) {
+    const int grid = std::max(1, ctx->n_cu) * 8;
+    int64_t* d_blk = nullptr;
+    CF_TRY(keep.get(&d_blk, (size_t)W * grid + 1, "exchange block counts"));
+    const size_t lds = (size_t)W * 4 + 16;
+    hipLaunchKernelGGL(cf_xch_bucket_kernel, dim3((unsigned)grid), dim3(XCH_THREADS), lds, ctx->stream, (const cf_slot*)ctx->d_table,
+                       (uint64_t)ctx->table_cap, W, 0, d_blk, (cf_pair*)nullptr);
+    CF_KERNEL_CHECK("cf_xch_bucket_kernel");
+    CF_HIP(hipMemsetAsync(d_blk + (size_t)W * grid, 0, 8, ctx->stream));
+    int64_t n_local = 0;
+    CF_TRY(cf_scan_exclusive_i64(ctx, d_blk, d_blk, (int64_t)W * grid + 1, &n_local));
+    start.assign((size_t)W + 1, 0);
+    for (uint32_t w = 0; w < W; ++w) CF_HIP(hipMemcpy(&start[w], d_blk + (size_t)w * grid, 8, hipMemcpyDeviceToHost));
+    start[W] = n_local;
+    CF_TRY(keep.get(d_send, (size_t)n_local, "exchange send records"));
+    if (n_local) {
+        hipLaunchKernelGGL(cf_xch_bucket_kernel, dim3((unsigned)grid), dim3(XCH_THREADS), lds, ctx->stream, (const cf_slot*)ctx->d_table,
+                           (uint64_t)ctx->table_cap, W, 1, d_blk, *d_send);
+        CF_KERNEL_CHECK("cf_xch_bucket_kernel");
+    }
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+// Step 4 of cf_exchange_table: the owner's table: fresh, sized for what arrived (an upper bound of the distinct owned keys), the
+// n records of d_recs added into it.  It is the context's table afterwards.
+int merge_records(cf_ctx* ctx, const cf_pair* d_recs, int64_t n, const char* who) {
+    const int grid = std::max(1, ctx->n_cu) * 8;
+    const uint64_t cap = cf_pow2_ceil((uint64_t)std::max<int64_t>(2 * n, 1024));
+    CF_TRY(cf_table_ensure(ctx, cap));
+    CF_HIP(hipMemsetAsync(ctx->d_table, 0, (size_t)cap * sizeof(cf_slot), ctx->stream));
+    cf_scratch tmp(ctx);
+    unsigned int* d_flags = nullptr;
+    CF_TRY(tmp.get(&d_flags, 4, "exchange flags"));
+    CF_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
+    if (n) {
+        hipLaunchKernelGGL(cf_xch_merge_kernel, dim3((unsigned)cf_grid_for(n, 256, grid)), dim3(256), 0, ctx->stream, ctx->d_table,
+                           (uint64_t)(cap - 1), d_recs, n, d_flags);
+        CF_KERNEL_CHECK("cf_xch_merge_kernel");
+    }
+    unsigned int flags = 0;
+    CF_HIP(hipMemcpy(&flags, d_flags, 4, hipMemcpyDeviceToHost));
+    if (flags & 1u) return cf_fail(ctx, -34, std::string(who) + ": owner table full");
     return 0;
 }
 
@@ -217,29 +254,12 @@ int cf_exchange_table(cf_ctx* ctx, int64_t* bytes_sent) {
     CF_HIP(hipSetDevice(ctx->device));
     cf_comm* cm = ctx->comm;
     const uint32_t W = (uint32_t)cm->world;
-    const int grid = std::max(1, ctx->n_cu) * 8;
     cf_scratch tmp(ctx);
-    int64_t* d_blk = nullptr;
-    CF_TRY(tmp.get(&d_blk, (size_t)W * grid + 1, "exchange block counts"));
-    const size_t lds = (size_t)W * 4 + 16;
     // 1. owner histogram per workgroup, scan (owner-major), scatter into the send buffer
-    hipLaunchKernelGGL(cf_xch_bucket_kernel, dim3((unsigned)grid), dim3(XCH_THREADS), lds, ctx->stream, (const cf_slot*)ctx->d_table,
-                       (uint64_t)ctx->table_cap, W, 0, d_blk, (cf_pair*)nullptr);
-    CF_KERNEL_CHECK("cf_xch_bucket_kernel");
-    CF_HIP(hipMemsetAsync(d_blk + (size_t)W * grid, 0, 8, ctx->stream));
-    int64_t n_local = 0;
-    CF_TRY(cf_scan_exclusive_i64(ctx, d_blk, d_blk, (int64_t)W * grid + 1, &n_local));
-    std::vector<int64_t> start((size_t)W + 1, 0);
-    for (uint32_t w = 0; w < W; ++w) CF_HIP(hipMemcpy(&start[w], d_blk + (size_t)w * grid, 8, hipMemcpyDeviceToHost));
-    start[W] = n_local;
+    std::vector<int64_t> start;
     cf_pair* d_send = nullptr;
-    CF_TRY(tmp.get(&d_send, (size_t)n_local, "exchange send records"));
-    if (n_local) {
-        hipLaunchKernelGGL(cf_xch_bucket_kernel, dim3((unsigned)grid), dim3(XCH_THREADS), lds, ctx->stream, (const cf_slot*)ctx->d_table,
-                           (uint64_t)ctx->table_cap, W, 1, d_blk, d_send);
-        CF_KERNEL_CHECK("cf_xch_bucket_kernel");
-    }
-    CF_HIP(hipStreamSynchronize(ctx->stream));
+    CF_TRY(bucket_by_owner(ctx, tmp, W, &d_send, start));
+    const int64_t n_local = start[W];
     // 2. who sends how much to whom: all-gather of the W send counts of every rank
     std::vector<int64_t> sb((size_t)W), soff((size_t)W), rb((size_t)W), roff((size_t)W);
     for (uint32_t w = 0; w < W; ++w) { soff[w] = start[w] * (int64_t)sizeof(cf_pair); sb[w] = (start[w + 1] - start[w]) * (int64_t)sizeof(cf_pair); }
@@ -266,21 +286,8 @@ int cf_exchange_table(cf_ctx* ctx, int64_t* bytes_sent) {
         int rc = cm->alltoallv(d_send, soff.data(), sb.data(), d_recv, roff.data(), rb.data(), ctx->stream, err);
         if (rc) return cf_fail(ctx, rc, err);
     }
-    // 4. the owner's table: fresh, sized for what arrived (an upper bound of the distinct owned keys), records added
-    const uint64_t cap = cf_pow2_ceil((uint64_t)std::max<int64_t>(2 * n_recv, 1024));
-    CF_TRY(cf_table_ensure(ctx, cap));
-    CF_HIP(hipMemsetAsync(ctx->d_table, 0, (size_t)cap * sizeof(cf_slot), ctx->stream));
-    unsigned int* d_flags = nullptr;
-    CF_TRY(tmp.get(&d_flags, 4, "exchange flags"));
-    CF_HIP(hipMemsetAsync(d_flags, 0, 16, ctx->stream));
-    if (n_recv) {
-        hipLaunchKernelGGL(cf_xch_merge_kernel, dim3((unsigned)cf_grid_for(n_recv, 256, grid)), dim3(256), 0, ctx->stream, ctx->d_table,
-                           (uint64_t)(cap - 1), (const cf_pair*)d_recv, n_recv, d_flags);
-        CF_KERNEL_CHECK("cf_xch_merge_kernel");
-    }
-    unsigned int flags = 0;
-    CF_HIP(hipMemcpy(&flags, d_flags, 4, hipMemcpyDeviceToHost));
-    if (flags & 1u) return cf_fail(ctx, -34, "cf_exchange_table: owner table full");
+    // 4. the owner's table: fresh, sized for what arrived, records added
+    CF_TRY(merge_records(ctx, d_recv, n_recv, "cf_exchange_table"));
     ctx->exchange_bytes = n_local * (int64_t)sizeof(cf_pair) - sb[(size_t)cm->rank];
     if (bytes_sent) *bytes_sent = ctx->exchange_bytes;
     return 0;
@@ -389,20 +396,52 @@ int cf_allreduce_unique(cf_ctx* ctx, int64_t* n_unique) {
         cf_scratch tmp(ctx);
         uint8_t* d_bytes = nullptr;
         CF_TRY(tmp.get(&d_bytes, (size_t)n, "unique mask bytes"));
-        const int grid = cf_grid_for(n, 256, std::max(1, ctx->n_cu) * 8);
-        hipLaunchKernelGGL(cf_xch_bits_to_bytes_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->d_unique_bits, n, d_bytes);
-        CF_KERNEL_CHECK("cf_xch_bits_to_bytes_kernel");
+        CF_TRY(cf_unique_bits_to_bytes(ctx, d_bytes));      // the mask travels as bytes (ncclMax on u8 = OR)
         CF_HIP(hipStreamSynchronize(ctx->stream));
         std::string err;
         int rc = ctx->comm->allreduce(d_bytes, n, CF_COMM_U8, CF_COMM_MAX, ctx->stream, err);
         if (rc) return cf_fail(ctx, rc, err);
-        hipLaunchKernelGGL(cf_xch_bytes_to_bits_kernel, dim3((unsigned)grid), dim3(256), 0, ctx->stream, ctx->d_unique_bits, n, (const uint8_t*)d_bytes);
-        CF_KERNEL_CHECK("cf_xch_bytes_to_bits_kernel");
+        CF_TRY(cf_unique_or_bytes(ctx, d_bytes));
         CF_HIP(hipStreamSynchronize(ctx->stream));
     }
     CF_TRY(cf_refresh_unique_count(ctx));
     if (n_unique) *n_unique = ctx->stats.n_unique;
     return 0;
+}
+
+// Self-tests (tests/ only): the two device steps of cf_exchange_table without a communicator, for a world of any size
+int cf_selftest_owner_buckets(cf_ctx* ctx, int32_t world, int64_t* start, uint64_t* keys, uint64_t* vals, int64_t cap, int64_t* n_out) {
+    if (!ctx || !n_out) return -22;
+    if (world < 1 || world > 4096) return cf_fail(ctx, -22, "cf_selftest_owner_buckets: world must be in [1, 4096]");
+    if (!ctx->d_table) return cf_fail(ctx, -22, "cf_selftest_owner_buckets: no table (call cf_count_kmers first)");
+    if (!start || (keys && !vals)) return cf_fail(ctx, -22, "cf_selftest_owner_buckets: null pointer");
+    CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
+    std::vector<int64_t> st;
+    cf_pair* d_send = nullptr;
+    CF_TRY(bucket_by_owner(ctx, tmp, (uint32_t)world, &d_send, st));
+    const int64_t n = st[(size_t)world];
+    *n_out = n;
+    for (int32_t w = 0; w <= world; ++w) start[w] = st[(size_t)w];
+    if (!keys) return 0;      // size query
+    if (n > cap) return cf_fail(ctx, -22, "cf_selftest_owner_buckets: buffer too small");
+    std::vector<cf_pair> h((size_t)n);
+    if (n) CF_HIP(hipMemcpy(h.data(), d_send, (size_t)n * sizeof(cf_pair), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < n; ++i) { keys[i] = h[(size_t)i].key; vals[i] = h[(size_t)i].val; }
+    return 0;
+}
+
+int cf_selftest_merge_records(cf_ctx* ctx, const uint64_t* keys, const uint64_t* vals, int64_t n) {
+    if (!ctx) return -22;
+    if (n < 0 || (n > 0 && (!keys || !vals))) return cf_fail(ctx, -22, "cf_selftest_merge_records: bad record list");
+    CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
+    cf_pair* d_recs = nullptr;
+    CF_TRY(tmp.get(&d_recs, (size_t)n, "selftest records"));
+    std::vector<cf_pair> h((size_t)n);
+    for (int64_t i = 0; i < n; ++i) h[(size_t)i] = cf_pair{keys[i], vals[i]};
+    if (n) CF_HIP(hipMemcpy(d_recs, h.data(), (size_t)n * sizeof(cf_pair), hipMemcpyHostToDevice));
+    return merge_records(ctx, d_recs, n, "cf_selftest_merge_records");
 }
 
 }  // extern "C"

@@ -602,3 +602,26 @@ class Engine:
         out = np.zeros(vals.size + 1, np.int64)
         self._check(self._lib.cf_selftest_scan(self._ctx, _ptr(vals), vals.size, _ptr(out)), "cf_selftest_scan")
         return out
+
+    def selftest_owner_buckets(self, world):
+        """The table bucketed for a virtual world, as cf_exchange_table's send buffer: (start int64[world + 1], keys uint64,
+        vals uint64 = pres | multi << 32); owner o's records are start[o] .. start[o + 1] - 1."""
+        world = int(world)
+        n = C.c_int64()
+        start = np.zeros(max(world, 0) + 1, np.int64)
+        self._check(self._lib.cf_selftest_owner_buckets(self._ctx, world, _ptr(start), None, None, 0, C.byref(n)), "cf_selftest_owner_buckets")
+        keys = np.zeros(max(n.value, 1), np.uint64)
+        vals = np.zeros(max(n.value, 1), np.uint64)
+        self._check(self._lib.cf_selftest_owner_buckets(self._ctx, world, _ptr(start), _ptr(keys), _ptr(vals), n.value, C.byref(n)),
+                    "cf_selftest_owner_buckets")
+        return start, keys[:n.value], vals[:n.value]
+
+    def selftest_merge_records(self, keys, vals):
+        """A fresh table with the records (keys[i], vals[i] = pres | multi << 32) added into it, as the owner's step of
+        cf_exchange_table does with what it received; table() reads it."""
+        keys = np.ascontiguousarray(keys, np.uint64)
+        vals = np.ascontiguousarray(vals, np.uint64)
+        if keys.size != vals.size:
+            raise ValueError("one value per key")
+        self._check(self._lib.cf_selftest_merge_records(self._ctx, _ptr(keys) if keys.size else None, _ptr(vals) if vals.size else None,
+                                                        keys.size), "cf_selftest_merge_records")

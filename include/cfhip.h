@@ -440,6 +440,18 @@ int cf_selftest_scan(cf_ctx* ctx, const int64_t* in, int64_t n, int64_t* out);
 /* the arg-max of the greedy placement (read_placer.py:63-78: larger (s0, s1), then the larger offset, then the smaller id rank)
  * over n candidates given as rows (s0, s1, offset, rank, valid); out6 = (s0, s1, offset, rank, index of the winner, valid) */
 int cf_selftest_argmax(cf_ctx* ctx, const uint32_t* cands, int64_t n, uint32_t* out6);
+/* The two device steps of cf_exchange_table on their own, with no communicator.
+ * cf_selftest_owner_buckets: the context's table bucketed for a virtual world of 1 .. 4096 ranks, as the send buffer of the
+ * exchange: start[world + 1] (start[0] = 0, start[world] = *n_out = the table's keys), the records of owner o at
+ * start[o] .. start[o + 1] - 1 as keys[i] and vals[i] = pres | multi << 32.  keys == NULL asks for start and *n_out alone;
+ * otherwise cap >= *n_out.  The table stays as it is.
+ * cf_selftest_merge_records: what an owner does with the n records (keys[i], vals[i]) it received: a fresh table of
+ * max(1024, 2 n rounded up to a power of two) slots, every record added into it (a key may come any number of times; pres and
+ * multi add up separately); it is the context's table afterwards (cf_get_table).  n = 0 leaves an empty table.
+ * -22: world out of range, no table, null pointers, cap too small. */
+int cf_selftest_owner_buckets(cf_ctx* ctx, int32_t world, int64_t* start /* world + 1 */, uint64_t* keys, uint64_t* vals, int64_t cap,
+                              int64_t* n_out);
+int cf_selftest_merge_records(cf_ctx* ctx, const uint64_t* keys, const uint64_t* vals, int64_t n);
 
 #ifdef __cplusplus
 }

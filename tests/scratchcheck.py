@@ -14,7 +14,9 @@ shared by test_emu_scratch.py (host emulator) and test_gpu_scratch.py (MI355X):
 
 The inputs: shapecheck.repeats_case(1, 4, 0) and cloud_size_case(513) for A1 - A6 and the placement, and the first case of
 mapcheck, scorecheck, editcheck and tandemcheck that gives the kernels work (editcheck's first pair is two empty strings,
-tandemcheck's first case has no reads: neither reaches an allocation).  sequence(engine, steps) runs a part of it: the emulator
+tandemcheck's first case has no reads: neither reaches an allocation), and xchcheck's smallest record set for the device steps of
+the table exchange (cf_selftest_owner_buckets, cf_selftest_merge_records) with their twins cf_reset_table + cf_merge_table and
+cf_or_unique_mask.  sequence(engine, steps) runs a part of it: the emulator
 test uses it to walk every exit that a failed allocation takes."""
 import copy
 import ctypes as C
@@ -28,6 +30,7 @@ import mapcheck
 import scorecheck
 import shapecheck
 import tandemcheck
+import xchcheck
 from centroflye_amd import session
 from centroflye_amd.engine import DeviceError
 from oracle import cport, placer
@@ -71,6 +74,7 @@ def _inputs():
         rng = np.random.default_rng(17)
         _CACHE["sort"] = rng.integers(0, 2 ** 40, 2 * shapecheck.TILE + 3, dtype=np.uint64)
         _CACHE["scan"] = rng.integers(0, 2 ** 36, 2 * 2048 + 5, dtype=np.int64)
+        _CACHE["xch_records"] = min((c for c in xchcheck.merge_cases() if c["recs"]), key=lambda c: len(c["recs"]))
     return _CACHE
 
 
@@ -176,9 +180,20 @@ def _selftests(e):
     assert np.array_equal(e.selftest_scan(inp["scan"]), np.concatenate([[0], np.cumsum(inp["scan"])]))
 
 
-STEPS = ("a1_a6", "place", "cloud513", "map_score", "edit", "tandem", "rr", "selftests")
+def _exchange(e):
+    """The device steps of the table exchange for a virtual world and their host-mediated twins, on xchcheck's smallest records
+    (codes 0 and 2^62 - 1, each twice), every result as xchcheck checks it."""
+    case = _inputs()["xch_records"]
+    xchcheck.check_merge(e, case)
+    table = {x: list(v) for x, v in xchcheck.expected_merge(case["recs"]).items()}
+    xchcheck.check_buckets(e, table, 3, "scratch: " + case["name"])
+    xchcheck.check_merge(e, case, parts=1)
+    xchcheck.check_or_unique_mask(e, xchcheck.MASK_SIZES[2])
+
+
+STEPS = ("a1_a6", "place", "cloud513", "map_score", "edit", "tandem", "rr", "selftests", "exchange")
 MANY_QUERIES = 700
-SMALL_STEPS = ("a1_a6", "map_score_hand", "tandem")      # a sequence of a tenth of a second on the emulator
+SMALL_STEPS = ("a1_a6", "map_score_hand", "tandem", "exchange")      # a sequence of a tenth of a second on the emulator
 
 
 def sequence(e, report, steps=STEPS):
@@ -204,6 +219,8 @@ def sequence(e, report, steps=STEPS):
             _rr(e)
         elif step == "selftests":
             _selftests(e)
+        elif step == "exchange":
+            _exchange(e)
         else:
             raise ValueError(step)
 
@@ -245,6 +262,9 @@ def check_refusals(engine, report):
     assert live[0] == live[1], f"refused cloud: hbm_bytes_live {live}"
     # an unsorted k-mer set: found by the kernel that builds the lookup table, after the set and its tables are allocated
     _refused(engine, -22, "sorted", lambda: engine.set_kmers(np.array([5, 3, 9], np.uint64), 4))
+    # 1025 keys into the 1024 slots of cf_reset_table(k, 0): found by the merge kernel, after the records and the flags are allocated
+    full = (np.arange(1, 1026, dtype=np.uint64), np.ones(1025, np.uint32), np.zeros(1025, np.uint32))
+    _refused(engine, -34, "table full", lambda: (engine.reset_table(31, 0), engine.merge_table(*full)))
     # cf_contig_spread with room for one rank less than there are: found after the flags and their scan
     src = _sources(engine, report)
     try:
