@@ -87,6 +87,9 @@ def lib():
     L.cfh_write_edges.argtypes = [C.c_char_p, C.c_int, C.c_void_p, i32, C.c_void_p, i64, C.c_char_p, C.c_int]
     L.cfh_read_kmers.argtypes = [C.c_char_p, i32, C.c_void_p, i64, pi64, C.c_char_p, C.c_int]
     L.cfh_export_read_units.argtypes = [P, C.c_void_p, C.c_void_p, i64, i64, i64, C.c_char_p, C.c_int, pi64, pi64, C.c_char_p, C.c_int]
+    L.cfh_write_sd_report.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, i64, C.c_void_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p, i32,
+                                      C.POINTER(i64), C.c_char_p, C.c_int]
+    L.cfh_write_sd_report.restype = C.c_int
     L.cfh_write_ualign_report.argtypes = [C.c_char_p, C.c_char_p, C.c_void_p, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, i64, C.c_void_p,
                                           C.c_void_p, C.c_void_p, i64, pi64, C.c_char_p, C.c_int]
     _lib = L
@@ -386,6 +389,29 @@ def write_ualign_report(path, header, unit, names, reads, read_off, hits, op_ptr
                                          reads.ctypes.data, read_off.ctypes.data, ids.ctypes.data, id_off.ctypes.data, len(names),
                                          hits.ctypes.data, op_ptr.ctypes.data, ops.ctypes.data if ops.size else None, int(min_length),
                                          C.byref(n), err, 512), err)
+    return n.value
+
+
+def write_sd_report(path, names, mono_names, info, inst_ptr, inst, min_identity=69):
+    """The report of the built-in monomer decomposer (cfh_write_sd_report): one line per instance in the six columns sd_parser reads,
+    reads in input order.  names / mono_names: the ids (bytes) of the reads and of the monomers; info / inst_ptr / inst:
+    Engine.monodec's.  Returns the number of lines written."""
+    info = np.ascontiguousarray(info)
+    inst = np.ascontiguousarray(inst)
+    inst_ptr = np.ascontiguousarray(inst_ptr, np.int64)
+    if info.size != len(names) or inst_ptr.size != len(names) + 1 or info.dtype.itemsize != 20 or inst.dtype.itemsize != 28:
+        raise ValueError("one name, one record of 5 int32 and one instance pointer per read; instances of 7 int32")
+    id_off = np.zeros(len(names) + 1, np.int64)
+    np.cumsum([len(x) for x in names], out=id_off[1:])
+    ids = np.frombuffer(b"".join(names) + b"\0", np.uint8)
+    m_off = np.zeros(len(mono_names) + 1, np.int64)
+    np.cumsum([len(x) for x in mono_names], out=m_off[1:])
+    m_ids = np.frombuffer(b"".join(mono_names) + b"\0", np.uint8)
+    n = C.c_int64()
+    err = C.create_string_buffer(512)
+    _check(lib().cfh_write_sd_report(os.fsencode(path), ids.ctypes.data, id_off.ctypes.data, len(names), m_ids.ctypes.data, m_off.ctypes.data,
+                                     len(mono_names), info.ctypes.data if info.size else None, inst_ptr.ctypes.data,
+                                     inst.ctypes.data if inst.size else None, int(min_identity), C.byref(n), err, 512), err)
     return n.value
 
 

@@ -66,6 +66,23 @@ class UalignShape(C.Structure):
         "n_batches")] + [("phase_ms", C.c_float * 4)]
 
 
+class MonodecRead(C.Structure):
+    """Mirror of ``cf_monodec_read``."""
+    _fields_ = [(n, C.c_int32) for n in ("status", "strand", "score", "n_inst", "prefix")]
+
+
+class MonodecInst(C.Structure):
+    """Mirror of ``cf_monodec_inst``."""
+    _fields_ = [(n, C.c_int32) for n in ("k", "st", "en", "n_match", "n_mismatch", "n_ins", "n_del")]
+
+
+class MonodecShape(C.Structure):
+    """Mirror of ``cf_monodec_shape``."""
+    _fields_ = [(n, C.c_int64) for n in (
+        "max_cols", "cols_per_thread", "block", "row_chunk", "launch_cap", "batch_bytes", "n_reads", "n_monomers", "n_cols",
+        "n_score_pairs", "n_move_pairs", "n_batches")] + [("phase_ms", C.c_float * 4)]
+
+
 # every symbol include/cfhip.h declares: name -> (restype, argtypes)
 _P, _I64, _I32, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
 _PI64 = C.POINTER(C.c_int64)
@@ -118,6 +135,9 @@ PROTOTYPES = {
     "cf_ualign_run": (C.c_int, [_P, _P, _I32, _P, _P, _I64, _I32, _I32, _I32, _P, C.POINTER(C.c_float)]),
     "cf_ualign_ops": (C.c_int, [_P, _P, _P, _I64, _PI64]),
     "cf_ualign_info": (C.c_int, [_P, C.POINTER(UalignShape)]),
+    "cf_monodec_run": (C.c_int, [_P, _P, _P, _I32, _P, _P, _I64, _I32, _I32, _I32, _P, C.POINTER(C.c_float)]),
+    "cf_monodec_get": (C.c_int, [_P, _P, _P, _I64, _PI64]),
+    "cf_monodec_info": (C.c_int, [_P, C.POINTER(MonodecShape)]),
     "cf_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "cf_get_times": (C.c_int, [_P, C.POINTER(Times)]),
     "cf_set_param": (C.c_int, [_P, C.c_char_p, _I64]),

@@ -607,6 +607,9 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
     } else if (n == "ualign_batch_bytes") {
         if (value < 0 || value > ((int64_t)1 << 36)) return cf_fail(ctx, -22, "ualign_batch_bytes out of range (0 = default, 1 .. 2^36)");
         ctx->ualign_batch_bytes = value;
+    } else if (n == "monodec_batch_bytes") {
+        if (value < 0 || value > ((int64_t)1 << 36)) return cf_fail(ctx, -22, "monodec_batch_bytes out of range (0 = default, 1 .. 2^36)");
+        ctx->monodec_batch_bytes = value;
     } else if (n == "count_mode") {
         ctx->count_mode = value != 0;
     } else if (n == "count_bits") {

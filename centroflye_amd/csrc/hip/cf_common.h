@@ -175,6 +175,13 @@ struct cf_ctx {
     std::vector<uint8_t> ualign_op_bytes;
     cf_ualign_shape ualign_last{};
 
+    // results of the last cf_monodec_run (cf_monodec.hip), in host memory: the reads' records, the instances as a CSR over its reads,
+    // and the run's shape and timings
+    std::vector<cf_monodec_read> monodec_reads;
+    std::vector<int64_t> monodec_ptr;
+    std::vector<cf_monodec_inst> monodec_inst;
+    cf_monodec_shape monodec_last{};
+
     // host <-> device copies of the caller's (pageable) buffers go through pinned staging slots, one per copy thread
     // (cf_api.hip: cf_copy_h2d / cf_copy_d2h)
     static constexpr int kCopyThreads = 16;      // slots; CF_COPY_THREADS (1 .. 16, default 16) picks how many are used
@@ -226,6 +233,7 @@ struct cf_ctx {
     int64_t tandem_batch_windows = 0;   // cf_tandem: windows per batch of whole reads (0 = 2^26; tests force borders inside small inputs)
     int64_t cons_batch_bytes = 0;       // cf_consensus: bytes of move areas per batch of pairs (0 = 2^30; tests force borders inside one position's reads)
     int64_t ualign_batch_bytes = 0;     // cf_ualign: bytes of move areas per batch of pairs of the moves pass (0 = an eighth of the device's memory, 2^28 .. 2^34; tests force one pair per batch)
+    int64_t monodec_batch_bytes = 0;    // cf_monodec: bytes of move areas per batch of pairs of the moves pass (0 = an eighth of the device's memory, 2^28 .. 2^34; tests force one pair per batch)
     int count_mode = 1;         // 1: sort and reduce (cf_count2.hip) when it applies; 0: the atomic table of round 1 (cf_count.hip)
     int count_bits = 0;          // bucket bits of the sort-and-reduce path; 0 = from the number of windows (tests force small / large values)
     int count_slots = 4096;

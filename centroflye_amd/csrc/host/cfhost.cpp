@@ -1513,6 +1513,56 @@ int cfh_write_ualign_report(const char* path, const char* header, const uint8_t*
     return 0;
 }
 
+int cfh_write_sd_report(const char* path, const char* ids, const int64_t* id_off, int64_t n_reads, const char* mono_names,
+                        const int64_t* mono_name_off, int32_t n_monomers, const int32_t* info, const int64_t* inst_ptr, const int32_t* inst,
+                        int32_t min_identity, int64_t* n_written, char* err, int errlen) {
+    if (n_written) *n_written = 0;
+    if (!path || n_reads < 0 || n_monomers < 1 || !id_off || !mono_name_off || (n_reads > 0 && (!info || !inst_ptr))) {
+        set_err(err, errlen, "cfh_write_sd_report: bad arguments");
+        return -22;
+    }
+    // every instance is looked at before anything is written
+    for (int64_t q = 0; q < n_reads; ++q) {
+        const int32_t* h = info + 5 * q;
+        bool ok = (h[1] == 0 || h[1] == 1) && inst_ptr[q + 1] >= inst_ptr[q] && inst_ptr[q + 1] - inst_ptr[q] == h[3];
+        for (int64_t x = inst_ptr[q]; ok && x < inst_ptr[q + 1]; ++x) {
+            const int32_t* a = inst + 7 * x;
+            ok = a[0] >= 0 && a[0] < n_monomers && a[1] >= 0 && a[1] <= a[2] && a[3] >= 0 && a[4] >= 0 && a[5] >= 0 && a[6] >= 0 &&
+                 (int64_t)a[3] + a[4] + a[5] + a[6] > 0;
+        }
+        if (!ok) {
+            set_err(err, errlen, "cfh_write_sd_report: the instances of read " + std::to_string(q) + " do not fit its record");
+            return -22;
+        }
+    }
+    const std::string tmp = std::string(path) + ".tmp";
+    const int fd = ::open(tmp.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
+    if (fd < 0) { set_err(err, errlen, "cannot open " + tmp + " for writing"); return -2; }
+    auto render = [&](int64_t lo, int64_t hi, std::vector<char>& out) {
+        char num[96];
+        for (int64_t q = lo; q < hi; ++q) {
+            const bool minus = info[5 * q + 1] != 0;
+            for (int64_t x = inst_ptr[q]; x < inst_ptr[q + 1]; ++x) {
+                const int32_t* a = inst + 7 * x;
+                const int64_t cols = (int64_t)a[3] + a[4] + a[5] + a[6];
+                out.insert(out.end(), ids + id_off[q], ids + id_off[q + 1]);
+                out.push_back('\t');
+                out.insert(out.end(), mono_names + mono_name_off[a[0]], mono_names + mono_name_off[a[0] + 1]);
+                if (minus) out.push_back('\'');
+                const int n = std::snprintf(num, sizeof num, "\t%d\t%d\t%.2f\t%c\n", a[1], a[2], (double)(100 * (int64_t)a[3]) / (double)cols,
+                                            100 * (int64_t)a[3] >= (int64_t)min_identity * cols ? '+' : '?');
+                out.insert(out.end(), num, num + n);
+            }
+        }
+    };
+    int rc = write_ordered(fd, n_reads, 64, render);
+    if (::close(fd) != 0 && rc == 0) rc = -5;
+    if (rc == 0 && ::rename(tmp.c_str(), path) != 0) rc = -5;
+    if (rc != 0) { ::unlink(tmp.c_str()); set_err(err, errlen, std::string("write to ") + path + " failed"); return rc; }
+    if (n_written) *n_written = n_reads > 0 ? inst_ptr[n_reads] - inst_ptr[0] : 0;
+    return 0;
+}
+
 int cfh_read_kmers(const char* path, int32_t k, uint64_t* out, int64_t cap, int64_t* n_out,
                    char* err, int errlen) {
     if (k < 1 || k > 32) { set_err(err, errlen, "cfh_read_kmers: k out of range"); return -22; }

@@ -583,6 +583,47 @@ class Engine:
         d["phase_ms"] = dict(zip(("copies", "score", "moves", "total"), (float(x) for x in s.phase_ms)))
         return d
 
+    # ------------------------------------------------------------------ the built-in monomer decomposer (cf_monodec.hip)
+    MONODEC_READ_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.MonodecRead._fields_])
+    MONODEC_INST_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.MonodecInst._fields_])
+
+    def monodec(self, monomers, reads, read_off, match=1, mismatch=1, gap=1):
+        """Every read reads[read_off[i]:read_off[i + 1]] cut into a chain of monomer instances, both strands (the rule: include/cfhip.h at
+        cf_monodec_run).  monomers: a list of byte strings of upper-case A, C, G, T.  Returns (info, ptr, inst): a structured array
+        (MONODEC_READ_DTYPE: status, strand, score, n_inst, prefix), one row per read, and the instances as a CSR over the reads
+        (MONODEC_INST_DTYPE: k, st, en, n_match, n_mismatch, n_ins, n_del), left to right."""
+        monomers = [bytes(m) for m in monomers]
+        mono = np.frombuffer(b"".join(monomers), dtype=np.uint8)
+        mono_off = np.zeros(len(monomers) + 1, np.int64)
+        mono_off[1:] = np.cumsum([len(m) for m in monomers], dtype=np.int64)
+        reads = np.frombuffer(reads, np.uint8) if isinstance(reads, (bytes, bytearray, memoryview)) else np.ascontiguousarray(reads, np.uint8)
+        read_off = np.ascontiguousarray(read_off, np.int64).reshape(-1)
+        if read_off.size < 1:
+            raise ValueError("read_off has one entry per read and one more")
+        if int(read_off.max()) > reads.size:
+            raise ValueError("an offset lies beyond the bytes")
+        n = read_off.size - 1
+        info = np.zeros(n, self.MONODEC_READ_DTYPE)
+        ms = C.c_float()
+        self._check(self._lib.cf_monodec_run(self._ctx, _ptr(mono) if mono.size else None, _ptr(mono_off), len(monomers),
+                                             _ptr(reads) if reads.size else None, _ptr(read_off), n, int(match), int(mismatch), int(gap),
+                                             _ptr(info) if n else None, C.byref(ms)), "cf_monodec_run")
+        cnt = C.c_int64()
+        self._check(self._lib.cf_monodec_get(self._ctx, None, None, 0, C.byref(cnt)), "cf_monodec_get")
+        ptr = np.zeros(n + 1, np.int64)
+        inst = np.zeros(max(cnt.value, 1), self.MONODEC_INST_DTYPE)
+        self._check(self._lib.cf_monodec_get(self._ctx, _ptr(ptr), _ptr(inst), cnt.value, C.byref(cnt)), "cf_monodec_get")
+        return info, ptr, inst[:cnt.value]
+
+    def monodec_info(self):
+        """The shape of cf_monodec.hip (max_cols, cols_per_thread, block, row_chunk, launch_cap, batch_bytes), the figures of the last
+        run (n_reads, n_monomers, n_cols, n_score_pairs, n_move_pairs, n_batches) and its device milliseconds per phase."""
+        s = _lib.MonodecShape()
+        self._check(self._lib.cf_monodec_info(self._ctx, C.byref(s)), "cf_monodec_info")
+        d = {n: int(getattr(s, n)) for n, _ in s._fields_ if n != "phase_ms"}
+        d["phase_ms"] = dict(zip(("copies", "score", "moves", "total"), (float(x) for x in s.phase_ms)))
+        return d
+
     # ------------------------------------------------------------------ self tests of primitives
     def selftest_sort(self, keys, bits=64):
         keys = np.ascontiguousarray(keys, np.uint64)

@@ -165,6 +165,20 @@ int cfh_write_ualign_report(const char* path, const char* header, const uint8_t*
                             const int64_t* op_ptr, const uint8_t* ops, int64_t min_length, int64_t* n_written,
                             char* err, int errlen);
 
+/* The report of the built-in monomer decomposer (cf_monodec_run of cfhip.h; scripts/monomer_decomposer.py): one line per
+ * instance, reads in the order given, instances left to right, in the six tab-separated columns scripts/sd_parser.py reads:
+ *   "<read id>\t<monomer name>[']\t<st>\t<en>\t<identity>\t<rel>"
+ * with an apostrophe behind the name on the "-" strand, st / en the first and last read base of the instance,
+ * identity = "%.2f" of 100 n_match / columns (columns = n_match + n_mismatch + n_ins + n_del) and rel = '+' iff
+ * 100 n_match >= min_identity * columns (as integers), else '?'.  Read q has the name ids[id_off[q], id_off[q + 1]), monomer k the
+ * name mono_names[mono_name_off[k], mono_name_off[k + 1]); info: 5 int32 per read (cf_monodec_read); inst_ptr / inst: the
+ * instances (7 int32 each, cf_monodec_inst) as a CSR over the reads.  The unassigned prefix of a read gets no line.  Lines are
+ * rendered by several threads and written in order to "<path>.tmp", which is renamed to path at the end.  *n_written (may be
+ * NULL): the lines written.  -22: an instance outside its monomers or with st > en, before anything is written. */
+int cfh_write_sd_report(const char* path, const char* ids, const int64_t* id_off, int64_t n_reads, const char* mono_names,
+                        const int64_t* mono_name_off, int32_t n_monomers, const int32_t* info, const int64_t* inst_ptr, const int32_t* inst,
+                        int32_t min_identity, int64_t* n_written, char* err, int errlen);
+
 /* Read a k-mer text file (one per line) into 2-bit codes; returns count via n_out, fills out
  * if non-NULL (size-query then fill). All k-mers must have length k and be ACGT. */
 int cfh_read_kmers(const char* path, int32_t k, uint64_t* out, int64_t cap, int64_t* n_out,
