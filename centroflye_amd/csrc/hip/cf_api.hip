@@ -547,6 +547,8 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
     } else if (n == "dist_group_cap") {
         if (value < 1 || value > 32) return cf_fail(ctx, -22, "dist_group_cap out of range (1 .. 32)");
         ctx->dist_group_cap = (int)value;
+    } else if (n == "dist_filter_once") {
+        ctx->dist_filter_once = value != 0;
     } else if (n == "dist_sketch") {
         ctx->dist_sketch = value != 0;
     } else if (n == "dist_est_pct") {

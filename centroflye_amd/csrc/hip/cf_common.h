@@ -213,6 +213,7 @@ struct cf_ctx {
     int dist_class_bits = 16;       // bits of the posting list's hash in the order key (1 .. 16; tests: few bits make different lists collide, which the comparison of the lists must undo)
     bool dist_classes = true;       // first k-mers with equal posting lists share one sweep of cf_dist_kernel (0: every k-mer on its own, as before)
     bool dist_groups = true;        // first k-mers with the same first posting unit share one sweep over the UNION of their lists, a 32-bit mask per (b, d); 0: classes only
+    bool dist_filter_once = true;   // the mask table's filter evaluates every (hot slot, member) pair of a group in one section, rows reserved per group; 0: the loop over the members, one filter each
     int dist_group_cap = 32;        // postings of a group's union (1 .. 32: the mask's bits; tests: small caps close groups early)
     int dist_sketch_bits = 0;   // bits of a sketch counter: 0 = 4 when min_cov <= 9, else 8; 8 forces bytes
     int dist_est_pct = 80;   // expected distinct (b,d) keys per 100 pair emissions: sizes the initial number of table partitions

@@ -32,6 +32,7 @@ int cf_refresh_unique_count(cf_ctx* ctx);  // cf_clouds.hip
 #define DIST_ITEM (64u * DIST_UNROLL)    /* cloud entries one wave takes per step: DIST_UNROLL consecutive ones per lane */
 #define DIST_BM_BITS 65536u              /* bitmap over hash(b): k-mers that may have a selected edge */
 #define DIST_HOT_CAP 2048u               /* slots the insert path can hand to the filter per pass (more: the filter scans the table) */
+#define DIST_MEMBER_KEYS 8               /* masks of one b (its distances in the table) that a thread of the one-section member filter keeps in registers; a b with more walks its chain per member */
 #define DIST_EDGE_CHUNK 8192ull          /* edge rows a workgroup reserves per global atomic */
 #define DIST_OVQ 160u                    /* per-wave list of inserts whose first probe did not finish (run through the probe loop down to < 32 after every drain: 31 + the 128 a drain can park) */
 #define DIST_LDS_HEAD (DIST_BM_BITS / 8 + 128)  /* bitmap + sh (32 words): the fixed head of the kernel's LDS */
@@ -507,6 +508,7 @@ struct cf_dist_args {
     const cf_dist_head* heads;     // the first k-mers of the launch in processing order (cf_items_fill_kernel) ...
     const cf_dist_item* items;     // ... and the item records of their sweeps, laid out per wave of a workgroup of blockDim.x threads
     uint32_t stage_cap;            // <= DIST_STAGE_CAP
+    uint32_t filter_once;          // mask table: the members of a group are filtered in one section (knob dist_filter_once)
     uint32_t hot_cap;              // cap on the filter's list of hot slots (tests: a small one forces the in-scan evaluation)
     uint32_t hot_entries;          // first k-mers with more partner entries than this do not keep the list at all (it would overflow: the filter scans)
     uint32_t* edges;
@@ -1109,6 +1111,24 @@ struct cf_tab_mask : cf_tab_narrow_t<DB, 4> {
         const unsigned long long total = (k.k[3] == kEmpty && N::home(N::hash(b), n_buckets) == bk) ? (unsigned long long)sum_of(k, m, b) : total_of(b, n_buckets);
         f(s, b, mine >> kBBits, cnt, total);
     }
+#if defined(CF_DIST_DIAG_COUNT)
+    // diagnostic build: does eval_slot(s) walk the chain for its total (total_of), and how many buckets does that walk read?  (0: no walk)
+    __device__ __forceinline__ uint32_t diag_walk(uint32_t s, uint32_t n_buckets, uint32_t min_cov) const {
+        const uint32_t bk0 = s >> 2, i = s & 3u;
+        const bucket k0 = this->read(bk0);
+        const uint32_t mine = k0.k[i];
+        if (mine == kEmpty || cnt_of(msk[s]) < min_cov) return 0u;
+        const uint32_t b = mine & kBMask;
+        if (k0.k[3] == kEmpty && N::home(N::hash(b), n_buckets) == bk0) return 0u;
+        uint32_t bk = N::home(N::hash(b), n_buckets), n = 0;
+        for (uint32_t probe = 0; probe < n_buckets; ++probe) {
+            ++n;
+            if (this->read(bk).k[3] == kEmpty) break;
+            bk = bk + 1 == n_buckets ? 0u : bk + 1;
+        }
+        return n;
+    }
+#endif
     template <class F>
     __device__ __forceinline__ void for_marked(uint32_t bk, F&& f) const {
         const uint32_t w = (mk[bk >> 3] >> ((bk & 7u) * 4u)) & 15u;
@@ -1815,6 +1835,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
     unsigned long long acc_E = 0, acc_spill = 0, acc_pass = 0, acc_edges = 0;  // flushed once per workgroup (thread 0)
 #if defined(CF_DIST_DIAG_COUNT)      /* diagnostic build: [0] loop trips of parked inserts [1] overflow calls [2] parked inserts run [3] drains [4] inserts drained */
     unsigned long long dg_swept = 0;      /* thread 0: partner entries of the passes, once per class (acc_E has them once per member) */
+    unsigned long long dg_hot = 0, dg_hot_mem = 0, dg_walks = 0, dg_walk_bk = 0, dg_ovf = 0;      /* the member filter (mask table): thread 0: n_hot per pass, n_hot x members; every thread: eval_slot calls that took total_of, buckets read there */
     unsigned long long dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};      /* [5] shader cycles inside the parked-insert runs [6] inside the drains [7] inside the table sweep, per wave (lane 0) */
 #define CF_DG(X) X
 #define CF_DG_PTR (&dg[0])
@@ -2027,6 +2048,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
         __syncthreads();      // [table cleared] (and, when every b is marked, the bitmap filled and the passes set up)
         while (true) {
             const uint32_t P = sh[3], pidx = sh[4], pmask = P - 1u;   // P is a power of two; P == 1: every b belongs to the pass
+            if constexpr (Tab::kMaskTab) { if (t == 0) { ((uint32_t*)stage)[0] = 0u; ((uint32_t*)stage)[3] = 0u; } }      // the one-section member filter's words of its first batch (visible behind [table swept])
             uint32_t my_e = 0, s_e = 0;      // partner entries swept by this lane (split passes) / by this wave (whole passes)
             CF_STAMP(2);   // pop partition + clear table
             // ---- phase B: sweep again; pairs of this partition whose b is marked go to the wave's queue and are
@@ -2341,6 +2363,148 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
             // row's first column its own.  sh[8] counts the selected rows of all members so far (nobody resets it between members: a member's
             // share is the difference); a class of one takes exactly the path and the barriers of a first k-mer without classes.
             uint32_t sel_prev = 0, sp_left = 0;
+            CF_DG(if (t == 0) { dg_hot += n_hot; dg_hot_mem += (unsigned long long)n_hot * n_mem; })
+            bool once = false;
+            if constexpr (Tab::kMaskTab) once = A.filter_once != 0u && n_hot <= hot_cap && CF_DIST_ABL < 1;      // (uniform)
+            if constexpr (Tab::kMaskTab) if (once) {
+                // ---- every member of the group in ONE section.  The loops of the member loop below are inverted: a thread takes a hot
+                // slot, reads its bucket and the masks of every key of its b ONCE (from the bucket's registers, or one chain walk where eval_slot
+                // walks) and then loops over the members in registers — cnt = cnt_of(mine & M_j), total = sum of cnt_of(w_k & M_j).  The members of a
+                // batch of 32 arrive with one coalesced load (lane j: M_j and a_j) and are handed out with v_readlane: scalar per member, no wait
+                // inside the loop.  Rows are reserved per batch: a lane keeps its selections as a bit per member, a wave takes its range with one
+                // returning LDS add, and behind ONE barrier everyone knows the batch's total; only when the rows pass the end of the workgroup's
+                // chunk does thread 0 reserve the next chunk(s) behind a second barrier — rows below the chunk's remainder go to the old chunk,
+                // the others into the new reservation.  No marks, no stage list, no marked-slot sweep.
+                // cw[n % 3]: rows of batch n, cw[3 + n % 3]: its members with a row.  Three words each in turn: thread 0 clears the words of batch
+                // n + 1 in front of barrier n (their last readers, of batch n - 2, are past barrier n - 1), and a wave that runs ahead into batch n + 1
+                // never touches the words the slow ones still read.  (The words lie at the head of the stage list, which this path does not use.)
+                uint32_t* cw = (uint32_t*)stage;
+                unsigned long long ch_base = ((unsigned long long)sh[29] << 32) | sh[28];
+                uint32_t ch_rows = sh[27], cur = sh[26], batch = 0;      // (uniform: the chunk, and the cursor in it, are kept in registers through the section; batch 0's words cw[0], cw[3] were cleared by thread 0 at the top of the pass loop, in front of [table swept])
+                const bool counting = T.counting;
+                auto cntf = [&](uint32_t w, uint32_t M) -> uint32_t { return counting ? w : (uint32_t)__popc(w & M); };
+                bool p_on = false;      // the previous batch's b of this lane: its unique-mask word is on its way
+                uint32_t p_w = 0, p_b = 0;
+                auto set_unique = [&](uint32_t w, uint32_t b) { const uint32_t bit = 1u << (b & 31); if (!(w & bit)) atomicOr(&A.unique_bits[b >> 5], bit); };
+                for (uint32_t i0 = 0; i0 < n_hot; i0 += (uint32_t)nt) {      // (one round whenever the list is no longer than the workgroup)
+                    const uint32_t i = i0 + (uint32_t)t;
+                    bool act = false, ovf = false;
+                    uint32_t b = 0, dd = 0, mine_m = 0, s = 0xFFFFu;
+                    uint32_t w[DIST_MEMBER_KEYS];
+#pragma unroll
+                    for (int q = 0; q < DIST_MEMBER_KEYS; ++q) w[q] = 0u;
+                    if (i < n_hot) s = hot[i];
+                    if (s != 0xFFFFu) {      // (0xFFFF: an entry of a wave's block of the list that the wave did not fill)
+                        const uint32_t bk = s >> 2, si = s & 3u;
+                        const typename Tab::bucket k = T.read(bk);
+                        const typename Tab::masks m = T.read_masks(bk);
+                        uint32_t mine = k.k[0];
+                        mine_m = m.w[0];
+#pragma unroll
+                        for (int j = 1; j < 4; ++j) { if (si == (uint32_t)j) { mine = k.k[j]; mine_m = m.w[j]; } }
+                        if (mine != Tab::kEmpty && T.all_of(mine_m) >= A.min_cov) {      // (no member counts more than the union)
+                            act = true; b = mine & Tab::kBMask; dd = mine >> Tab::kBBits;
+                            if (k.k[3] == Tab::kEmpty && Tab::N::home(Tab::N::hash(b), n_buckets) == bk) {      // eval_slot's rule: every key of b is in this bucket
+#pragma unroll
+                                for (int j = 0; j < 4; ++j) w[j] = ((k.k[j] & Tab::kBMask) == b && k.k[j] != Tab::kEmpty) ? m.w[j] : 0u;
+                            } else {      // one walk of b's chain: the masks of its keys into registers, the first DIST_MEMBER_KEYS of them
+                                uint32_t n_w = 0, cb = Tab::N::home(Tab::N::hash(b), n_buckets);
+                                for (uint32_t probe = 0; probe < n_buckets; ++probe) {
+                                    const typename Tab::bucket k2 = T.read(cb);
+                                    CF_DG(++dg_walk_bk;)
+                                    const typename Tab::masks m2 = T.read_masks(cb);
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j)
+                                        if ((k2.k[j] & Tab::kBMask) == b && k2.k[j] != Tab::kEmpty) {
+#pragma unroll
+                                            for (int q = 0; q < DIST_MEMBER_KEYS; ++q) w[q] = n_w == (uint32_t)q ? m2.w[j] : w[q];
+                                            ++n_w;
+                                        }
+                                    if (k2.k[3] == Tab::kEmpty) break;
+                                    cb = cb + 1 == n_buckets ? 0u : cb + 1;
+                                }
+                                ovf = n_w > (uint32_t)DIST_MEMBER_KEYS;      // more keys than registers: this slot walks the chain per member (slow, rare)
+                                CF_DG(++dg_walks; dg_ovf += (unsigned long long)ovf;)
+                            }
+                        }
+                    }
+                    for (uint32_t j0 = 0; j0 < n_mem; j0 += 32u, ++batch) {      // (uniform) the members, 32 at a time: a bit each in `selbits`
+                        const uint32_t nbm = min(32u, n_mem - j0), c = batch % 3u, cn = (batch + 1u) % 3u;
+                        uint32_t Mv = 0, Av = 0;
+                        if ((uint32_t)lane < nbm) { Mv = A.member_mask[(size_t)m_first + j0 + (uint32_t)lane]; Av = (j0 + (uint32_t)lane) ? (uint32_t)A.order[(size_t)m_first + j0 + (uint32_t)lane] : a; }
+                        uint32_t selbits = 0, wave_n = 0, wave_mem = 0;
+                        for (uint32_t jj = 0; jj < nbm; ++jj) {
+                            const uint32_t M = (uint32_t)__builtin_amdgcn_readlane((int)Mv, (int)jj), aj = (uint32_t)__builtin_amdgcn_readlane((int)Av, (int)jj);
+                            const uint32_t cnt = cntf(mine_m, M);
+                            bool sel = false;
+                            if (act && cnt >= A.min_cov && b != aj) {
+                                unsigned long long total = 0;
+                                if (ovf) { T.set_member(M, counting); total = T.total_of(b, n_buckets); }
+                                else {
+#pragma unroll
+                                    for (int q = 0; q < DIST_MEMBER_KEYS; ++q) total += cntf(w[q], M);
+                                }
+                                sel = dominant(cnt, total);
+                            }
+                            const unsigned long long bal = cf_ballot(sel);
+                            selbits |= (uint32_t)sel << jj;
+                            wave_n += (uint32_t)__popcll(bal);
+                            wave_mem |= (uint32_t)(bal != 0ull) << jj;
+                        }
+                        uint32_t rel0 = 0;
+                        if (lane == 0 && wave_n) { rel0 = atomicAdd(&cw[c], wave_n); atomicOr(&cw[3u + c], wave_mem); }
+                        if (t == 0) { cw[cn] = 0u; cw[3u + cn] = 0u; }
+                        __syncthreads();      // [batch counted]
+                        rel0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)rel0);
+                        const uint32_t tot = cw[c], end = cur + tot;
+                        unsigned long long nbase = 0;
+                        if (end > ch_rows) {      // (uniform; once per chunk) the rows pass the end of the chunk: thread 0 reserves what is missing, in whole chunks
+                            if (t == 0) {
+                                const unsigned long long take = ((unsigned long long)(end - ch_rows) + A.edge_chunk - 1ull) / A.edge_chunk * A.edge_chunk;
+                                const unsigned long long nb = atomicAdd(&A.counters[0], take);
+                                sh[28] = (uint32_t)nb; sh[29] = (uint32_t)(nb >> 32); sh[27] = (uint32_t)take;
+                            }
+                            __syncthreads();      // [rows reserved]
+                            nbase = ((unsigned long long)sh[29] << 32) | sh[28];
+                        }
+                        // a member has rows when any wave selected something for it: its unique bit (thread j of the batch, which holds a_j) and the edge count
+                        if ((uint32_t)t < nbm && ((cw[3u + c] >> t) & 1u)) atomicOr(&A.unique_bits[Av >> 5], 1u << (Av & 31u));
+                        if (t == 0) acc_edges += tot;
+                        if (wave_n) {      // (wave-uniform) the rows, member by member, from registers
+                            uint32_t run = cur + rel0;
+                            for (uint32_t jj = 0; jj < nbm; ++jj) {
+                                const bool bit = ((selbits >> jj) & 1u) != 0u;
+                                const unsigned long long bal = cf_ballot(bit);
+                                if (!bal) continue;
+                                const uint32_t M = (uint32_t)__builtin_amdgcn_readlane((int)Mv, (int)jj), aj = (uint32_t)__builtin_amdgcn_readlane((int)Av, (int)jj);      // (by the whole wave)
+                                if (bit) {
+                                    const uint32_t r = run + (uint32_t)__popcll(bal & lt);
+                                    const unsigned long long o = r < ch_rows ? ch_base + r : nbase + (r - ch_rows);
+                                    if (o < A.edge_cap) *(cf_u32x4*)(A.edges + 4 * o) = cf_u32x4{dd, aj, b, cntf(mine_m, M)};
+                                }
+                                run += (uint32_t)__popcll(bal);
+                            }
+                        }
+                        // b's unique bit once per lane and batch, whatever the number of its rows: the word is requested here and looked at a batch later
+                        if (p_on) set_unique(p_w, p_b);
+                        p_on = selbits != 0u;
+                        if (p_on) { p_w = A.unique_bits[b >> 5]; p_b = b; }
+                        if (end > ch_rows) { cur = end - ch_rows; ch_base = nbase; ch_rows = sh[27]; } else cur = end;
+                    }
+                }
+                if (p_on) set_unique(p_w, p_b);      // (the one exposed wait of the group)
+                // A pass without a hot slot has met no barrier in this section, and the next first k-mer's head (publish_next above, thread 0)
+                // reaches the other waves only behind one: without it a wave that runs ahead reads the OLD head at the top of the loop and
+                // goes through this first k-mer again, out of step with the workgroup.  (The member loop below has its [filtered] per member.)
+                if (n_hot == 0u) __syncthreads();
+                sp_left = sh[2];      // partitions still on the stack (thread 0 changes the word only behind the next barrier)
+                if (t == 0) {
+                    sh[26] = cur; sh[27] = ch_rows;      // (sh[28, 29] follow every reservation)
+                    ++acc_pass; CF_DG(dg_swept += sh[7];)
+                }
+                CF_STAMP(4);   // filter (all members, rows included)
+            }
+            if (!once)
             for (uint32_t mj = 0; mj < n_mem; ++mj) {
                 const uint32_t am = mj ? (uint32_t)A.order[(size_t)m_first + mj] : a;
                 if constexpr (Tab::kMaskTab) T.set_member(A.member_mask[(size_t)m_first + mj], T.counting);      // the member's own postings among the union's
@@ -2383,6 +2547,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
                         bool sel = false;
                         uint32_t s = 0, eb = 0, ed = 0, ec = 0;
                         if (i < n_hot && (s = hot[i]) != 0xFFFFu) {      // (0xFFFF: an entry of a wave's block of the list that the wave did not fill)
+                            if constexpr (Tab::kMaskTab) { CF_DG(const uint32_t wb_ = T.diag_walk(s, n_buckets, A.min_cov); dg_walks += (unsigned long long)(wb_ != 0u); dg_walk_bk += wb_;) }
                             T.eval_slot(s, n_buckets, A.min_cov, [&](uint32_t, uint32_t b, uint32_t dd, uint32_t cnt, unsigned long long total) { sel = b != am && dominant(cnt, total); eb = b; ed = dd; ec = cnt; });
                         }
                         const bool wrote = keep(sel, s, eb, ed, ec);
@@ -2470,6 +2635,9 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
 #if defined(CF_DIST_DIAG_COUNT)
     for (int i = 0; i < 8; ++i) if (dg[i]) atomicAdd(&A.counters[8 + i], dg[i]);
     if (t == 0 && dg_swept) atomicAdd(&A.counters[147], dg_swept);
+    for (int d = 32; d >= 1; d >>= 1) { dg_walks += __shfl_down(dg_walks, (unsigned)d); dg_walk_bk += __shfl_down(dg_walk_bk, (unsigned)d); dg_ovf += __shfl_down(dg_ovf, (unsigned)d); }
+    if (lane == 0 && dg_walks) { atomicAdd(&A.counters[154], dg_walks); atomicAdd(&A.counters[155], dg_walk_bk); if (dg_ovf) atomicAdd(&A.counters[156], dg_ovf); }
+    if (t == 0 && dg_hot) { atomicAdd(&A.counters[152], dg_hot); atomicAdd(&A.counters[153], dg_hot_mem); }
 #endif
 }
 
@@ -2583,7 +2751,7 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     unsigned long long* d_cnt = nullptr;
     int64_t n_post = 0;
     unsigned long long h_cnt[8] = {0};
-    const size_t n_cnt = 8 + 16 * 9;   // counters + 8 queue heads on their own cache lines; [144] a cloud row is not a set (cf_entry_unit_kernel) [145, 146] diagnostic build: useful items, items [147] entries swept once per class [148] postings of the groups' unions [149] classes inside the groups
+    const size_t n_cnt = 8 + 16 * 9 + 5;   // counters + 8 queue heads on their own cache lines; [144] a cloud row is not a set (cf_entry_unit_kernel) [145, 146] diagnostic build: useful items, items [147] entries swept once per class [148] postings of the groups' unions [149] classes inside the groups [152..155] the member filter: hot slots, hot slots x members, evaluations that walked the chain, buckets read there [156] hot slots of the one-section filter whose b has more than DIST_MEMBER_KEYS keys
     const int max_blocks = std::max(1, ctx->n_cu) * 8;
     cf_free_edges(ctx);      // (the buffer of this call is allocated below, once the launch shape is known)
     cf_scratch tmp(ctx);
@@ -2704,6 +2872,7 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
     A.n_kmers = K; A.part = part; A.n_parts = n_parts; A.min_d = min_d_eff; A.max_d = max_d; A.min_cov = min_cov; A.thr = rel_threshold;
     A.thr_num = (rel_threshold == 0.8 && ctx->dist_int_thr) ? 4u : 0u; A.thr_den = A.thr_num ? 5u : 0u;
     A.stage_cap = (uint32_t)std::min(ctx->dist_stage, DIST_STAGE_CAP);
+    A.filter_once = ctx->dist_filter_once ? 1u : 0u;
     A.hot_cap = ctx->dist_hot_cap > 0 ? (uint32_t)ctx->dist_hot_cap : 0xFFFFFFFFu;
     A.hot_entries = ctx->dist_hot_entries >= 0 ? (uint32_t)ctx->dist_hot_entries : 0xFFFFFFFFu;
     // launch shape: two 512-thread workgroups per CU (80 KiB of LDS each) overlap each other's latency-bound phases
@@ -2890,6 +3059,9 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         const bool have_up = groups && hipMemcpy(up, d_cnt + 148, 16, hipMemcpyDeviceToHost) == hipSuccess;
         if (hipMemcpy(su, d_cnt + 144, 32, hipMemcpyDeviceToHost) == hipSuccess)
             std::fprintf(stderr, "[cf_dist diag] sketch items=%llu of items=%llu (rows are sets=%d) classes=%lld members=%lld entries swept=%llu of %llu per member\n", su[1], su[2], su[0] ? 0 : 1, have_up ? (long long)up[1] : (long long)n_heads, (long long)n_order, su[3], h_cnt[1]);      // (with groups: the distinct lists inside the groups)
+        unsigned long long mf[5];
+        if (hipMemcpy(mf, d_cnt + 152, 40, hipMemcpyDeviceToHost) == hipSuccess)
+            std::fprintf(stderr, "[cf_dist diag] member filter: n_hot=%llu n_hot x members=%llu eval_slot calls with total_of=%llu buckets read in total_of=%llu slots with more keys than registers=%llu\n", mf[0], mf[1], mf[2], mf[3], mf[4]);
         if (have_up)
             std::fprintf(stderr, "[cf_dist diag] groups=%lld members=%lld union postings=%llu slots=%d split groups=%llu\n", (long long)n_heads, (long long)n_order, up[0], (int)A.slots, h_cnt[2]);
     }
