@@ -83,6 +83,23 @@ class MonodecShape(C.Structure):
         "n_score_pairs", "n_move_pairs", "n_batches")] + [("phase_ms", C.c_float * 4)]
 
 
+class Monokmer(C.Structure):
+    """Mirror of ``cf_monokmer``."""
+    _fields_ = [(n, C.c_int32) for n in ("s", "i", "count", "pos")]
+
+
+class MonokmerOcc(C.Structure):
+    """Mirror of ``cf_monokmer_occ``."""
+    _fields_ = [(n, C.c_int32) for n in ("s", "i")]
+
+
+class MonokmersShape(C.Structure):
+    """Mirror of ``cf_monokmers_shape``."""
+    _fields_ = [(n, C.c_int64) for n in (
+        "sort_tile", "scan_tile", "block", "launch_cap", "n_strings", "n_letters", "k", "min_mult", "with_positions", "n_windows",
+        "n_distinct", "n_kmers", "n_occ", "n_rounds", "n_sorts", "n_sort_passes")] + [("phase_ms", C.c_float * 4)]
+
+
 # every symbol include/cfhip.h declares: name -> (restype, argtypes)
 _P, _I64, _I32, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
 _PI64 = C.POINTER(C.c_int64)
@@ -138,6 +155,9 @@ PROTOTYPES = {
     "cf_monodec_run": (C.c_int, [_P, _P, _P, _I32, _P, _P, _I64, _I32, _I32, _I32, _P, C.POINTER(C.c_float)]),
     "cf_monodec_get": (C.c_int, [_P, _P, _P, _I64, _PI64]),
     "cf_monodec_info": (C.c_int, [_P, C.POINTER(MonodecShape)]),
+    "cf_monokmers_run": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _PI64, C.POINTER(C.c_float)]),
+    "cf_monokmers_get": (C.c_int, [_P, _P, _I64, _PI64, _P, _P, _I64, _PI64]),
+    "cf_monokmers_info": (C.c_int, [_P, C.POINTER(MonokmersShape)]),
     "cf_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "cf_get_times": (C.c_int, [_P, C.POINTER(Times)]),
     "cf_set_param": (C.c_int, [_P, C.c_char_p, _I64]),

@@ -182,6 +182,14 @@ struct cf_ctx {
     std::vector<cf_monodec_inst> monodec_inst;
     cf_monodec_shape monodec_last{};
 
+    // results of the last cf_monokmers_run (cf_monokmers.hip), in host memory: the k-mers in the order of first occurrence, their
+    // occurrences as a CSR (when asked for), and the run's shape and timings
+    bool monokmers_have = false;
+    std::vector<cf_monokmer> monokmers_first;
+    std::vector<int64_t> monokmers_ptr;
+    std::vector<cf_monokmer_occ> monokmers_occ;
+    cf_monokmers_shape monokmers_last{};
+
     // host <-> device copies of the caller's (pageable) buffers go through pinned staging slots, one per copy thread
     // (cf_api.hip: cf_copy_h2d / cf_copy_d2h)
     static constexpr int kCopyThreads = 16;      // slots; CF_COPY_THREADS (1 .. 16, default 16) picks how many are used
@@ -338,3 +346,6 @@ int cf_tile_digit_offsets(cf_ctx* ctx, const uint32_t* d_hist, int n_tiles, int 
 int cf_radix_sort_u64(cf_ctx* ctx, unsigned long long* d_keys, unsigned long long* d_tmp, int64_t n, int bits);
 int cf_radix_sort_u64_any(cf_ctx* ctx, unsigned long long* d_keys, unsigned long long* d_tmp, int64_t n, int bits, unsigned long long** result);
 int cf_radix_sort_rec16(cf_ctx* ctx, void* d_recs, void* d_tmp, int64_t n, const int* words, const int* bits, int n_fields);
+// keys per tile of the scan and records per tile of cf_radix_sort_rec16
+int cf_scan_tile();
+int cf_radix_rec16_tile();

@@ -357,6 +357,10 @@ cf_rec16_scatter(const cf_rec16* __restrict__ in, cf_rec16* __restrict__ out, co
     }
 }
 
+// the tiles of the scan and of the record sort, for the shapes a caller reports (cf_monokmers_info)
+int cf_scan_tile() { return SCAN_TILE; }
+int cf_radix_rec16_tile() { return RS_TILE; }
+
 // d_recs: n records of 16 bytes; d_tmp: scratch of the same size; fields: n_fields (word index, significant bits), least
 // significant field first.  The sorted records end in d_recs.
 int cf_radix_sort_rec16(cf_ctx* ctx, void* d_recs, void* d_tmp, int64_t n, const int* words, const int* bits, int n_fields) {

@@ -624,6 +624,56 @@ class Engine:
         d["phase_ms"] = dict(zip(("copies", "score", "moves", "total"), (float(x) for x in s.phase_ms)))
         return d
 
+    # ------------------------------------------------------------------ exact counts of gap-free windows of monostrings (cf_monokmers.hip)
+    MONOKMER_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.Monokmer._fields_])
+    MONOKMER_OCC_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.MonokmerOcc._fields_])
+
+    def monokmers(self, strings, k, min_mult, positions=False, gap=b"?"):
+        """Every k-mer with at least min_mult valid windows over `strings` (a list of byte strings, or (bytes, offsets)), in the order
+        of first occurrence (the rule: include/cfhip.h at cf_monokmers_run).  A window is valid when it lies inside one string and
+        holds no gap byte.  Returns a structured array (MONOKMER_DTYPE: s, i, count, pos — the first window's string, index and
+        offset in the concatenation), one row per k-mer; with positions=True also (ptr int64[n + 1], occ MONOKMER_OCC_DTYPE): every
+        valid window of every k-mer, in ascending (s, i)."""
+        if isinstance(strings, tuple):
+            flat, off = strings
+            flat = np.frombuffer(flat, np.uint8) if isinstance(flat, (bytes, bytearray, memoryview)) else np.ascontiguousarray(flat, np.uint8)
+            off = np.ascontiguousarray(off, np.int64).reshape(-1)
+        else:
+            strings = [s.encode() if isinstance(s, str) else bytes(s) for s in strings]
+            flat = np.frombuffer(b"".join(strings), dtype=np.uint8)
+            off = np.zeros(len(strings) + 1, np.int64)
+            off[1:] = np.cumsum([len(s) for s in strings], dtype=np.int64)
+        if off.size < 1:
+            raise ValueError("the offsets have one entry per string and one more")
+        if int(off.max()) > flat.size:
+            raise ValueError("an offset lies beyond the bytes")
+        gap = gap.encode() if isinstance(gap, str) else bytes(gap)
+        if len(gap) != 1:
+            raise ValueError("the gap is one byte")
+        n = C.c_int64()
+        self._check(self._lib.cf_monokmers_run(self._ctx, _ptr(flat) if flat.size else None, _ptr(off), off.size - 1, int(k), int(min_mult), gap[0],
+                                               1 if positions else 0, C.byref(n), None), "cf_monokmers_run")
+        n_occ = C.c_int64()
+        self._check(self._lib.cf_monokmers_get(self._ctx, None, 0, C.byref(n), None, None, 0, C.byref(n_occ)), "cf_monokmers_get")
+        first = np.zeros(max(n.value, 1), self.MONOKMER_DTYPE)
+        if not positions:
+            self._check(self._lib.cf_monokmers_get(self._ctx, _ptr(first), n.value, None, None, None, 0, None), "cf_monokmers_get")
+            return first[:n.value]
+        ptr = np.zeros(n.value + 1, np.int64)
+        occ = np.zeros(max(n_occ.value, 1), self.MONOKMER_OCC_DTYPE)
+        self._check(self._lib.cf_monokmers_get(self._ctx, _ptr(first), n.value, None, _ptr(ptr), _ptr(occ), n_occ.value, None), "cf_monokmers_get")
+        return first[:n.value], ptr, occ[:n_occ.value]
+
+    def monokmers_info(self):
+        """The shape constants of cf_monokmers.hip (sort_tile, scan_tile, block, launch_cap), the figures of the last run (n_strings,
+        n_letters, k, min_mult, with_positions, n_windows, n_distinct, n_kmers, n_occ, n_rounds, n_sorts, n_sort_passes) and its device
+        milliseconds per phase."""
+        s = _lib.MonokmersShape()
+        self._check(self._lib.cf_monokmers_info(self._ctx, C.byref(s)), "cf_monokmers_info")
+        d = {n: int(getattr(s, n)) for n, _ in s._fields_ if n != "phase_ms"}
+        d["phase_ms"] = dict(zip(("copies", "sorts", "glue", "total"), (float(x) for x in s.phase_ms)))
+        return d
+
     # ------------------------------------------------------------------ self tests of primitives
     def selftest_sort(self, keys, bits=64):
         keys = np.ascontiguousarray(keys, np.uint64)

@@ -455,6 +455,52 @@ int cf_monodec_run(cf_ctx* ctx, const uint8_t* monomers, const int64_t* mono_off
 int cf_monodec_get(cf_ctx* ctx, int64_t* ptr, cf_monodec_inst* inst, int64_t cap, int64_t* n_out);
 int cf_monodec_info(cf_ctx* ctx, cf_monodec_shape* out);
 
+/* Exact counts of the gap-free windows of k letters over a set of monostrings (cf_monokmers.hip): what the reference's second
+ * pipeline computes in a Python loop over string slices (scripts/debruijn_graph.py get_frequent_kmers and read_kmer_locations,
+ * scripts/mono_error_correction.py correct_gaps).  The rule below is the specification (tests/monokmercheck.py
+ * restates it).
+ * cf_monokmers_run: strings s_0 .. s_{S-1}, S = n_strings >= 0, s_j = bytes[off[j], off[j + 1]) (any bytes; offsets >= 0 and
+ * non-decreasing, so a string may be empty), N = off[S] - off[0] < 2^31 letters in all; k >= 1; min_mult >= 1; gap: the gap byte
+ * (0 .. 255; the pipeline's is '?').
+ *   Window (j, i) is VALID iff i + k <= len(s_j) and none of the bytes s_j[i .. i + k) is the gap byte.  No window reaches from
+ *   one string into the next.  Two valid windows are the same k-mer iff their k bytes are equal (bytes are compared, nothing is
+ *   hashed).  The result is every k-mer with at least min_mult valid windows, IN THE ORDER OF FIRST OCCURRENCE — the k-mer whose
+ *   smallest (j, i) is smallest first, which is the order of the reference's dict and so of its graph's node numbers —, per k-mer
+ *   its first (j, i), its count and pos = the first window's offset in the concatenation (bytes[off[0] + pos ..] are its letters).
+ *   with_positions != 0: also every valid window of every reported k-mer, as a CSR over the k-mers in ascending (j, i).
+ *   *n_kmers (may be NULL): the number of reported k-mers; *ms (may be NULL): device milliseconds of the call, copies included.
+ * The device works by prefix doubling on equality ranks: R_1 = the byte, R_2m[p] = the dense id of (R_m[p], R_m[p + m]) over the
+ * valid windows of length 2m, and with a the largest power of two not above k one overlapping combine (R_a[p], R_a[p + k - a]);
+ * a round is a key pass, the stable record sort of cf_prims.hip with the position as payload, head flags, a scan and a scatter of
+ * the ids.  Validity is a per-position distance to the next gap or string end, computed once.  The call keeps nothing on the device.
+ * Nothing is added to cf_times or cf_stats.  Errors (-22: k < 1, min_mult < 1, N >= 2^31, offsets that do not ascend or are
+ * negative, null pointers, a gap outside 0 .. 255, n_strings outside 0 .. 2^31 - 1) are raised before anything is allocated and
+ * leave the context and the results of the call before as they were.
+ * cf_monokmers_get: the last run's k-mers (cap >= their number) and, when it kept positions, ptr[n + 1] and the occurrences
+ * (occ_cap >= their number).  Every pointer may be NULL; *n_out and *n_occ_out (-1: no positions kept) give the sizes.
+ * cf_monokmers_info: the shape constants the tests straddle and the last run's figures: n_windows = the valid windows of length k,
+ * n_distinct = the distinct k-mers among them (before min_mult), n_rounds = the combining rounds (0 for k = 1), n_sorts = the
+ * record sorts (the rounds', the grouping of the bytes for k = 1, the sort of the classes by first position), n_sort_passes = their
+ * 8-bit passes.  phase_ms: copies to and from the device, the sorts, everything else, the whole call; by HIP events. */
+typedef struct cf_monokmer {
+    int32_t s, i, count, pos;
+} cf_monokmer;
+typedef struct cf_monokmer_occ {
+    int32_t s, i;
+} cf_monokmer_occ;
+typedef struct cf_monokmers_shape {
+    int64_t sort_tile, scan_tile;         /* records per tile of the record sort; values per tile of the scan           */
+    int64_t block, launch_cap;            /* threads per workgroup of the streaming passes; their workgroups at most    */
+    int64_t n_strings, n_letters, k, min_mult, with_positions; /* of the last run                                       */
+    int64_t n_windows, n_distinct, n_kmers, n_occ, n_rounds, n_sorts, n_sort_passes;
+    float phase_ms[4];
+} cf_monokmers_shape;
+int cf_monokmers_run(cf_ctx* ctx, const uint8_t* bytes, const int64_t* off, int64_t n_strings, int64_t k, int64_t min_mult, int32_t gap,
+                     int32_t with_positions, int64_t* n_kmers, float* ms);
+int cf_monokmers_get(cf_ctx* ctx, cf_monokmer* kmers, int64_t cap, int64_t* n_out, int64_t* occ_ptr, cf_monokmer_occ* occ, int64_t occ_cap,
+                     int64_t* n_occ_out);
+int cf_monokmers_info(cf_ctx* ctx, cf_monokmers_shape* out);
+
 int cf_get_stats(cf_ctx* ctx, cf_stats* out);
 int cf_get_times(cf_ctx* ctx, cf_times* out);
 
