@@ -205,7 +205,7 @@ cf_order_keys_kernel(const uint32_t* __restrict__ pcnt, const uint32_t* __restri
                      unsigned long long* __restrict__ keys, unsigned long long* __restrict__ n_out,
                      int hb, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post, const unsigned long long* __restrict__ not_a_set, int by_second) {
     // by_second (groups): the hb bits are the low bits of the k-mer's SECOND posting unit instead of a hash of the list — the k-mers of
-    // one first unit whose lists go on alike stand together, and the greedy cut of cf_group_mark_kernel finds small unions (in hash order the
+    // one first unit whose lists go on alike stand together, and the greedy cut of cf_group_walk_kernel finds small unions (in hash order the
     // unions of the bench's reads sweep 0.70 of the classes' entries, in this order 0.44: tools/dist_groups_cpu.py --order)
     // hb > 0 (classes of first k-mers): hb bits of a hash of the k-mer's posting list stand between the first unit and the
     // rank, so that the sort puts k-mers with equal lists next to each other (they share their first unit).  The hash only brings candidates
@@ -312,32 +312,142 @@ cf_class_first_kernel(const uint32_t* __restrict__ flags, const int64_t* __restr
 #define DIST_GROUP_MAX 32u
 // One WAVE walks a run of equal first units (the runs that start among its 64 positions; a thread per run with the union in a private array
 // took 100 ms at 50 000 reads: every step of its merges was a round trip to scratch memory).  The union lives in the lanes — lane i holds
-// its i-th posting, in the order they joined — and a member's list in the lanes too: membership is nu broadcasts and compares, and the
-// member's mask falls out of the same loop in scalar registers.  Per position of the sorted keys the kernel writes the start flag, the
-// member's mask over its group's union, and which of its own postings were NEW to the union (cf_group_fill_kernel strings those together:
-// the union's order is the order of joining, not ascending — the place of a posting in the union only names its bit).
+// its i-th posting, in the order they joined — and a member's list in the lanes too.  Per position of the sorted keys the kernel writes the
+// start flag, the member's mask over its group's union, and which of its own postings were NEW to the union (cf_group_fill_kernel strings
+// those together: the union's order is the order of joining, not ascending — the place of a posting in the union only names its bit).
+// the lists of a WINDOW of 64 positions are fetched together (lane l walks the list of position wb + l, every load of the
+// window in flight at once) and parked in the wave's LDS rows; the greedy cut, sequential by definition, then costs a member one LDS read
+// (issued one member ahead) and a broadcast per posting of its list — no trip to memory.  The wave that owns a window (the chunk's own
+// wave: every position belongs to exactly one) also sums, on the lists it has just fetched, what cf_dist_edges reports as n_emissions: every
+// first k-mer's OWN partner entries and its self pairs (postings (u, v) of one k-mer in one read with min_d <= v - u <= max_d: entries that are
+// the first k-mer itself) — with groups a pass sweeps the union's entries, and n_emissions stays what it was.  The lists are ascending
+// (postings by sort), so the postings of one read stand next to each other: a lane looks for pairs only where two neighbours share a read.
 __device__ __forceinline__ unsigned long long cf_readlane64(unsigned long long v, int l) {
     return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), l) << 32) | (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l);
 }
+#define DIST_WALK_ROW 33u      // words of a position's LDS row: DIST_GROUP_MAX postings and one of padding (lane l writes row l: 33 l + k takes every bank once)
+#define DIST_WALK_LDS(block) ((size_t)((block) / 64) * 64 * DIST_WALK_ROW * 4)
 __global__ void __launch_bounds__(256)
-cf_group_mark_kernel(const unsigned long long* __restrict__ keys, int64_t n, int kb, int ab, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
-                     const unsigned long long* __restrict__ not_a_set, uint32_t cap, uint32_t* __restrict__ flags, uint32_t* __restrict__ member_mask, uint32_t* __restrict__ new_mask) {
+cf_group_walk_kernel(const unsigned long long* __restrict__ keys, int64_t n, int kb, int ab, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
+                     const unsigned long long* __restrict__ not_a_set, uint32_t cap, const cf_dist_rec* __restrict__ urange, const int32_t* __restrict__ rend, int32_t min_d, int32_t max_d,
+                     uint32_t* __restrict__ flags, uint32_t* __restrict__ member_mask, uint32_t* __restrict__ new_mask,
+                     unsigned long long* __restrict__ entries_out, unsigned long long* __restrict__ self_out) {
     // kb: the key's bits below the first unit (rank and order bits); ab: bits of the rank
     const uint32_t lane = threadIdx.x & 63u;
+    uint32_t* const rows = (uint32_t*)cf_lds + (size_t)(threadIdx.x >> 6) * (64u * DIST_WALK_ROW);      // the wave's 64 rows
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const unsigned long long rank_mask = (1ull << ab) - 1ull;
     const bool off = *not_a_set != 0ull;
+    if (cap > DIST_GROUP_MAX) cap = DIST_GROUP_MAX;
+    unsigned long long ent = 0, self = 0;
     for (int64_t c0 = wave * 64; c0 < n; c0 += n_waves * 64) {      // (wave-uniform)
-        // a window of 64 positions: first unit, start and length of the list (lane l: position wb + l)
+        // a window of 64 positions: first unit, start and length of the list (lane l: position wb + l), the lists of up to DIST_GROUP_MAX
+        // postings in the LDS rows, and what the walk found for the position (written when the wave leaves the window)
         int64_t wb = c0, w_p0 = 0;
         unsigned long long w_fu = ~0ull;
-        uint32_t w_len = 0;
-        auto load_window = [&](int64_t b) {
+        uint32_t w_len = 0, o_mask = 0, o_new = 0;
+        bool o_start = false, o_done = false;
+        auto flush = [&]() {
+            if (o_done) { const int64_t i = wb + (int64_t)lane; flags[i] = o_start ? 1u : 0u; member_mask[i] = o_mask; new_mask[i] = o_new; }
+            o_done = false;
+        };
+        // all: every list of the window (else: the window a run goes on in — the lists of `fu` only).  own: the chunk of this wave — the emissions of its positions too.
+        auto load_window = [&](int64_t b, bool all, bool own, unsigned long long fu) {
+            flush();
             wb = b; w_fu = ~0ull; w_p0 = 0; w_len = 0;
             const int64_t i = b + (int64_t)lane;
-            if (i < n) { const unsigned long long k = keys[i]; const uint32_t x = (uint32_t)(k & rank_mask); w_fu = k >> kb; w_p0 = post_ptr[x]; w_len = (uint32_t)(post_ptr[x + 1] - w_p0); }
+            if (i < n) {
+                const unsigned long long k = keys[i];
+                w_fu = k >> kb;
+                if (all || w_fu == fu) { const uint32_t x = (uint32_t)(k & rank_mask); w_p0 = post_ptr[x]; w_len = (uint32_t)(post_ptr[x + 1] - w_p0); }
+            }
+            const uint32_t len_l = w_len <= DIST_GROUP_MAX ? w_len : 0u;      // (a longer list is a group of its own: the walk never reads it)
+            // A TEAM of 8 lanes reads one list, 8 postings to a load (a lane per list, each walking its own, fetched a cache line per lane and
+            // load: 6.1 ms for the kernel, as much as the serial walk it replaced): eight rounds of eight lists, the first 8 postings of all 64 lists
+            // in flight together, the rest of the longer lists behind.  A lane without a posting reads post[0] or its list's first word: in bounds.
+            const uint32_t tl = lane & 7u, team = lane >> 3;
+            unsigned long long adj_m = 0;      // the positions of the window with two neighbours of the list in one read
+            int64_t t_p0[8];
+            uint32_t t_len[8];
+            int32_t t_u[8], t_r[8];
+            uint32_t t_el[8], t_ig[8];
+            __builtin_amdgcn_wave_barrier();      // (the rows are read by every lane: nobody is still reading the window before)
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const int m = r * 8 + (int)team;
+                t_p0[r] = (int64_t)__shfl((long long)w_p0, m);
+                t_len[r] = __shfl(len_l, m);
+                t_u[r] = post[t_p0[r] + (int64_t)(tl < t_len[r] ? tl : 0u)];
+            }
+            if (own) {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) { t_el[r] = urange[t_u[r]].len; t_ig[r] = urange[t_u[r]].ig; }
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const uint32_t m = (uint32_t)r * 8u + team;
+                const bool on = tl < t_len[r];
+                if (on) rows[m * DIST_WALK_ROW + tl] = (uint32_t)t_u[r];
+                t_r[r] = -1;
+                if (own) {
+                    if (on) { ent += t_el[r]; t_r[r] = t_u[r] - (int32_t)t_ig[r]; }      // first unit of the posting's read
+                    const int32_t prev = __shfl_up(t_r[r], 1u, 8);
+                    if (on && tl > 0u && t_r[r] == prev) adj_m |= 1ull << m;
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {      // (lists of more than 8 postings: one in five on the bench's reads)
+                const uint32_t m = (uint32_t)r * 8u + team;
+                int32_t r_carry = own ? __shfl(t_r[r], 7, 8) : -1;
+                for (uint32_t k0 = 8u; cf_ballot(k0 < t_len[r]) != 0ull; k0 += 8u) {      // (wave-uniform trip count)
+                    const uint32_t k = k0 + tl;
+                    const bool on = k < t_len[r];
+                    const int32_t u = post[t_p0[r] + (int64_t)(on ? k : 0u)];
+                    if (on) rows[m * DIST_WALK_ROW + k] = (uint32_t)u;
+                    if (own) {
+                        int32_t rr = -1;
+                        if (on) { ent += urange[u].len; rr = u - (int32_t)urange[u].ig; }
+                        int32_t prev = __shfl_up(rr, 1u, 8);
+                        if (tl == 0u) prev = r_carry;
+                        if (on && rr == prev) adj_m |= 1ull << m;
+                        r_carry = __shfl(rr, 7, 8);
+                    }
+                }
+            }
+            bool adj = false;
+            if (own && cf_ballot(adj_m != 0ull) != 0ull) {      // (rare: the bits of the teams, brought together)
+                for (int d = 32; d >= 1; d >>= 1) adj_m |= (unsigned long long)__shfl_xor((long long)adj_m, d);
+                adj = (adj_m >> lane) & 1ull;
+            }
+            __builtin_amdgcn_wave_barrier();
+            if (!own) return;
+            if (adj)      // (rare: the k-mer twice in one read)
+                for (uint32_t p = 0; p + 1u < len_l; ++p) {
+                    const int32_t up = (int32_t)rows[lane * DIST_WALK_ROW + p], re = rend[up];
+                    for (uint32_t q = p + 1u; q < len_l; ++q) {
+                        const int32_t v = (int32_t)rows[lane * DIST_WALK_ROW + q];
+                        if (v >= re || v - up > max_d) break;
+                        self += (unsigned long long)(v - up >= min_d);
+                    }
+                }
+            // the lists that do not fit a row: the wave takes them 64 postings at a time
+            unsigned long long lm = cf_ballot(w_len > DIST_GROUP_MAX);
+            while (lm) {
+                const int sl = __ffsll((long long)lm) - 1;
+                lm &= lm - 1ull;
+                const int64_t p0 = (int64_t)cf_readlane64((unsigned long long)w_p0, sl), p1 = p0 + (int64_t)(uint32_t)__builtin_amdgcn_readlane((int)w_len, sl);
+                for (int64_t p = p0 + (int64_t)lane; p < p1; p += 64) {
+                    const int32_t up = post[p], re = rend[up];
+                    ent += urange[up].len;
+                    for (int64_t q = p + 1; q < p1; ++q) {
+                        const int32_t v = post[q];
+                        if (v >= re || v - up > max_d) break;
+                        self += (unsigned long long)(v - up >= min_d);
+                    }
+                }
+            }
         };
-        load_window(c0);
+        load_window(c0, true, true, 0ull);
         const int64_t i_me = c0 + (int64_t)lane;
         if (off) { if (i_me < n) { flags[i_me] = 1u; member_mask[i_me] = 0u; new_mask[i_me] = 0u; } continue; }
         bool head = i_me < n;
@@ -346,73 +456,106 @@ cf_group_mark_kernel(const unsigned long long* __restrict__ keys, int64_t n, int
         while (hm) {      // the runs that start in this chunk, one after the other
             const int s = __ffsll((long long)hm) - 1;
             hm &= hm - 1ull;
-            if (wb != c0) load_window(c0);      // (the run before went on beyond the chunk)
+            if (wb != c0) load_window(c0, true, false, 0ull);      // (a run that went on beyond the chunk is the chunk's last: not taken)
             const unsigned long long fu = cf_readlane64(w_fu, s);
-            uint32_t un = 0xFFFFFFFFu, nu = 0, members = 0;
+            uint32_t un = 0xFFFFFFFEu, nu = 0, members = 0;      // (no posting is 0xFFFFFFFE or 0xFFFFFFFF: unit numbers have 31 bits)
+            uint32_t L_next = rows[(uint32_t)s * DIST_WALK_ROW + (lane & 31u)];      // the list of the member to come, fetched while this one is tested
             for (int64_t j = c0 + s; j < n; ++j) {
-                if (j - wb == 64) load_window(j);
+                if (j - wb == 64) { load_window(j, false, false, fu); L_next = rows[lane & 31u]; }
                 const int sl = (int)(j - wb);
                 if (cf_readlane64(w_fu, sl) != fu) break;
-                const int64_t p0 = (int64_t)cf_readlane64((unsigned long long)w_p0, sl);
                 const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)w_len, sl);
-                if (len > cap) {      // a group of its own (it counts); the next k-mer starts one too
-                    if (lane == 0u) { flags[j] = 1u; member_mask[j] = 0u; new_mask[j] = 0u; }
-                    nu = 0; members = 0;
-                    continue;
+                const uint32_t L = lane < len ? L_next : 0xFFFFFFFFu;      // (len <= cap below: the list's lanes)
+                L_next = rows[(uint32_t)min(sl + 1, 63) * DIST_WALK_ROW + (lane & 31u)];
+                uint32_t mask = 0, fresh = 0;
+                bool start = true;
+                if (len > cap) { nu = 0; members = 0; }      // a group of its own (it counts); the next k-mer starts one too
+                else {
+                    uint32_t found = 0;      // the postings of the list that the union has
+                    // eight postings to a trip, without a branch: the broadcasts and compares of a trip do not wait for each other.  A posting is in
+                    // the union once at most, and the lane that holds it there IS its bit: the ballot goes into the mask as it is.  (The lanes of L
+                    // beyond the list hold 0xFFFFFFFF and the lanes of the union beyond nu 0xFFFFFFFE: they never match.)
+                    if (nu)
+                        for (uint32_t t0 = 0; t0 < len; t0 += 8u) {
+#pragma unroll
+                            for (uint32_t q = 0; q < 8u; ++q) {
+                                const unsigned long long h = cf_ballot(un == (uint32_t)__builtin_amdgcn_readlane((int)L, (int)(t0 + q)));
+                                mask |= (uint32_t)h;
+                                found |= (uint32_t)(h != 0ull) << (t0 + q);
+                            }
+                        }
+                    const uint32_t mine = (uint32_t)((1ull << len) - 1ull);
+                    uint32_t nm = mine & ~found;
+                    start = members == 0u || members == DIST_CLASS_CAP || nu + (uint32_t)__popc(nm) > cap;
+                    if (start) { nu = 0; members = 0; mask = 0; nm = mine; un = 0xFFFFFFFEu; }
+                    fresh = nm;
+                    while (nm) {
+                        const int t = __ffs((int)nm) - 1;
+                        nm &= nm - 1u;
+                        const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)L, t);
+                        if (lane == nu) un = x;
+                        mask |= 1u << nu;
+                        ++nu;
+                    }
+                    ++members;
                 }
-                const uint32_t L = lane < len ? (uint32_t)post[p0 + lane] : 0xFFFFFFFFu;
-                uint32_t mask = 0;
-                unsigned long long found = 0;
-                for (uint32_t i = 0; i < nu; ++i) {
-                    const unsigned long long h = cf_ballot(L == (uint32_t)__builtin_amdgcn_readlane((int)un, (int)i));
-                    if (h) { mask |= 1u << i; found |= h; }
-                }
-                const unsigned long long mine = cf_ballot(lane < len);
-                unsigned long long nm = mine & ~found;
-                const bool start = members == 0u || members == DIST_CLASS_CAP || nu + (uint32_t)__popcll(nm) > cap;
-                if (start) { nu = 0; members = 0; mask = 0; nm = mine; }
-                const uint32_t fresh = (uint32_t)nm;      // (len <= 32: the list's lanes)
-                while (nm) {
-                    const int t = __ffsll((long long)nm) - 1;
-                    nm &= nm - 1ull;
-                    const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)L, t);
-                    if (lane == nu) un = x;
-                    mask |= 1u << nu;
-                    ++nu;
-                }
-                ++members;
-                if (lane == 0u) { if (start) flags[j] = 1u; member_mask[j] = mask; new_mask[j] = fresh; }
+                if (lane == (uint32_t)sl) { o_start = start; o_mask = mask; o_new = fresh; o_done = true; }
             }
         }
+        flush();
+    }
+    for (int d = 32; d >= 1; d >>= 1) { ent += __shfl_down(ent, (unsigned)d); self += __shfl_down(self, (unsigned)d); }
+    if (lane == 0u) {
+        if (ent) atomicAdd(entries_out, ent);
+        if (self) atomicAdd(self_out, self);
     }
 }
 // Per group g (the k-mers order[gfirst[g] .. gfirst[g + 1])): the union of the members' lists at upost[32 g ..] — every member's new postings, in
 // the order of joining — and its size in ulen[g] (bit 31: a counting group — no union, the sweep takes the k-mer's own list).
+// A TEAM of DIST_FILL_TEAM lanes per group (a thread per group walked members and bits one load after the other): lane t takes
+// member t of a batch, the counts of new postings are prefix-summed across the team, and every member's lane writes its own.  (A group has
+// 3.6 members on the bench's reads: teams of 32 left the wave with two chains of loads in flight, 1.68 ms against the thread per group's 1.42.)
+#define DIST_FILL_TEAM 8
 __global__ void __launch_bounds__(256)
 cf_group_fill_kernel(const int32_t* __restrict__ order, const uint32_t* __restrict__ gfirst, int64_t n_groups, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
                      const unsigned long long* __restrict__ not_a_set, uint32_t cap, const uint32_t* __restrict__ new_mask, const uint32_t* __restrict__ member_mask,
                      int32_t* __restrict__ upost, uint32_t* __restrict__ ulen, unsigned long long* __restrict__ diag, unsigned long long* __restrict__ err) {
     const bool off = *not_a_set != 0ull;
     unsigned long long dg_u = 0, dg_c = 0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < n_groups; g += stride) {
-        const uint32_t f = gfirst[g], e = gfirst[g + 1];
+    constexpr uint32_t T = DIST_FILL_TEAM;
+    const uint32_t tl = threadIdx.x & (T - 1u);
+    const int64_t team = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / T, n_teams = ((int64_t)gridDim.x * blockDim.x) / T;
+    for (int64_t g0 = 0; g0 < n_groups; g0 += n_teams) {      // (uniform trip count: shuffles inside)
+        const int64_t g = g0 + team;
+        const bool on = g < n_groups;
+        uint32_t f = 0, e = 0;
+        if (on) { f = gfirst[g]; e = gfirst[g + 1]; }
         bool counting = off;
-        if (e - f == 1u) { const int32_t x = order[f]; counting = counting || (uint32_t)(post_ptr[x + 1] - post_ptr[x]) > cap; }
+        if (on && e - f == 1u) { const int32_t x = order[f]; counting = counting || (uint32_t)(post_ptr[x + 1] - post_ptr[x]) > cap; }
+        const uint32_t n_mem = (on && !counting) ? e - f : 0u;
+        uint32_t n_max = n_mem;      // (the wave's teams loop together)
+        for (uint32_t d = T; d < 64u; d <<= 1) n_max = max(n_max, __shfl_xor(n_max, (int)d));
         uint32_t k = 0;
-        if (!counting)
-            for (uint32_t j = f; j < e; ++j) {
-                uint32_t nm = new_mask[j];
-                if (!nm) continue;
+        for (uint32_t b = 0; b < n_max; b += T) {
+            const uint32_t j = f + b + tl;
+            uint32_t nm = b + tl < n_mem ? new_mask[j] : 0u;
+            const uint32_t c = (uint32_t)__popc(nm);
+            uint32_t incl = c;
+            for (uint32_t d = 1; d < T; d <<= 1) { const uint32_t t = __shfl_up(incl, d, (int)T); if (tl >= d) incl += t; }
+            uint32_t at = k + incl - c;
+            if (nm) {
                 const int64_t p0 = post_ptr[order[j]];
                 while (nm) {
                     const int t = __ffs((int)nm) - 1;
                     nm &= nm - 1u;
-                    if (k < DIST_GROUP_MAX) upost[(size_t)DIST_GROUP_MAX * (size_t)g + k] = post[p0 + t];
-                    ++k;
+                    if (at < DIST_GROUP_MAX) upost[(size_t)DIST_GROUP_MAX * (size_t)g + at] = post[p0 + t];
+                    ++at;
                 }
             }
-        if (k > DIST_GROUP_MAX) { atomicOr(err, 4ull); k = DIST_GROUP_MAX; }      // (cf_group_mark_kernel cut the run so that this cannot be: the launch fails)
+            k += __shfl(incl, (int)T - 1, (int)T);
+        }
+        if (!on || tl != 0u) continue;      // (no shuffle below)
+        if (k > DIST_GROUP_MAX) { atomicOr(err, 4ull); k = DIST_GROUP_MAX; }      // (cf_group_walk_kernel cut the run so that this cannot be: the launch fails)
         ulen[g] = counting ? 0x80000000u : k;
         dg_u += k;
 #if defined(CF_DIST_DIAG_COUNT)      /* the group's classes: its distinct member masks (equal lists in one group have equal masks) */
@@ -429,38 +572,6 @@ cf_group_fill_kernel(const int32_t* __restrict__ order, const uint32_t* __restri
 #else
     (void)diag; (void)dg_u; (void)dg_c; (void)member_mask;
 #endif
-}
-// Summed over the launch's first k-mers (one thread each): their OWN partner entries and self pairs (postings (u, v) of one k-mer in one read
-// with min_d <= v - u <= max_d: entries that are the first k-mer itself) — with groups a pass sweeps the union's entries, and n_emissions
-// stays what it was.  The lists are ascending (postings by sort), so the postings of one read stand next to each other.
-__global__ void __launch_bounds__(256)
-cf_member_emissions_kernel(const int32_t* __restrict__ order, int64_t n_order, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
-                           const cf_dist_rec* __restrict__ urange, const int32_t* __restrict__ rend, int32_t min_d, int32_t max_d,
-                           unsigned long long* __restrict__ entries_out, unsigned long long* __restrict__ self_out) {
-    unsigned long long ent = 0, self = 0;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_order; i += stride) {
-        const int32_t x = order[i];
-        const int64_t p0 = post_ptr[x], p1 = post_ptr[x + 1];
-        int32_t u = p0 < p1 ? post[p0] : 0;
-        for (int64_t p = p0; p < p1; ++p) {
-            ent += urange[u].len;
-            const int32_t u_next = p + 1 < p1 ? post[p + 1] : 0x7FFFFFFF;
-            if (u_next < rend[u]) {      // (rare: the k-mer twice in one read)
-                for (int64_t q = p + 1; q < p1; ++q) {
-                    const int32_t v = post[q];
-                    if (v >= rend[u] || v - u > max_d) break;
-                    self += (unsigned long long)(v - u >= min_d);
-                }
-            }
-            u = u_next;
-        }
-    }
-    for (int d = 32; d >= 1; d >>= 1) { ent += __shfl_down(ent, (unsigned)d); self += __shfl_down(self, (unsigned)d); }
-    if ((threadIdx.x & 63) == 0) {
-        if (ent) atomicAdd(entries_out, ent);
-        if (self) atomicAdd(self_out, self);
-    }
 }
 
 // One item = up to DIST_ITEM consecutive partner entries of one posting: what one wave takes per step.
@@ -1471,7 +1582,7 @@ __device__ __forceinline__ uint32_t cf_dist_insert(const Tab& T, uint32_t n_buck
 // read with min_d <= v - u <= max_d (the reference skips a == b, distance_based_kmer_recruitment.py:118; the sweeps count such an
 // entry like any other and the host subtracts this sum).
 // GRP (groups): the list of head i is the UNION of its group, upost[32 i .. 32 i + ulen[i]) — or, ulen[i] bit 31, the k-mer's own
-// list (a counting group of one); the self pairs are not counted here (cf_member_emissions_kernel counts every member's own)
+// list (a counting group of one); the self pairs are not counted here (cf_group_walk_kernel counts every member's own)
 template <bool GRP>
 __global__ void __launch_bounds__(256)
 cf_items_count_kernel(const int32_t* __restrict__ order, int64_t n_order, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
@@ -2620,7 +2731,7 @@ __global__ void __launch_bounds__(CF_DIST_LB_THREADS, CF_DIST_LB_BLOCKS) cf_dist
         if (spilled && t == 0) ++acc_spill;
     }
     if (t == 0) {
-        if (acc_E && !Tab::kMaskTab) atomicAdd(&A.counters[1], acc_E);      // (groups: the members' own partner entries were summed by cf_member_emissions_kernel; what a pass sweeps is the union's)
+        if (acc_E && !Tab::kMaskTab) atomicAdd(&A.counters[1], acc_E);      // (groups: the members' own partner entries were summed by cf_group_walk_kernel; what a pass sweeps is the union's)
         if (acc_spill) atomicAdd(&A.counters[2], acc_spill);
         if (acc_pass) atomicAdd(&A.counters[5], acc_pass);
         if (acc_edges) atomicAdd(&A.counters[6], acc_edges);
@@ -2978,9 +3089,10 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         CF_TRY(tmp.get(&d_cfirst, (size_t)n_order + 1, "class starts"));
         CF_HIP(hipMemsetAsync(d_cflag, 0, (size_t)(n_order + 1) * 4, ctx->stream));
         if (groups) { CF_TRY(tmp.get(&d_mmask, (size_t)n_order + 1, "member masks")); CF_TRY(tmp.get(&d_newm, (size_t)n_order + 1, "members' new postings")); }
-        if (groups)
-            hipLaunchKernelGGL(cf_group_mark_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const unsigned long long*)d_okeys, n_order, ab + hb, ab,
-                               (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), (uint32_t)ctx->dist_group_cap, d_cflag, d_mmask, d_newm);
+        if (groups)      // the cut of the runs into groups, and the members' own emissions
+            hipLaunchKernelGGL(cf_group_walk_kernel, dim3(g_cls), dim3(256), DIST_WALK_LDS(256), ctx->stream, (const unsigned long long*)d_okeys, n_order, ab + hb, ab,
+                               (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), (uint32_t)ctx->dist_group_cap,
+                               (const cf_dist_rec*)d_urange, (const int32_t*)d_rend, min_d_eff, max_d, d_cflag, d_mmask, d_newm, d_cnt + 1, d_cnt + 3);
         else
         hipLaunchKernelGGL(cf_class_mark_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const unsigned long long*)d_okeys, n_order, ab,
                            (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), d_cflag);
@@ -2989,11 +3101,9 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         if (groups) {      // the unions, and the members' own emissions
             CF_TRY(tmp.get(&d_upost, (size_t)n_heads * DIST_GROUP_MAX + 1, "group unions"));
             CF_TRY(tmp.get(&d_ulen, (size_t)n_heads + 1, "group union sizes"));
-            hipLaunchKernelGGL(cf_group_fill_kernel, dim3((unsigned)cf_grid_for(n_heads, 256, max_blocks)), dim3(256), 0, ctx->stream, (const int32_t*)d_order, (const uint32_t*)d_cfirst, n_heads,
+            hipLaunchKernelGGL(cf_group_fill_kernel, dim3((unsigned)cf_grid_for(n_heads * DIST_FILL_TEAM, 256, max_blocks)), dim3(256), 0, ctx->stream, (const int32_t*)d_order, (const uint32_t*)d_cfirst, n_heads,
                                (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), (uint32_t)ctx->dist_group_cap, (const uint32_t*)d_newm, (const uint32_t*)d_mmask,
                                d_upost, d_ulen, d_cnt + 148, d_cnt + 4);
-            hipLaunchKernelGGL(cf_member_emissions_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const int32_t*)d_order, n_order, (const int64_t*)d_post_ptr, (const int32_t*)d_post,
-                               (const cf_dist_rec*)d_urange, (const int32_t*)d_rend, min_d_eff, max_d, d_cnt + 1, d_cnt + 3);
         }
         CF_KERNEL_CHECK("the class kernels");
     }
