@@ -171,6 +171,10 @@ PROTOTYPES = {
     "cf_allreduce_unique": (C.c_int, [_P, _PI64]),
     "cf_selftest_sort": (C.c_int, [_P, _P, _I64, _I32, _P]),
     "cf_selftest_scan": (C.c_int, [_P, _P, _I64, _P]),
+    "cf_selftest_scan_inplace": (C.c_int, [_P, _P, _I64, _P]),
+    "cf_selftest_scan_u32": (C.c_int, [_P, _P, _I64, _P]),
+    "cf_selftest_sort_rec16": (C.c_int, [_P, _P, _I64, _P, _P, _I32, _P]),
+    "cf_selftest_digit_offsets": (C.c_int, [_P, _P, _I32, _I32, _P, _P]),
     "cf_selftest_argmax": (C.c_int, [_P, _P, _I64, _P]),
     "cf_selftest_owner_buckets": (C.c_int, [_P, _I32, _P, _P, _P, _I64, _PI64]),
     "cf_selftest_merge_records": (C.c_int, [_P, _P, _P, _I64]),

@@ -665,4 +665,79 @@ int cf_selftest_scan(cf_ctx* ctx, const int64_t* in, int64_t n, int64_t* out) {
     return 0;
 }
 
+// the same with one device buffer as input and output, as cf_count.hip and cf_exchange.hip call the scan
+int cf_selftest_scan_inplace(cf_ctx* ctx, const int64_t* in, int64_t n, int64_t* out) {
+    if (!ctx) return -22;
+    CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
+    int64_t* a = nullptr;
+    CF_TRY(tmp.get(&a, (size_t)n + 1, "selftest in and out"));
+    int64_t total = 0;
+    if (n && hipMemcpy(a, in, (size_t)n * 8, hipMemcpyHostToDevice) != hipSuccess) return cf_fail(ctx, -5, "selftest copy");
+    CF_TRY(cf_scan_exclusive_i64(ctx, a, a, n, &total));
+    if (n && hipMemcpy(out, a, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return cf_fail(ctx, -5, "selftest copy back");
+    out[n] = total;
+    return 0;
+}
+
+int cf_selftest_scan_u32(cf_ctx* ctx, const uint32_t* in, int64_t n, int64_t* out) {
+    if (!ctx) return -22;
+    CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
+    uint32_t* a = nullptr;
+    int64_t* b = nullptr;
+    CF_TRY(tmp.get(&a, (size_t)n + 1, "selftest in"));
+    CF_TRY(tmp.get(&b, (size_t)n + 1, "selftest out"));
+    int64_t total = 0;
+    if (n && hipMemcpy(a, in, (size_t)n * 4, hipMemcpyHostToDevice) != hipSuccess) return cf_fail(ctx, -5, "selftest copy");
+    CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, a, b, n, &total));
+    if (n && hipMemcpy(out, b, (size_t)n * 8, hipMemcpyDeviceToHost) != hipSuccess) return cf_fail(ctx, -5, "selftest copy back");
+    out[n] = total;
+    return 0;
+}
+
+int cf_selftest_sort_rec16(cf_ctx* ctx, const uint32_t* recs, int64_t n, const int32_t* words, const int32_t* bits, int32_t n_fields, uint32_t* out) {
+    if (!ctx) return -22;
+    if (n < 0 || n_fields < 0 || n_fields > 16 || (n_fields && (!words || !bits))) return cf_fail(ctx, -22, "cf_selftest_sort_rec16: bad field list");
+    int w[16], b[16];
+    for (int f = 0; f < n_fields; ++f) {
+        if (words[f] < 0 || words[f] > 3 || bits[f] < 0 || bits[f] > 32) return cf_fail(ctx, -22, "cf_selftest_sort_rec16: a field is a word 0 .. 3 and 0 .. 32 bits");
+        w[f] = words[f];
+        b[f] = bits[f];
+    }
+    CF_HIP(hipSetDevice(ctx->device));
+    cf_scratch tmp(ctx);
+    uint32_t *a = nullptr, *t = nullptr;
+    CF_TRY(tmp.get(&a, (size_t)n * 4 + 4, "selftest records"));
+    CF_TRY(tmp.get(&t, (size_t)n * 4 + 4, "selftest tmp"));
+    if (n && hipMemcpy(a, recs, (size_t)n * 16, hipMemcpyHostToDevice) != hipSuccess) return cf_fail(ctx, -5, "selftest copy");
+    CF_TRY(cf_radix_sort_rec16(ctx, a, t, n, w, b, n_fields));
+    if (n && hipMemcpy(out, a, (size_t)n * 16, hipMemcpyDeviceToHost) != hipSuccess) return cf_fail(ctx, -5, "selftest copy back");
+    return 0;
+}
+
+int cf_selftest_digit_offsets(cf_ctx* ctx, const uint32_t* hist, int32_t n_tiles, int32_t D, int64_t* offs, int64_t* total) {
+    if (!ctx) return -22;
+    if (n_tiles < 0) return cf_fail(ctx, -22, "cf_selftest_digit_offsets: negative tile count");
+    CF_HIP(hipSetDevice(ctx->device));
+    const size_t dd = (size_t)std::max(D, 1), nh = (size_t)n_tiles * dd, nc = (size_t)cf_tile_digit_chunks(n_tiles) * dd;
+    cf_scratch tmp(ctx);
+    uint32_t *d_hist = nullptr, *d_part = nullptr;
+    int64_t *d_offs = nullptr, *d_base = nullptr, *d_total = nullptr;
+    CF_TRY(tmp.get(&d_hist, nh + 1, "selftest histogram"));
+    CF_TRY(tmp.get(&d_offs, nh + 1, "selftest offsets"));
+    CF_TRY(tmp.get(&d_part, nc + 1, "selftest column sums"));
+    CF_TRY(tmp.get(&d_base, nc + 1, "selftest column bases"));
+    if (total) CF_TRY(tmp.get(&d_total, 1, "selftest total"));
+    const bool run = D >= 1 && nh > 0;               // a refused D copies nothing
+    if (run && hipMemcpy(d_hist, hist, nh * 4, hipMemcpyHostToDevice) != hipSuccess) return cf_fail(ctx, -5, "selftest copy");
+    if (run && hipMemcpy(d_offs, offs, nh * 8, hipMemcpyHostToDevice) != hipSuccess) return cf_fail(ctx, -5, "selftest copy");   // (what the call leaves alone comes back as it went in)
+    if (total && hipMemcpy(d_total, total, 8, hipMemcpyHostToDevice) != hipSuccess) return cf_fail(ctx, -5, "selftest copy");
+    CF_TRY(cf_tile_digit_offsets(ctx, d_hist, n_tiles, D, d_offs, d_total, d_part, d_base));
+    CF_HIP(hipStreamSynchronize(ctx->stream));
+    if (run && hipMemcpy(offs, d_offs, nh * 8, hipMemcpyDeviceToHost) != hipSuccess) return cf_fail(ctx, -5, "selftest copy back");
+    if (total && hipMemcpy(total, d_total, 8, hipMemcpyDeviceToHost) != hipSuccess) return cf_fail(ctx, -5, "selftest copy back");
+    return 0;
+}
+
 }  // extern "C"

@@ -336,15 +336,26 @@ extern "C" int cf_comm_free(cf_ctx* ctx);   // cf_exchange.hip
 void cf_edit_free(cf_ctx* ctx);              // cf_edit.hip: drops the sequences cf_hpc left resident
 
 // primitives (cf_prims.hip)
+// exclusive scans into 64-bit sums; *total (host; may be null) = the sum, 0 for n <= 0.  d_out == d_in is allowed for the
+// 64-bit scan (cf_count.hip and cf_exchange.hip call it so): a thread of cf_scan_local has read its eight items before it
+// writes any, and no other thread touches them, so the aliased __restrict__ pair never meets on one element
+// (tests/primcheck.py pins in place == out of place through all three levels of the recursion).
 int cf_scan_exclusive_i64(cf_ctx* ctx, const int64_t* d_in, int64_t* d_out, int64_t n, int64_t* total);
 int cf_scan_exclusive_u32_to_i64(cf_ctx* ctx, const uint32_t* d_in, int64_t* d_out, int64_t n, int64_t* total);
-// exclusive scan, in (digit, tile) order, of a tile-major digit histogram hist[tile * D + digit] (D <= 512) -> offs in the
-// same layout; *d_total = the sum (device; may be null).  d_part, d_base: scratch of cf_tile_digit_chunks(n_tiles) * D entries.
+// exclusive scan, in (digit, tile) order, of a tile-major digit histogram hist[tile * D + digit] (1 <= D <= 512, else -22)
+// -> offs in the same layout; *d_total = the sum (device; may be null).  d_part, d_base: scratch of
+// cf_tile_digit_chunks(n_tiles) * D entries.  n_tiles = 0: returns 0 with no launch; neither offs nor *d_total is written.
 int cf_tile_digit_chunks(int n_tiles);
 int cf_tile_digit_offsets(cf_ctx* ctx, const uint32_t* d_hist, int n_tiles, int D, int64_t* d_offs, int64_t* d_total, uint32_t* d_part, int64_t* d_base);
 // stable LSD radix sort of 64-bit keys on the whole bytes that hold the `bits` low bits; result lands in d_keys (d_tmp is scratch)
 int cf_radix_sort_u64(cf_ctx* ctx, unsigned long long* d_keys, unsigned long long* d_tmp, int64_t n, int bits);
 int cf_radix_sort_u64_any(cf_ctx* ctx, unsigned long long* d_keys, unsigned long long* d_tmp, int64_t n, int bits, unsigned long long** result);
+// stable LSD radix sort of n 16-byte records (four 32-bit words) by n_fields fields, least significant field first; field f
+// is word words[f] (0 .. 3) with bits[f] (0 .. 32) significant bits.  The contract of `bits`: a field is sorted on the
+// ceil(bits / 8) low BYTES of its word.  The bits of the word above that rounded width take no part (records equal below them
+// keep their input order, whatever those bits hold); the bits between `bits` and the rounded width DO take part, so a caller
+// whose word holds something else there either wants it sorted on or keeps it equal.  bits = 0 skips the field.  The sorted
+// records end in d_recs (d_tmp: scratch of the same size), after an odd number of passes through a copy.
 int cf_radix_sort_rec16(cf_ctx* ctx, void* d_recs, void* d_tmp, int64_t n, const int* words, const int* bits, int n_fields);
 // keys per tile of the scan and records per tile of cf_radix_sort_rec16
 int cf_scan_tile();

@@ -362,7 +362,7 @@ int cf_scan_tile() { return SCAN_TILE; }
 int cf_radix_rec16_tile() { return RS_TILE; }
 
 // d_recs: n records of 16 bytes; d_tmp: scratch of the same size; fields: n_fields (word index, significant bits), least
-// significant field first.  The sorted records end in d_recs.
+// significant field first.  The sorted records end in d_recs.  (What `bits` means when it is no multiple of 8: cf_common.h.)
 int cf_radix_sort_rec16(cf_ctx* ctx, void* d_recs, void* d_tmp, int64_t n, const int* words, const int* bits, int n_fields) {
     if (n <= 1) return 0;
     const int ntiles = (int)((n + RS_TILE - 1) / RS_TILE);

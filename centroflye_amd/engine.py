@@ -694,6 +694,45 @@ class Engine:
         self._check(self._lib.cf_selftest_scan(self._ctx, _ptr(vals), vals.size, _ptr(out)), "cf_selftest_scan")
         return out
 
+    def selftest_scan_inplace(self, vals):
+        """selftest_scan with one device buffer as input and output."""
+        vals = np.ascontiguousarray(vals, np.int64)
+        out = np.zeros(vals.size + 1, np.int64)
+        self._check(self._lib.cf_selftest_scan_inplace(self._ctx, _ptr(vals), vals.size, _ptr(out)), "cf_selftest_scan_inplace")
+        return out
+
+    def selftest_scan_u32(self, vals):
+        """Exclusive scan of uint32 counts into int64 offsets; the last element is the total."""
+        vals = np.ascontiguousarray(vals, np.uint32)
+        out = np.zeros(vals.size + 1, np.int64)
+        self._check(self._lib.cf_selftest_scan_u32(self._ctx, _ptr(vals), vals.size, _ptr(out)), "cf_selftest_scan_u32")
+        return out
+
+    def selftest_sort_rec16(self, recs, words, bits):
+        """cf_radix_sort_rec16 of records of four uint32 by the fields (words[f], bits[f]), least significant field first."""
+        recs = np.ascontiguousarray(recs, np.uint32).reshape(-1, 4)
+        words = np.ascontiguousarray(words, np.int32)
+        bits = np.ascontiguousarray(bits, np.int32)
+        if words.size != bits.size:
+            raise ValueError("one width per field")
+        out = np.zeros_like(recs)
+        self._check(self._lib.cf_selftest_sort_rec16(self._ctx, _ptr(recs), recs.shape[0], _ptr(words), _ptr(bits), words.size, _ptr(out)),
+                    "cf_selftest_sort_rec16")
+        return out
+
+    def selftest_digit_offsets(self, hist, n_tiles, D, with_total=True, fill=-1):
+        """cf_tile_digit_offsets of the tile-major counts hist (n_tiles x D uint32) -> (offs int64 in the same layout, total or
+        None).  offs and the total start as `fill`: what the call does not write keeps it."""
+        hist = np.ascontiguousarray(hist, np.uint32).ravel()
+        n_tiles, D = int(n_tiles), int(D)
+        if hist.size != n_tiles * max(D, 1):
+            raise ValueError("hist holds n_tiles x max(D, 1) counts")
+        offs = np.full(hist.size, fill, np.int64)
+        total = np.full(1, fill, np.int64)
+        self._check(self._lib.cf_selftest_digit_offsets(self._ctx, _ptr(hist), n_tiles, D, _ptr(offs), _ptr(total) if with_total else None),
+                    "cf_selftest_digit_offsets")
+        return offs.reshape(n_tiles, max(D, 1)), (int(total[0]) if with_total else None)
+
     def selftest_owner_buckets(self, world):
         """The table bucketed for a virtual world, as cf_exchange_table's send buffer: (start int64[world + 1], keys uint64,
         vals uint64 = pres | multi << 32); owner o's records are start[o] .. start[o + 1] - 1."""

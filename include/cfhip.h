@@ -545,6 +545,20 @@ int cf_set_param(cf_ctx* ctx, const char* name, int64_t value);
 /* Self-tests of the device primitives against host results (used by tests/ only). */
 int cf_selftest_sort(cf_ctx* ctx, const uint64_t* keys, int64_t n, int32_t bits, uint64_t* out);
 int cf_selftest_scan(cf_ctx* ctx, const int64_t* in, int64_t n, int64_t* out);
+/* The other primitives of cf_prims.hip, one call each (tests/primcheck.py).
+ * cf_selftest_scan_inplace: cf_selftest_scan with one device buffer as input and output, as two stages call the scan.
+ * cf_selftest_scan_u32: the scan of 32-bit counts into 64-bit offsets; out[n] = the total, as for cf_selftest_scan.
+ * cf_selftest_sort_rec16: the stable sort of n records of four 32-bit words by n_fields <= 16 fields (words[f] = 0 .. 3,
+ * bits[f] = 0 .. 32), least significant field first.  A field is sorted on the whole bytes of its word that hold its
+ * bits[f] low bits: the bits of the word above them take no part, the bits between bits[f] and the next byte border do.
+ * cf_selftest_digit_offsets: offs[t * D + d] = the exclusive scan, in (digit, tile) order, of the tile-major counts
+ * hist[t * D + d] (1 <= D <= 512, else -22); *total = the sum, total may be NULL.  n_tiles = 0 returns 0 and writes
+ * neither offs nor *total. */
+int cf_selftest_scan_inplace(cf_ctx* ctx, const int64_t* in, int64_t n, int64_t* out);
+int cf_selftest_scan_u32(cf_ctx* ctx, const uint32_t* in, int64_t n, int64_t* out);
+int cf_selftest_sort_rec16(cf_ctx* ctx, const uint32_t* recs, int64_t n, const int32_t* words, const int32_t* bits, int32_t n_fields,
+                           uint32_t* out);
+int cf_selftest_digit_offsets(cf_ctx* ctx, const uint32_t* hist, int32_t n_tiles, int32_t D, int64_t* offs, int64_t* total);
 /* the arg-max of the greedy placement (read_placer.py:63-78: larger (s0, s1), then the larger offset, then the smaller id rank)
  * over n candidates given as rows (s0, s1, offset, rank, valid); out6 = (s0, s1, offset, rank, index of the winner, valid) */
 int cf_selftest_argmax(cf_ctx* ctx, const uint32_t* cands, int64_t n, uint32_t* out6);

@@ -16,7 +16,7 @@ The inputs: shapecheck.repeats_case(1, 4, 0) and cloud_size_case(513) for A1 - A
 mapcheck, scorecheck, editcheck and tandemcheck that gives the kernels work (editcheck's first pair is two empty strings,
 tandemcheck's first case has no reads: neither reaches an allocation), and xchcheck's smallest record set for the device steps of
 the table exchange (cf_selftest_owner_buckets, cf_selftest_merge_records) with their twins cf_reset_table + cf_merge_table and
-cf_or_unique_mask.  sequence(engine, steps) runs a part of it: the emulator
+cf_or_unique_mask, and one small call of each selftest export of cf_prims.hip.  sequence(engine, steps) runs a part of it: the emulator
 test uses it to walk every exit that a failed allocation takes."""
 import copy
 import ctypes as C
@@ -27,6 +27,7 @@ import numpy as np
 
 import editcheck
 import mapcheck
+import primcheck
 import scorecheck
 import shapecheck
 import tandemcheck
@@ -178,7 +179,13 @@ def _selftests(e):
     inp = _inputs()
     assert np.array_equal(e.selftest_sort(inp["sort"], 40), np.sort(inp["sort"]))
     assert np.array_equal(e.selftest_scan(inp["scan"]), np.concatenate([[0], np.cumsum(inp["scan"])]))
-
+    # the other primitives of cf_prims.hip, each with scratch of its own and the primitive's (primcheck holds their cases)
+    assert np.array_equal(e.selftest_scan_inplace(inp["scan"]), np.concatenate([[0], np.cumsum(inp["scan"])]))
+    counts = (inp["scan"] & 0xFFFFFFFF).astype(np.uint32)
+    assert np.array_equal(e.selftest_scan_u32(counts), primcheck.reference_scan(counts))
+    recs = primcheck.records(counts.size, {1: counts})
+    primcheck.check_sort(e, recs, [1], [24], "scratch")
+    primcheck.check_offsets(e, counts[:17 * 65].reshape(17, 65) >> np.uint32(16), "scratch")
 
 def _exchange(e):
     """The device steps of the table exchange for a virtual world and their host-mediated twins, on xchcheck's smallest records
