@@ -1,8 +1,8 @@
 #!/usr/bin/env bash
 # Build the HOST-EMULATED device library (test infrastructure only; see hip/hip_runtime.h).
 # usage: build_emu.sh                     -> libcfhip_emu.so
-#        build_emu.sh NAME [-DFLAG ...]   -> libcfhip_emu_NAME.so: the same sources with extra defines (the A/B builds of
-#                                            cf_dist.hip, tests/test_emu_variants.py)
+#        build_emu.sh NAME [-DFLAG ...]   -> libcfhip_emu_NAME.so: the same sources with extra defines (the diagnostic builds of
+#                                            cf_dist.hip and cf_count2.hip, tests/test_emu_variants.py)
 # Objects are kept in obj/ under a hash of the preprocessed source and the flags, so a build compiles only the sources whose
 # preprocessed text differs from one built before (a variant of cf_dist.hip: that file alone, ~9 s).
 set -euo pipefail

@@ -1,29 +1,17 @@
-"""The A/B builds of the distance kernel (cf_dist.hip's compile-time switches, timed against the default by tools/build_variant.sh
-and tools/dist_ab.py) compute what the default build computes — checked on the host emulator, each build in a process of its own
-(a build that writes out of bounds fails its test instead of the suite).  Every build runs the dominance-tie clouds, the random
-clouds of pathcheck.check_synthetic_clouds (a multi-chunk posting list, at a threshold that selects edges) and A1..A6 of the
+"""The diagnostic builds of the distance and counting kernels (compile-time switches of cf_dist.hip and cf_count2.hip, built for the
+GPU by tools/build_variant.sh) compute what the default build computes — checked on the host emulator, each build in a process of
+its own (a build that writes out of bounds fails its test instead of the suite).  Every build runs the dominance-tie clouds, the
+random clouds of pathcheck.check_synthetic_clouds (a multi-chunk posting list, at a threshold that selects edges) and A1..A6 of the
 lowcov fixture, under knobs that force the rare paths (no hot list, no sketch, a small table) and under the defaults.
 
 Result-preserving builds, by their comments in cf_dist.hip / cf_count2.hip:
-  CF_DIST_HOTBLK=1          hot-list entries through per-wave blocks of 64 (round 5, measured slower and kept off)
-  CF_DIST_PUSH_FLAT=1       the table sweep's pushes without the per-step grouping
-  CF_DIST_SKETCH_BY_B=1     the counting sketch indexed by b alone (round 6, measured and kept off)
-  CF_DIST_PROBE_TWICE=1     a second straight-line probe before an insert is parked (round 6, kept off)
-  CF_DIST_FILLRD=0          the fill level read in front of every drain instead of inside it
-  CF_DIST_DRAIN2=0          drains of 64 queued inserts, one per lane
-  CF_DIST_OLD_DRAIN=1       the drain's probe as nested match / claim branches (rounds 2-3)
-  CF_DIST_ITEMS_BLOCKED=1   wave w sweeps a contiguous run of the item records instead of a round-robin share
-  CF_DIST_PF_A / _PF_B      loads in flight per lane in the sketch / table sweep
-  CF_NARROW_PB=8            8 keys per bucket of the 6-byte-slot layout
   CF_DIST_STAMPS, CF_C2_STAMPS   per-phase clock sums of the distance / counting kernels (the host's clock is a counter)
   CF_DIST_DIAG_NOHOT        no first k-mer keeps the hot list (the filter scans; it read an empty list and selected nothing before)
   CF_DIST_DIAG_COUNT        counters of the parked inserts and drains, printed per launch
 Not here:
-  CF_DIST_ABL=n             removes the kernel's phases from the end (tools/dist_ablation.sh): wrong results by design
-  CF_DIST_DIAG_NOPARK       drops parked inserts (timing only): wrong results by design
   CF_NO_BUFFER_LOAD         the emulator's own build defines it: every emulator test runs it
-  CF_DIST_LB_THREADS / _LB_BLOCKS   launch bounds (register allocation): the host build's code is the default's
-  CF_PL2_STAMPS / _STAMPS2  placement, not the distance stage (test_emu_kernels.py covers its kernels)"""
+  CF_PL2_STAMPS / _STAMPS2  placement, not the distance stage (test_emu_kernels.py covers its kernels)
+(The A/B switches of the distance kernel's insert path, rounds 2 to 6, are retired: DESIGN.md, "Retired compile-time switches".)"""
 import os
 import pickle
 import subprocess
@@ -34,17 +22,6 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VARIANTS = {
-    "hotblk": ["-DCF_DIST_HOTBLK=1"],
-    "push_flat": ["-DCF_DIST_PUSH_FLAT=1"],
-    "sketch_by_b": ["-DCF_DIST_SKETCH_BY_B=1"],
-    "probe_twice": ["-DCF_DIST_PROBE_TWICE=1"],
-    "fillrd_off": ["-DCF_DIST_FILLRD=0"],
-    "drain2_off": ["-DCF_DIST_DRAIN2=0"],
-    "old_drain": ["-DCF_DIST_OLD_DRAIN=1"],
-    "items_blocked": ["-DCF_DIST_ITEMS_BLOCKED=1"],
-    "pf_a3": ["-DCF_DIST_PF_A=3"],
-    "pf_b2": ["-DCF_DIST_PF_B=2"],
-    "narrow_pb8": ["-DCF_NARROW_PB=8"],
     "dist_stamps": ["-DCF_DIST_STAMPS"],
     "c2_stamps": ["-DCF_C2_STAMPS"],
     "diag_nohot": ["-DCF_DIST_DIAG_NOHOT"],
