@@ -100,6 +100,23 @@ class MonokmersShape(C.Structure):
         "n_distinct", "n_kmers", "n_occ", "n_rounds", "n_sorts", "n_sort_passes")] + [("phase_ms", C.c_float * 4)]
 
 
+class MonomapRead(C.Structure):
+    """Mirror of ``cf_monomap_read``."""
+    _fields_ = [(n, C.c_int32) for n in ("n_hits", "e0", "j0", "i0", "e1", "j1", "i1", "valid", "n_path")]
+
+
+class MonomapHit(C.Structure):
+    """Mirror of ``cf_monomap_hit``."""
+    _fields_ = [(n, C.c_int32) for n in ("e", "j", "i")]
+
+
+class MonomapShape(C.Structure):
+    """Mirror of ``cf_monomap_shape``."""
+    _fields_ = [(n, C.c_int64) for n in (
+        "sort_tile", "scan_tile", "block", "launch_cap", "n_edges", "n_reads", "k", "with_hits", "n_edge_letters", "n_read_letters",
+        "n_edge_windows", "n_indexed", "n_hits", "n_path", "n_rounds", "n_sorts")] + [("phase_ms", C.c_float * 4)]
+
+
 # every symbol include/cfhip.h declares: name -> (restype, argtypes)
 _P, _I64, _I32, _U32 = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32
 _PI64 = C.POINTER(C.c_int64)
@@ -158,6 +175,9 @@ PROTOTYPES = {
     "cf_monokmers_run": (C.c_int, [_P, _P, _P, _I64, _I64, _I64, _I32, _I32, _PI64, C.POINTER(C.c_float)]),
     "cf_monokmers_get": (C.c_int, [_P, _P, _I64, _PI64, _P, _P, _I64, _PI64]),
     "cf_monokmers_info": (C.c_int, [_P, C.POINTER(MonokmersShape)]),
+    "cf_monomap_run": (C.c_int, [_P, _P, _P, _P, _P, _I64, _P, _P, _I64, _I64, _I32, _I32, _P, C.POINTER(C.c_float)]),
+    "cf_monomap_get": (C.c_int, [_P, _P, _P, _I64, _PI64, _P, _P, _I64, _PI64]),
+    "cf_monomap_info": (C.c_int, [_P, C.POINTER(MonomapShape)]),
     "cf_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "cf_get_times": (C.c_int, [_P, C.POINTER(Times)]),
     "cf_set_param": (C.c_int, [_P, C.c_char_p, _I64]),

@@ -1,34 +1,46 @@
-"""The cen6 pipeline's driver up to the graph: the drop-in for the reference's ``scripts/centroFlyeMono.py`` as far as this project
-builds it.  It takes the reference's arguments and ``--stop-after {correction,graph}``; without ``--stop-after`` it refuses at once
-(mapping reads to the graph, scaffolding, pseudounits and polishing are not built) and writes nothing.
+"""The cen6 pipeline's driver up to the pseudounits: the drop-in for the reference's ``scripts/centroFlyeMono.py`` as far as this project
+builds it.  It takes the reference's arguments and ``--stop-after {correction,graph,mapping,scaffolds,pseudounits}``; without
+``--stop-after`` it refuses at once (polishing is not built) and writes nothing.
 
-With it: the report is read (``SD_Report``), the monostrings are corrected (``error_correction``, verbose, on a copy) and, for
-``graph``, the iterative de Bruijn graph is built for k = --min-k .. --max-k; the reference's progress lines are printed.  Two files
-of our own are written, each through ``.tmp`` and a rename (formats: INTEGRATION.md):
-  OUTDIR/ec_monostrings.tsv   id, part ('.' for an uncut read), strand, string — one line per corrected read, in output order
-  OUTDIR/idb/contigs.tsv      k, contig — the contigs of every k, sorted"""
+With it: the report is read (``SD_Report``), the monostrings are corrected (``error_correction``, verbose, on a copy), the iterative
+de Bruijn graph is built for k = --min-k .. --max-k, the corrected reads are mapped to the graph of --max-k (``map_reads``, one
+device call), the long edges are chained into scaffolds (``scaffolding``), the reads are laid on the scaffolds (``read2scaffolds``,
+``cover_scaffolds_w_reads``) and the pseudounits with the reads that cover them are cut out (``extract_read_pseudounits``); the
+reference's progress lines are printed.  The reference joins its first two scaffolds by hand for cen6 and fails with fewer than two;
+here every scaffold goes to the three later calls as the list they take, and no scaffold gives empty files.  Files of our own are
+written, each through ``.tmp`` and a rename (formats: INTEGRATION.md):
+  OUTDIR/ec_monostrings.tsv    id, part ('.' for an uncut read), strand, string — one line per corrected read, in output order
+  OUTDIR/idb/contigs.tsv       k, contig — the contigs of every k, sorted
+  OUTDIR/idb/edges.tsv         the graph of --max-k: index in edges() order, u, v, key, colour, length, median coverage, sequence
+  OUTDIR/mappings.tsv          id, part, first hit, last hit (edge:letter:read position), valid, path as edge indices; '.' without a hit
+  OUTDIR/scaffolds.tsv         index, edge indices, sequence
+  OUTDIR/pseudounits.tsv       scaffold, unit, st, en, number of reads
+  OUTDIR/read_pseudounits.tsv  scaffold, unit, id, part, st, en, strand — sorted by id and part within a unit"""
 import argparse
 import os
 import sys
 
-from .debruijn_graph import iterative_graph
+import numpy as np
+
+from .debruijn_graph import cover_scaffolds_w_reads, extract_read_pseudounits, iterative_graph, read2scaffolds, scaffolding
 from .mono_error_correction import error_correction
 from .sd_parser import SD_Report
 
+STAGES = ('correction', 'graph', 'mapping', 'scaffolds', 'pseudounits')
+
 
 def parse_args(argv=None):
-    parser = argparse.ArgumentParser(description="Monostring error correction and the iterative de Bruijn graph of the cen6 pipeline")
+    parser = argparse.ArgumentParser(description="The cen6 pipeline from the String Decomposer report to the pseudounits and the reads that cover them")
     parser.add_argument('--sd-report', help='the String Decomposer report (decomposition.tsv)', required=True)
     parser.add_argument('--monomers', help='FASTA of the monomers the report was made with', required=True)
     parser.add_argument('--centromeric-reads', help='the centromeric reads (read by the polishing stage only: accepted, unused)', required=True)
-    parser.add_argument('--outdir', help='directory the two files are written to', required=True)
+    parser.add_argument('--outdir', help='directory the files are written to', required=True)
     parser.add_argument('--min-k', help='smallest k of the iterative graph', type=int, default=100)
     parser.add_argument('--max-k', help='largest k of the iterative graph', type=int, default=400)
     parser.add_argument('--min-mult', help='windows a mono-k-mer needs to count as frequent', type=int, default=5)
     parser.add_argument('--polish-n-iter', help='polishing rounds (accepted, unused)', type=int, default=2)
     parser.add_argument('--polish-n-threads', help='polishing threads (accepted, unused)', type=int, default=50)
-    parser.add_argument('--stop-after', choices=('correction', 'graph'),
-                        help='Stop after this stage (required: the stages behind the graph are not built)')
+    parser.add_argument('--stop-after', choices=STAGES, help='Stop after this stage (required: polishing is not built)')
     return parser.parse_args(argv)
 
 
@@ -39,9 +51,13 @@ def _write(path, lines):
     os.replace(tmp, path)
 
 
+def _id_part(key):
+    return (key[0], str(key[1])) if isinstance(key, tuple) else (key, '.')
+
+
 def ec_lines(ec_monostrings):
     for key, ms in ec_monostrings.items():
-        r_id, part = (key[0], str(key[1])) if isinstance(key, tuple) else (key, '.')
+        r_id, part = _id_part(key)
         yield f'{r_id}\t{part}\t{ms.strand}\t{ms.tostring()}\n'
 
 
@@ -51,11 +67,45 @@ def contig_lines(contigs):
             yield f'{k}\t{contig}\n'
 
 
+def edge_lines(edges):
+    """edges: [(u, v, key, colour, coverages, sequence)] in edges() order"""
+    for x, (u, v, key, colour, coverages, seq) in enumerate(edges):
+        yield f'{x}\t{u}\t{v}\t{key}\t{colour}\t{len(coverages)}\t{float(np.median(coverages)):g}\t{seq}\n'
+
+
+def mapping_lines(mappings, edge_index):
+    for key, m in mappings.items():
+        r_id, part = _id_part(key)
+        if m is None:
+            yield f'{r_id}\t{part}\t.\t.\t.\t.\n'
+            continue
+        ((e0, j0), i0), ((e1, j1), i1), valid, path = m
+        yield f'{r_id}\t{part}\t{e0}:{j0}:{i0}\t{e1}:{j1}:{i1}\t{int(bool(valid))}\t{",".join(str(edge_index[tuple(e)]) for e in path)}\n'
+
+
+def scaffold_lines(scaffolds, edge_scaffolds, edge_index):
+    for x, (seq, path) in enumerate(zip(scaffolds, edge_scaffolds)):
+        yield f'{x}\t{",".join(str(edge_index[tuple(e)]) for e in path)}\t{seq}\n'
+
+
+def pseudounit_lines(pseudounits, read_pseudounits):
+    for s, (units, reads) in enumerate(zip(pseudounits, read_pseudounits)):
+        for x, ((st, en), covering) in enumerate(zip(units, reads)):
+            yield f'{s}\t{x}\t{st}\t{en}\t{len(covering)}\n'
+
+
+def read_pseudounit_lines(read_pseudounits):
+    for s, reads in enumerate(read_pseudounits):
+        for x, covering in enumerate(reads):
+            for r_id, part, st, en, strand in sorted(_id_part(key) + tuple(v) for key, v in covering.items()):
+                yield f'{s}\t{x}\t{r_id}\t{part}\t{st}\t{en}\t{strand}\n'
+
+
 def main(argv=None):
     params = parse_args(argv)
     if params.stop_after is None:
-        sys.exit('centroFlyeMono: mapping reads to the graph, scaffolding, pseudounits and polishing are not built; '
-                 'run with --stop-after correction or --stop-after graph')
+        sys.exit('centroFlyeMono: polishing is not built; run with --stop-after ' + ', '.join(STAGES[:-1]) + ' or ' + STAGES[-1])
+    stop = STAGES.index(params.stop_after)
     os.makedirs(params.outdir, exist_ok=True)
 
     print('Reading report')
@@ -64,11 +114,39 @@ def main(argv=None):
     print('Error correcting monoreads')
     ec_monostrings = error_correction(sd_report.monostrings, verbose=True, inplace=False)
     _write(os.path.join(params.outdir, 'ec_monostrings.tsv'), ec_lines(ec_monostrings))
-    if params.stop_after == 'correction':
+    if stop == 0:
         return 0
 
     print('Building the graph')
     idb = os.path.join(params.outdir, 'idb')
-    contigs, _, _, _ = iterative_graph(ec_monostrings, min_k=params.min_k, max_k=params.max_k, outdir=idb, min_mult=params.min_mult)
+    contigs, dbs, _, _ = iterative_graph(ec_monostrings, min_k=params.min_k, max_k=params.max_k, outdir=idb, min_mult=params.min_mult)
     _write(os.path.join(idb, 'contigs.tsv'), contig_lines(contigs))
+    if stop == 1:
+        return 0
+
+    print('Mapping reads to the graph')
+    db = dbs[params.max_k]
+    db_edges = db.graph.edges()
+    edge_index = {e: x for x, e in enumerate(db_edges)}
+    datas = [db.graph.data(*e) for e in db_edges]
+    _write(os.path.join(idb, 'edges.tsv'), edge_lines([e + (d['color'], d['coverages'], d['edge_kmer']) for e, d in zip(db_edges, datas)]))
+    mappings = db.map_reads(ec_monostrings, verbose=False)
+    _write(os.path.join(params.outdir, 'mappings.tsv'), mapping_lines(mappings, edge_index))
+    if stop == 2:
+        return 0
+
+    print('Scaffolding')
+    scaffolds, edge_scaffolds = scaffolding(db, mappings)
+    _write(os.path.join(params.outdir, 'scaffolds.tsv'), scaffold_lines(scaffolds, edge_scaffolds, edge_index))
+    if stop == 3:
+        return 0
+
+    print('Mapping reads to scaffolds')
+    r2s = read2scaffolds(db, edge_scaffolds, mappings, ec_monostrings)
+    print('Covering scaffolds with reads')
+    coverage = cover_scaffolds_w_reads(r2s, mappings, scaffolds, ec_monostrings, k=db.k)
+    print('Extracting pseudounits and reads covering them')
+    pseudounits, read_pseudounits = extract_read_pseudounits(coverage, scaffolds, monostrings=ec_monostrings)
+    _write(os.path.join(params.outdir, 'pseudounits.tsv'), pseudounit_lines(pseudounits, read_pseudounits))
+    _write(os.path.join(params.outdir, 'read_pseudounits.tsv'), read_pseudounit_lines(read_pseudounits))
     return 0

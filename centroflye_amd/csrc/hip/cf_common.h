@@ -190,6 +190,15 @@ struct cf_ctx {
     std::vector<cf_monokmer_occ> monokmers_occ;
     cf_monokmers_shape monokmers_last{};
 
+    // results of the last cf_monomap_run (cf_monomap.hip), in host memory: the reads' records, the paths as a CSR over its reads,
+    // the hits as a CSR (when asked for), and the run's shape and timings
+    bool monomap_have = false;
+    std::vector<cf_monomap_read> monomap_reads;
+    std::vector<int64_t> monomap_path_ptr, monomap_hit_ptr;
+    std::vector<int32_t> monomap_path;
+    std::vector<cf_monomap_hit> monomap_hits;
+    cf_monomap_shape monomap_last{};
+
     // host <-> device copies of the caller's (pageable) buffers go through pinned staging slots, one per copy thread
     // (cf_api.hip: cf_copy_h2d / cf_copy_d2h)
     static constexpr int kCopyThreads = 16;      // slots; CF_COPY_THREADS (1 .. 16, default 16) picks how many are used
@@ -360,3 +369,22 @@ int cf_radix_sort_rec16(cf_ctx* ctx, void* d_recs, void* d_tmp, int64_t n, const
 // keys per tile of the scan and records per tile of cf_radix_sort_rec16
 int cf_scan_tile();
 int cf_radix_rec16_tile();
+
+// the equality classes of the valid windows of k letters (cf_monokmers.hip): what cf_monokmers_run and cf_monomap_run share
+struct __attribute__((aligned(16))) cf_mk_rec { uint32_t w[4]; };
+struct cf_mk_ranked {
+    cf_mk_rec *rec, *rec2;      // the last round's sorted records (w[2] = the position), and the sort's buffer
+    uint32_t *R, *dist, *head;  // per position: the ranks of the round before the last, the letters up to the next gap or string end; per record: head flags
+    int64_t *e, *scalar;        // per record: the heads in front of it; two counters
+    int64_t n_valid, n_classes, n_rounds, n_sorts, n_sort_passes;
+    float sort_ms;
+};
+// The distances, the doubling rounds and, for k = 1, the grouping of the bytes.  d_bytes: the N letters of all strings back to back
+// on the device, padded with zeros to a multiple of 4 and 16 more; d_off: n_strings + 1 offsets (d_off[s] - d_off[0] is where
+// string s starts).  1 <= k <= N < 2^31.  Every buffer is taken through the caller's guard, each of N entries rounded up to a
+// multiple of 4.  It leaves the last round's records sorted: the n_valid valid windows first, class by class, ascending position
+// inside a class; head[i] marks a class's first record and e[i] = the heads in front of record i, so record i is of class
+// e[i] + head[i] - 1 of n_classes.  n_valid = 0 when no window of k letters is valid.  who: the caller's name, for messages.
+int cf_mk_rank_windows(cf_ctx* ctx, cf_scratch& tmp, const uint8_t* d_bytes, const int64_t* d_off, int64_t n_strings, int64_t N, int64_t k, int32_t gap,
+                       const char* who, cf_mk_ranked* out);
+int cf_mk_launch_cap(const cf_ctx* ctx);

@@ -34,14 +34,14 @@
 //                                         rank[c] = j or -1; the last kept index + 1 = K
 //                         (scan)          the CSR's offsets from the counts
 //                         cf_mk_occ       record i of a kept class c goes to ptr[rank[c]] + i - first record of c, as (string, index)
+// The distances and the rounds are one function, cf_mk_rank_windows (cf_common.h), which cf_monomap.hip runs over the edges of the
+// graph and the reads together; the finish is cf_monokmers_run's own.
 // Every kernel is a grid-stride streaming pass of 256 threads with 4-, 8- or 16-byte accesses per lane and no LDS, no atomics and no
 // wave operation; every index is below N < 2^31 and is checked against its array's length where it is a loaded value.
 #include "cf_common.h"
 
 #define CF_MK_BLOCK 256
 #define CF_MK_WGS_PER_CU 8
-
-struct __attribute__((aligned(16))) cf_mk_rec { uint32_t w[4]; };
 
 #define CF_MK_LOOP(i, n) for (int64_t i = (int64_t)blockIdx.x * CF_MK_BLOCK + threadIdx.x; i < (n); i += (int64_t)gridDim.x * CF_MK_BLOCK)
 
@@ -204,8 +204,103 @@ cf_mk_occ(const cf_mk_rec* __restrict__ rec, const uint32_t* __restrict__ head, 
     }
 }
 
-static int cf_mk_launch_cap(const cf_ctx* ctx) { return std::max(1, ctx->n_cu) * CF_MK_WGS_PER_CU; }
+int cf_mk_launch_cap(const cf_ctx* ctx) { return std::max(1, ctx->n_cu) * CF_MK_WGS_PER_CU; }
 static int cf_mk_bits(uint64_t x) { int b = 1; while (b < 32 && (x >> b)) ++b; return b; }      // bits that hold the value x (at least 1)
+
+// The equality classes of the valid windows of k letters (declared in cf_common.h): the distances, the rounds and the grouping of
+// the bytes for k = 1.  d_bytes: the N letters on the device, padded with zeros to a multiple of 4 and 16 more; d_off: the
+// n_strings + 1 offsets.  N >= 1 and k <= N.  Every buffer comes from the caller's guard.
+int cf_mk_rank_windows(cf_ctx* ctx, cf_scratch& tmp, const uint8_t* d_bytes, const int64_t* d_off, int64_t n_strings, int64_t N, int64_t k, int32_t gap,
+                       const char* who, cf_mk_ranked* out) {
+    hipEvent_t e2 = ctx->ev2, e3 = ctx->ev3;
+    float t = 0.f, sort_ms = 0.f;
+    const int cap = cf_mk_launch_cap(ctx);
+    const size_t n = (size_t)N, n4 = (n + 3) & ~(size_t)3;
+    const uint32_t ugap = (uint32_t)gap, kk = (uint32_t)k;
+    auto grid = [&](int64_t items) { return dim3((unsigned)cf_grid_for(items, CF_MK_BLOCK, cap)); };
+    int64_t *d_e = nullptr, *d_scalar = nullptr;
+    uint32_t *d_R = nullptr, *d_dist = nullptr, *d_head = nullptr;
+    cf_mk_rec *d_rec = nullptr, *d_rec2 = nullptr;
+    cf_mk_ranked shape{};
+    CF_TRY(tmp.get(&d_R, n4, "monokmers ranks"));
+    CF_TRY(tmp.get(&d_dist, n4, "monokmers distances"));
+    CF_TRY(tmp.get(&d_head, n4, "monokmers head flags"));
+    CF_TRY(tmp.get(&d_e, n4, "monokmers scan"));
+    CF_TRY(tmp.get(&d_rec, n4, "monokmers records"));
+    CF_TRY(tmp.get(&d_rec2, n4, "monokmers sort buffer"));
+    CF_TRY(tmp.get(&d_scalar, 2, "monokmers counters"));
+
+    // the distances: the stop flags, the list of stops and the marks of the last bytes live in the record buffers until round 1
+    {
+        uint32_t* d_stop = (uint32_t*)d_rec;                        // n4 entries
+        uint32_t* d_list = (uint32_t*)d_rec + n4;                   // at most n entries
+        uint8_t* d_last = (uint8_t*)((uint32_t*)d_rec + 2 * n4);    // n4 bytes
+        CF_HIP(hipMemsetAsync(d_last, 0, n4, ctx->stream));
+        if (n_strings > 0) {
+            hipLaunchKernelGGL(cf_mk_last, grid(n_strings), dim3(CF_MK_BLOCK), 0, ctx->stream, (const int64_t*)d_off, n_strings, d_last, N);
+            CF_KERNEL_CHECK("cf_mk_last");
+        }
+        hipLaunchKernelGGL(cf_mk_stops, grid((int64_t)(n4 / 4)), dim3(CF_MK_BLOCK), 0, ctx->stream, (const uint32_t*)d_bytes, (const uint32_t*)d_last, ugap,
+                           (cf_mk_rec*)d_stop, N);
+        CF_KERNEL_CHECK("cf_mk_stops");
+        int64_t n_stops = 0;
+        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_stop, d_e, N, &n_stops));
+        if (n_stops < 1 || n_stops > N) return cf_fail(ctx, -5, std::string(who) + ": the stops do not add up (internal error)");
+        hipLaunchKernelGGL(cf_mk_stop_list, grid(N), dim3(CF_MK_BLOCK), 0, ctx->stream, (const uint32_t*)d_stop, (const int64_t*)d_e, d_list, N, n_stops);
+        CF_KERNEL_CHECK("cf_mk_stop_list");
+        hipLaunchKernelGGL(cf_mk_dist, grid(N), dim3(CF_MK_BLOCK), 0, ctx->stream, (const uint8_t*)d_bytes, (const int64_t*)d_e, (const uint32_t*)d_list, ugap,
+                           d_dist, d_R, N, n_stops);
+        CF_KERNEL_CHECK("cf_mk_dist");
+    }
+
+    // the rounds: (shift d, length L) = (1, 2), (2, 4), .. (a / 2, a), then (k - a, k) when k is no power of two; k = 1: one
+    // grouping of the bytes themselves, which is no combining round
+    struct round { uint32_t d, need; };
+    std::vector<round> rounds;
+    uint32_t a = 1;
+    while ((uint64_t)a * 2 <= (uint64_t)kk) { rounds.push_back(round{a, a * 2}); a *= 2; }
+    if (a != kk) rounds.push_back(round{kk - a, kk});
+    shape.n_rounds = (int64_t)rounds.size();
+    if (rounds.empty()) rounds.push_back(round{0u, 1u});
+    int64_t n_ids = 256, n_valid = 0, n_classes = 0;      // ids of the round before: the bytes
+    for (size_t r = 0; r < rounds.size(); ++r) {
+        const bool last = r + 1 == rounds.size();
+        const uint32_t sentinel = (uint32_t)n_ids;
+        hipLaunchKernelGGL(cf_mk_keys, grid(N), dim3(CF_MK_BLOCK), 0, ctx->stream, (const uint32_t*)d_R, (const uint32_t*)d_dist, d_rec, N, rounds[r].d,
+                           rounds[r].need, sentinel);
+        CF_KERNEL_CHECK("cf_mk_keys");
+        const int b = cf_mk_bits((uint64_t)n_ids);
+        const int words[2] = {1, 0}, bits[2] = {b, b};
+        CF_HIP(hipEventRecord(e2, ctx->stream));
+        if (rounds[r].d == 0) CF_TRY(cf_radix_sort_rec16(ctx, d_rec, d_rec2, N, words + 1, bits + 1, 1));
+        else CF_TRY(cf_radix_sort_rec16(ctx, d_rec, d_rec2, N, words, bits, 2));
+        CF_HIP(hipEventRecord(e3, ctx->stream));
+        CF_HIP(hipEventSynchronize(e3));
+        (void)hipEventElapsedTime(&t, e2, e3); sort_ms += t;
+        ++shape.n_sorts;
+        shape.n_sort_passes += (rounds[r].d == 0 ? 1 : 2) * ((b + 7) / 8);
+        CF_HIP(hipMemsetAsync(d_scalar, 0, 16, ctx->stream));
+        hipLaunchKernelGGL(cf_mk_heads, grid(N), dim3(CF_MK_BLOCK), 0, ctx->stream, (const cf_mk_rec*)d_rec, d_head, N, sentinel, d_scalar);
+        CF_KERNEL_CHECK("cf_mk_heads");
+        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_head, d_e, N, &n_classes));
+        CF_TRY(cf_copy_d2h(ctx, &n_valid, d_scalar, 8));
+        if (n_valid < 0 || n_valid > N || n_classes < 0 || n_classes > n_valid || (n_valid > 0) != (n_classes > 0))
+            return cf_fail(ctx, -5, std::string(who) + ": the classes of a round do not add up (internal error)");
+        if (!last && n_valid > 0) {
+            hipLaunchKernelGGL(cf_mk_ids, grid(n_valid), dim3(CF_MK_BLOCK), 0, ctx->stream, (const cf_mk_rec*)d_rec, (const uint32_t*)d_head, (const int64_t*)d_e,
+                               d_R, n_valid, N);
+            CF_KERNEL_CHECK("cf_mk_ids");
+        }
+        n_ids = std::max<int64_t>(n_classes, 1);
+        if (n_valid == 0) break;      // no window of this length: none of a longer one
+    }
+    shape.rec = d_rec; shape.rec2 = d_rec2; shape.R = d_R; shape.dist = d_dist; shape.head = d_head; shape.e = d_e; shape.scalar = d_scalar;
+    shape.n_valid = n_valid;      // (a break in front of the last round leaves 0)
+    shape.n_classes = n_classes;
+    shape.sort_ms = sort_ms;
+    *out = shape;
+    return 0;
+}
 
 extern "C" {
 
@@ -285,23 +380,13 @@ int cf_monokmers_run(cf_ctx* ctx, const uint8_t* bytes, const int64_t* off, int6
     float t = 0.f, sort_ms = 0.f, copy_ms = 0.f;
     const int cap = cf_mk_launch_cap(ctx);
     const size_t n = (size_t)N, n4 = (n + 3) & ~(size_t)3;
-    const uint32_t ugap = (uint32_t)gap, kk = (uint32_t)k;
     auto grid = [&](int64_t items) { return dim3((unsigned)cf_grid_for(items, CF_MK_BLOCK, cap)); };
     cf_scratch tmp(ctx);
     uint8_t* d_bytes = nullptr;
-    int64_t *d_off = nullptr, *d_e = nullptr, *d_scalar = nullptr;
-    uint32_t *d_R = nullptr, *d_dist = nullptr, *d_head = nullptr;
-    cf_mk_rec *d_rec = nullptr, *d_rec2 = nullptr;
+    int64_t* d_off = nullptr;
     CF_HIP(hipEventRecord(e0, ctx->stream));
     CF_TRY(tmp.get(&d_bytes, n4 + 16, "monokmers letters"));
     CF_TRY(tmp.get(&d_off, (size_t)n_strings + 1, "monokmers offsets"));
-    CF_TRY(tmp.get(&d_R, n4, "monokmers ranks"));
-    CF_TRY(tmp.get(&d_dist, n4, "monokmers distances"));
-    CF_TRY(tmp.get(&d_head, n4, "monokmers head flags"));
-    CF_TRY(tmp.get(&d_e, n4, "monokmers scan"));
-    CF_TRY(tmp.get(&d_rec, n4, "monokmers records"));
-    CF_TRY(tmp.get(&d_rec2, n4, "monokmers sort buffer"));
-    CF_TRY(tmp.get(&d_scalar, 2, "monokmers counters"));
     CF_HIP(hipMemsetAsync(d_bytes + n, 0, n4 + 16 - n, ctx->stream));
     CF_TRY(cf_copy_h2d(ctx, d_bytes, bytes + off[0], n));
     CF_TRY(cf_copy_h2d(ctx, d_off, off, ((size_t)n_strings + 1) * 8));
@@ -309,70 +394,16 @@ int cf_monokmers_run(cf_ctx* ctx, const uint8_t* bytes, const int64_t* off, int6
     CF_HIP(hipEventSynchronize(e1));
     (void)hipEventElapsedTime(&t, e0, e1); copy_ms += t;
 
-    // the distances: the stop flags, the list of stops and the marks of the last bytes live in the record buffers until round 1
-    {
-        uint32_t* d_stop = (uint32_t*)d_rec;                        // n4 entries
-        uint32_t* d_list = (uint32_t*)d_rec + n4;                   // at most n entries
-        uint8_t* d_last = (uint8_t*)((uint32_t*)d_rec + 2 * n4);    // n4 bytes
-        CF_HIP(hipMemsetAsync(d_last, 0, n4, ctx->stream));
-        if (n_strings > 0) {
-            hipLaunchKernelGGL(cf_mk_last, grid(n_strings), dim3(CF_MK_BLOCK), 0, ctx->stream, (const int64_t*)d_off, n_strings, d_last, N);
-            CF_KERNEL_CHECK("cf_mk_last");
-        }
-        hipLaunchKernelGGL(cf_mk_stops, grid((int64_t)(n4 / 4)), dim3(CF_MK_BLOCK), 0, ctx->stream, (const uint32_t*)d_bytes, (const uint32_t*)d_last, ugap,
-                           (cf_mk_rec*)d_stop, N);
-        CF_KERNEL_CHECK("cf_mk_stops");
-        int64_t n_stops = 0;
-        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_stop, d_e, N, &n_stops));
-        if (n_stops < 1 || n_stops > N) return cf_fail(ctx, -5, "cf_monokmers_run: the stops do not add up (internal error)");
-        hipLaunchKernelGGL(cf_mk_stop_list, grid(N), dim3(CF_MK_BLOCK), 0, ctx->stream, (const uint32_t*)d_stop, (const int64_t*)d_e, d_list, N, n_stops);
-        CF_KERNEL_CHECK("cf_mk_stop_list");
-        hipLaunchKernelGGL(cf_mk_dist, grid(N), dim3(CF_MK_BLOCK), 0, ctx->stream, (const uint8_t*)d_bytes, (const int64_t*)d_e, (const uint32_t*)d_list, ugap,
-                           d_dist, d_R, N, n_stops);
-        CF_KERNEL_CHECK("cf_mk_dist");
-    }
-
-    // the rounds: (shift d, length L) = (1, 2), (2, 4), .. (a / 2, a), then (k - a, k) when k is no power of two; k = 1: one
-    // grouping of the bytes themselves, which is no combining round
-    struct round { uint32_t d, need; };
-    std::vector<round> rounds;
-    uint32_t a = 1;
-    while ((uint64_t)a * 2 <= (uint64_t)kk) { rounds.push_back(round{a, a * 2}); a *= 2; }
-    if (a != kk) rounds.push_back(round{kk - a, kk});
-    shape.n_rounds = (int64_t)rounds.size();
-    if (rounds.empty()) rounds.push_back(round{0u, 1u});
-    int64_t n_ids = 256, n_valid = 0, n_classes = 0;      // ids of the round before: the bytes
-    for (size_t r = 0; r < rounds.size(); ++r) {
-        const bool last = r + 1 == rounds.size();
-        const uint32_t sentinel = (uint32_t)n_ids;
-        hipLaunchKernelGGL(cf_mk_keys, grid(N), dim3(CF_MK_BLOCK), 0, ctx->stream, (const uint32_t*)d_R, (const uint32_t*)d_dist, d_rec, N, rounds[r].d,
-                           rounds[r].need, sentinel);
-        CF_KERNEL_CHECK("cf_mk_keys");
-        const int b = cf_mk_bits((uint64_t)n_ids);
-        const int words[2] = {1, 0}, bits[2] = {b, b};
-        CF_HIP(hipEventRecord(e2, ctx->stream));
-        if (rounds[r].d == 0) CF_TRY(cf_radix_sort_rec16(ctx, d_rec, d_rec2, N, words + 1, bits + 1, 1));
-        else CF_TRY(cf_radix_sort_rec16(ctx, d_rec, d_rec2, N, words, bits, 2));
-        CF_HIP(hipEventRecord(e3, ctx->stream));
-        CF_HIP(hipEventSynchronize(e3));
-        (void)hipEventElapsedTime(&t, e2, e3); sort_ms += t;
-        ++shape.n_sorts;
-        shape.n_sort_passes += (rounds[r].d == 0 ? 1 : 2) * ((b + 7) / 8);
-        CF_HIP(hipMemsetAsync(d_scalar, 0, 16, ctx->stream));
-        hipLaunchKernelGGL(cf_mk_heads, grid(N), dim3(CF_MK_BLOCK), 0, ctx->stream, (const cf_mk_rec*)d_rec, d_head, N, sentinel, d_scalar);
-        CF_KERNEL_CHECK("cf_mk_heads");
-        CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_head, d_e, N, &n_classes));
-        CF_TRY(cf_copy_d2h(ctx, &n_valid, d_scalar, 8));
-        if (n_valid < 0 || n_valid > N || n_classes < 0 || n_classes > n_valid || (n_valid > 0) != (n_classes > 0))
-            return cf_fail(ctx, -5, "cf_monokmers_run: the classes of a round do not add up (internal error)");
-        if (!last && n_valid > 0) {
-            hipLaunchKernelGGL(cf_mk_ids, grid(n_valid), dim3(CF_MK_BLOCK), 0, ctx->stream, (const cf_mk_rec*)d_rec, (const uint32_t*)d_head, (const int64_t*)d_e,
-                               d_R, n_valid, N);
-            CF_KERNEL_CHECK("cf_mk_ids");
-        }
-        n_ids = std::max<int64_t>(n_classes, 1);
-        if (n_valid == 0) break;      // no window of this length: none of a longer one
-    }
+    cf_mk_ranked rk{};
+    CF_TRY(cf_mk_rank_windows(ctx, tmp, d_bytes, d_off, n_strings, N, k, gap, "cf_monokmers_run", &rk));
+    cf_mk_rec *d_rec = rk.rec, *d_rec2 = rk.rec2;
+    uint32_t* d_head = rk.head;
+    int64_t *d_e = rk.e, *d_scalar = rk.scalar;
+    const int64_t n_valid = rk.n_valid, n_classes = rk.n_classes;
+    sort_ms = rk.sort_ms;
+    shape.n_rounds = rk.n_rounds;
+    shape.n_sorts = rk.n_sorts;
+    shape.n_sort_passes = rk.n_sort_passes;
     shape.n_windows = n_valid;      // (a break in front of the last round leaves 0)
     shape.n_distinct = n_valid ? n_classes : 0;
 

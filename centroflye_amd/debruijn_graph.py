@@ -1,5 +1,7 @@
-"""The de Bruijn graph on monostrings up to its contigs: the drop-in for the part of the reference's ``scripts/debruijn_graph.py``
-that ``centroFlyeMono.py`` runs up to ``iterative_graph`` (mapping, scaffolding, pseudounits and polishing are not here).
+"""The de Bruijn graph on monostrings, the reads mapped to it, scaffolds and pseudounits: the drop-in for the reference's
+``scripts/debruijn_graph.py`` as far as ``centroFlyeMono.py`` runs it before polishing (``polish`` is not here).  The hits of the reads on
+the edges come from the device too (``Engine.monomap``, cf_monomap.hip); scaffolding and what follows it work on edge paths of a few
+dozen elements and are host Python.
 
 The k-mer counts — every gap-free window of k letters over all strings, counted exactly, in the order of first occurrence — come
 from the device (``Engine.monokmers``, cf_monokmers.hip); the reference slices a k-letter string at every position in Python.  The
@@ -229,6 +231,44 @@ class DeBruijnGraph:
         g = self.graph
         return {e: g.data(*e)['edge_kmer'] for e in g.edges() if g.data(*e)['color'] == 'blue'}
 
+    def index_edges(self, min_k=2):
+        """{k: {k-mer: (edge index, letter)}} for k = min_k .. self.k over the edges in ``edges()`` order, only the k-mers that occur
+        exactly once; memoised in ``self.db_index``.  Host Python, for the API: ``map_reads`` does not use it."""
+        if not hasattr(self, 'db_index'):
+            seqs = [self.graph.data(*e)['edge_kmer'] for e in self.graph.edges()]
+            self.db_index = {}
+            for k in range(min_k, self.k + 1):
+                places = {}
+                for e_ind, seq in enumerate(seqs):
+                    for j in range(len(seq) - k + 1):
+                        places.setdefault(seq[j:j + k], []).append((e_ind, j))
+                self.db_index[k] = {kmer: at[0] for kmer, at in places.items() if len(at) == 1}
+        return self.db_index
+
+    def map_reads(self, monoreads, gap_symb='?', verbose=True, engine=None):
+        """{read id: (((edge index, letter), first read position), ((edge index, letter), last read position), valid path, [edges])} or
+        None for a read without a hit: the hits of every read on the edge k-mers that occur exactly once, in one device call
+        (``Engine.monomap``, cf_monomap.hip; the rule: include/cfhip.h).  Edges are numbered in ``edges()`` order.  ``self.db_index`` is
+        neither built nor read."""
+        from . import session
+        engine = engine or session.engine()
+        g = self.graph
+        db_edges = g.edges()
+        strings = _as_strings(monoreads)
+        info, (ptr, path) = engine.monomap([g.data(*e)['edge_kmer'].encode('latin-1') for e in db_edges], [(u, v) for u, v, _ in db_edges],
+                                           [s.encode('latin-1') for s in strings.values()], self.k, gap_symb.encode('latin-1'))
+        ptr, path = ptr.tolist(), path.tolist()
+        mapping = {}
+        for x, (r_id, row) in enumerate(zip(strings, info.tolist())):
+            if verbose:
+                print(x + 1, len(strings))
+            n_hits, e0, j0, i0, e1, j1, i1, valid, _ = row
+            if n_hits == 0:
+                mapping[r_id] = None
+            else:
+                mapping[r_id] = (((e0, j0), i0), ((e1, j1), i1), bool(valid), [db_edges[e] for e in path[ptr[x]:ptr[x + 1]]])
+        return mapping
+
 
 def _as_strings(strings):
     """{id: str} of a dict of strings or MonoStrings"""
@@ -325,3 +365,194 @@ def iterative_graph(monostrings, min_k, max_k, outdir, min_mult=5, step=1, start
         input_strings = with_contigs(contigs, k)
         complex_kp1mers = get_paths_thru_complex_nodes(db, strings)
     return all_contigs, dbs, all_frequent, all_positions
+
+
+# ---------------------------------------------------------------- scaffolds and pseudounits (host Python: edge paths of a few dozen elements)
+class OrderedDiGraph(OrderedMultiDiGraph):
+    """The simple digraph of the scaffolding step: one edge per (u, v).  Its results depend on iteration orders of the graph library
+    the reference uses, which are kept here: components by their first node in node order, each found breadth first over successors,
+    then predecessors; the nodes of a component smaller than half the graph in the order of a set of them (built as that library
+    builds it: from the search order, then once more from that set), else in node order; successors and predecessors in insertion
+    order.  The nodes are tuples of ints, so the set's order is the same in every run."""
+
+    def add_edge(self, u, v, **data):
+        return OrderedMultiDiGraph.add_edge(self, u, v, key=0, **data)
+
+    def components(self):
+        seen, out = set(), []
+        for n in self.succ:
+            if n in seen:
+                continue
+            found, order, level = {n}, [n], [n]
+            while level:
+                nxt = []
+                for x in level:
+                    for y in list(self.succ[x]) + list(self.pred[x]):      # (no node is in both lists twice: found is checked)
+                        if y not in found:
+                            found.add(y)
+                            nxt.append(y)
+                            order.append(y)
+                level = nxt
+            comp = set(order)
+            seen.update(comp)
+            out.append(comp)
+        return out
+
+    def component_nodes(self, comp):
+        shown = set(n for n in comp if n in self.succ)
+        if 2 * len(shown) < len(self.succ):
+            return [n for n in shown if n in self.succ]
+        return [n for n in self.succ if n in shown]
+
+    def topological_order(self, comp):
+        """the component's nodes generation by generation, or None when it holds a cycle"""
+        nodes = self.component_nodes(comp)
+        waiting = {n: len(self.pred[n]) for n in nodes if self.pred[n]}
+        level = [n for n in nodes if not self.pred[n]]
+        order = []
+        while level:
+            nxt = []
+            for n in level:
+                order.append(n)
+                for child in self.succ[n]:
+                    waiting[child] -= 1
+                    if waiting[child] == 0:
+                        nxt.append(child)
+                        del waiting[child]
+            level = nxt
+        return None if waiting else order
+
+    def longest_path(self, order):
+        """the longest path of a component given in topological order: per node the first best predecessor in predecessor order, the
+        end the first farthest node in that order"""
+        if not order:
+            return []
+        dist = {}
+        for n in order:
+            best = (0, n)
+            froms = [(dist[p][0] + 1, p) for p in self.pred[n]]
+            if froms:
+                best = max(froms, key=lambda x: x[0])
+            dist[n] = best
+        at = max(dist, key=lambda n: dist[n][0])
+        path, before = [], None
+        while before != at:
+            path.append(at)
+            before, at = at, dist[at][1]
+        return path[::-1]
+
+
+def scaffolding(db, mappings, min_connections=2, additional_edges=list()):
+    """(scaffold strings, scaffolds as edge lists): long (blue) edges that reads with a valid path connect at least min_connections
+    times, chained along the longest path of every acyclic component of the connection graph, each link filled with its best
+    supported path, and extended left and right by the longest read path.  No scaffold_graph.dot is written."""
+    long_edges = list(db.get_long_edges())
+    anchors = set(long_edges + list(additional_edges))
+    valid_paths = [m[3] for m in mappings.values() if m is not None and m[2]]
+
+    connections = {}
+    for path in valid_paths:
+        shared = set(path) & anchors
+        if len(shared) > 1:
+            at = sorted(path.index(e) for e in shared)
+            for i, j in zip(at, at[1:]):
+                support = connections.setdefault((path[i], path[j]), {})
+                link = tuple(path[i:j + 1])
+                support[link] = support.get(link, 0) + 1
+
+    graph = OrderedDiGraph()
+    for e in long_edges:
+        graph.add_node(e)
+    for (e1, e2), support in connections.items():
+        if sum(support.values()) >= min_connections:
+            graph.add_edge(e1, e2)
+
+    edge_scaffolds = []
+    for comp in graph.components():
+        order = graph.topological_order(comp)
+        if order is None:
+            continue
+        chain = graph.longest_path(order)
+        scaffold = [chain[0]]
+        for e1, e2 in zip(chain, chain[1:]):
+            support = connections[(e1, e2)]
+            scaffold += max(support, key=support.get)[1:]
+        left, right = [], []
+        for path in valid_paths:
+            if chain[0] in path:
+                ext = path[:path.index(chain[0])]
+                if len(ext) > len(left):
+                    left = ext
+            if chain[-1] in path:
+                ext = path[path.index(chain[-1]) + 1:]
+                if len(ext) > len(right):
+                    right = ext
+        edge_scaffolds.append(list(left) + scaffold + list(right))
+    return [db.get_path(s) for s in edge_scaffolds], edge_scaffolds
+
+
+def read2scaffolds(db, scaffold_paths, mappings, monoreads):
+    """{read id: (scaffold, first coordinate, last coordinate)} of the reads whose valid path fits exactly one place of one scaffold"""
+    coords = [db.get_edgepath2coords(p) for p in scaffold_paths]
+    places = {}
+    for r_id, mapping in mappings.items():
+        if mapping is None or not mapping[2]:
+            continue
+        ((_, j_st), _), ((_, j_en), _), _, read_path = mapping
+        n = len(read_path)
+        for s, scaffold in enumerate(scaffold_paths):
+            for i in range(len(scaffold) - n + 1):
+                if scaffold[i:i + n] == read_path:
+                    places.setdefault(r_id, []).append((s, coords[s][i, j_st], coords[s][i + n - 1, j_en + db.k - 1]))
+    return {r_id: at[0] for r_id, at in places.items() if len(at) == 1}
+
+
+def cover_scaffolds_w_reads(r2s, mappings, scaffold_seqs, monoreads, k):
+    """per scaffold and letter {read id: (monomer, st, en)}: the reads laid on their scaffold letter by letter through ``mono2nucl`` —
+    as ``split_monostring`` leaves it, so a cut read covers what its truncated map still holds.  A read whose span on
+    the scaffold and in itself differ is skipped."""
+    coverage = [[{} for _ in seq] for seq in scaffold_seqs]
+    for r_id, (s, s_st, s_en) in r2s.items():
+        (_, r_st), (_, r_en), valid, _ = mappings[r_id]
+        if not valid or s_en - s_st != r_en - r_st + k - 1:
+            continue
+        m2n = monoreads[r_id].mono2nucl
+        for i in range(s_en - s_st + 1):
+            if r_st + i in m2n:
+                coverage[s][s_st + i][r_id] = m2n[r_st + i]
+    return coverage
+
+
+def partition_pseudounits(monostring):
+    """[(st, en)]: the string cut greedily into stretches that hold no monomer twice"""
+    units, st = [], 0
+    while st < len(monostring):
+        seen, en = set(), st
+        while en < len(monostring) and monostring[en] not in seen:
+            seen.add(monostring[en])
+            en += 1
+        units.append((st, en - 1))
+        st = en
+    return units
+
+
+def extract_read_pseudounits(scaf_read_coverage, scaffold_seqs, monostrings, min_coverage=0):
+    """(pseudounits per scaffold, per scaffold and kept pseudounit {read id: (st, en, strand)}): the reads that cover both ends of a
+    pseudounit, with the nucleotide span between their two monomers"""
+    pseudounits, read_pseudounits = [], []
+    for seq, cov in zip(scaffold_seqs, scaf_read_coverage):
+        units = partition_pseudounits(seq)
+        pseudounits.append(units)
+        per_unit = []
+        for u_st, u_en in units:
+            first, last = cov[u_st], cov[u_en]
+            r_ids = set(first) & set(last)
+            if len(r_ids) < min_coverage:
+                continue
+            spans = {}
+            for r_id in r_ids:
+                ends = first[r_id][1:] + last[r_id][1:]
+                spans[r_id] = (min(ends), max(ends), monostrings[r_id].strand)
+            per_unit.append(spans)
+        read_pseudounits.append(per_unit)
+    return pseudounits, read_pseudounits

@@ -634,19 +634,7 @@ class Engine:
         holds no gap byte.  Returns a structured array (MONOKMER_DTYPE: s, i, count, pos — the first window's string, index and
         offset in the concatenation), one row per k-mer; with positions=True also (ptr int64[n + 1], occ MONOKMER_OCC_DTYPE): every
         valid window of every k-mer, in ascending (s, i)."""
-        if isinstance(strings, tuple):
-            flat, off = strings
-            flat = np.frombuffer(flat, np.uint8) if isinstance(flat, (bytes, bytearray, memoryview)) else np.ascontiguousarray(flat, np.uint8)
-            off = np.ascontiguousarray(off, np.int64).reshape(-1)
-        else:
-            strings = [s.encode() if isinstance(s, str) else bytes(s) for s in strings]
-            flat = np.frombuffer(b"".join(strings), dtype=np.uint8)
-            off = np.zeros(len(strings) + 1, np.int64)
-            off[1:] = np.cumsum([len(s) for s in strings], dtype=np.int64)
-        if off.size < 1:
-            raise ValueError("the offsets have one entry per string and one more")
-        if int(off.max()) > flat.size:
-            raise ValueError("an offset lies beyond the bytes")
+        flat, off = self._flat_strings(strings)
         gap = gap.encode() if isinstance(gap, str) else bytes(gap)
         if len(gap) != 1:
             raise ValueError("the gap is one byte")
@@ -670,6 +658,72 @@ class Engine:
         milliseconds per phase."""
         s = _lib.MonokmersShape()
         self._check(self._lib.cf_monokmers_info(self._ctx, C.byref(s)), "cf_monokmers_info")
+        d = {n: int(getattr(s, n)) for n, _ in s._fields_ if n != "phase_ms"}
+        d["phase_ms"] = dict(zip(("copies", "sorts", "glue", "total"), (float(x) for x in s.phase_ms)))
+        return d
+
+    # ------------------------------------------------------------------ monoreads mapped to the graph's edges (cf_monomap.hip)
+    MONOMAP_READ_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.MonomapRead._fields_])
+    MONOMAP_HIT_DTYPE = np.dtype([(n, np.int32) for n, _ in _lib.MonomapHit._fields_])
+
+    @staticmethod
+    def _flat_strings(strings):
+        """a list of byte strings, or (bytes, offsets) -> (uint8 array, int64 offsets)"""
+        if isinstance(strings, tuple):
+            flat, off = strings
+            flat = np.frombuffer(flat, np.uint8) if isinstance(flat, (bytes, bytearray, memoryview)) else np.ascontiguousarray(flat, np.uint8)
+            off = np.ascontiguousarray(off, np.int64).reshape(-1)
+        else:
+            strings = [s.encode() if isinstance(s, str) else bytes(s) for s in strings]
+            flat = np.frombuffer(b"".join(strings), dtype=np.uint8)
+            off = np.zeros(len(strings) + 1, np.int64)
+            off[1:] = np.cumsum([len(s) for s in strings], dtype=np.int64)
+        if off.size < 1:
+            raise ValueError("the offsets have one entry per string and one more")
+        if int(off.max()) > flat.size:
+            raise ValueError("an offset lies beyond the bytes")
+        return flat, off
+
+    def monomap(self, edges, edge_uv, reads, k, gap=b"?", hits=False):
+        """The reads mapped to the edges (the rule: include/cfhip.h at cf_monomap_run).  edges, reads: a list of byte strings, or
+        (bytes, offsets); edge_uv: the nodes (u, v) of every edge, an (E, 2) array.  An edge k-mer is indexed when exactly one valid
+        edge window holds it; a hit is a valid read window that equals an indexed k-mer.  Returns a structured array per read
+        (MONOMAP_READ_DTYPE: n_hits, the first hit e0 j0 i0, the last hit e1 j1 i1 — -1 without a hit —, valid, n_path) and
+        (ptr int64[R + 1], path int32): the reads' paths of edge indices; with hits=True also (hptr int64[R + 1], hits
+        MONOMAP_HIT_DTYPE): every hit, in ascending i per read."""
+        e_flat, e_off = self._flat_strings(edges)
+        r_flat, r_off = self._flat_strings(reads)
+        n_edges, n_reads = e_off.size - 1, r_off.size - 1
+        uv = np.ascontiguousarray(edge_uv, np.int32).reshape(-1, 2)
+        if uv.shape[0] != n_edges:
+            raise ValueError("one (u, v) per edge")
+        u, v = np.ascontiguousarray(uv[:, 0]), np.ascontiguousarray(uv[:, 1])
+        gap = gap.encode() if isinstance(gap, str) else bytes(gap)
+        if len(gap) != 1:
+            raise ValueError("the gap is one byte")
+        info = np.zeros(max(n_reads, 1), self.MONOMAP_READ_DTYPE)
+        self._check(self._lib.cf_monomap_run(self._ctx, _ptr(e_flat) if e_flat.size else None, _ptr(e_off), _ptr(u) if n_edges else None,
+                                             _ptr(v) if n_edges else None, n_edges, _ptr(r_flat) if r_flat.size else None, _ptr(r_off), n_reads,
+                                             int(k), gap[0], 1 if hits else 0, _ptr(info), None), "cf_monomap_run")
+        n_path, n_hits = C.c_int64(), C.c_int64()
+        self._check(self._lib.cf_monomap_get(self._ctx, None, None, 0, C.byref(n_path), None, None, 0, C.byref(n_hits)), "cf_monomap_get")
+        ptr = np.zeros(n_reads + 1, np.int64)
+        path = np.zeros(max(n_path.value, 1), np.int32)
+        if not hits:
+            self._check(self._lib.cf_monomap_get(self._ctx, _ptr(ptr), _ptr(path), n_path.value, None, None, None, 0, None), "cf_monomap_get")
+            return info[:n_reads], (ptr, path[:n_path.value])
+        hptr = np.zeros(n_reads + 1, np.int64)
+        hit = np.zeros(max(n_hits.value, 1), self.MONOMAP_HIT_DTYPE)
+        self._check(self._lib.cf_monomap_get(self._ctx, _ptr(ptr), _ptr(path), n_path.value, None, _ptr(hptr), _ptr(hit), n_hits.value, None),
+                    "cf_monomap_get")
+        return info[:n_reads], (ptr, path[:n_path.value]), (hptr, hit[:n_hits.value])
+
+    def monomap_info(self):
+        """The shape constants of cf_monomap.hip (sort_tile, scan_tile, block, launch_cap), the figures of the last run (n_edges,
+        n_reads, k, with_hits, n_edge_letters, n_read_letters, n_edge_windows, n_indexed, n_hits, n_path, n_rounds, n_sorts) and its
+        device milliseconds per phase."""
+        s = _lib.MonomapShape()
+        self._check(self._lib.cf_monomap_info(self._ctx, C.byref(s)), "cf_monomap_info")
         d = {n: int(getattr(s, n)) for n, _ in s._fields_ if n != "phase_ms"}
         d["phase_ms"] = dict(zip(("copies", "sorts", "glue", "total"), (float(x) for x in s.phase_ms)))
         return d

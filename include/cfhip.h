@@ -501,6 +501,59 @@ int cf_monokmers_get(cf_ctx* ctx, cf_monokmer* kmers, int64_t cap, int64_t* n_ou
                      int64_t* n_occ_out);
 int cf_monokmers_info(cf_ctx* ctx, cf_monokmers_shape* out);
 
+/* Monoreads mapped to the edges of the de Bruijn graph (cf_monomap.hip): what the reference's DeBruijnGraph.map_reads computes with
+ * a dict of every window of every edge and a slice at every read position (scripts/debruijn_graph.py index_edges, map_reads).  The
+ * rule below is the specification (tests/monomapcheck.py restates it).
+ * cf_monomap_run: edge strings e_0 .. e_{E-1} = edge_bytes[edge_off[e], edge_off[e + 1]), E = n_edges >= 0, with the nodes u[e] and
+ * v[e] of every edge; read strings r_0 .. r_{R-1} = read_bytes[read_off[r], read_off[r + 1]), R = n_reads >= 0 (any bytes; offsets
+ * >= 0 and non-decreasing, so a string may be empty); N = edge letters + read letters < 2^31; k >= 1; gap: the gap byte (0 .. 255;
+ * the pipeline's is '?').
+ *   A window of either set is VALID iff it lies inside one string and holds no gap byte.  (An edge window with a gap can never
+ *   equal a read window, so leaving it out changes nothing against the reference.)
+ *   An edge k-mer is INDEXED iff exactly one valid edge window, over all edges together, has its bytes (a k-mer occurring twice is
+ *   dropped, not kept at its first place); its place is (e, j): edge e, letter j.
+ *   A HIT of read r is a valid read window (r, i) whose k bytes equal an indexed k-mer; it carries (e, j, i), i counted in the
+ *   whole read string, gaps included.  The hits of a read are in ascending i.
+ *   The PATH of a read is the edges of its hits with equal neighbours collapsed: a miss between two hits on one edge does not
+ *   split the run, A-B-A stays three elements, and no run reaches from one read into the next.
+ *   The read is VALID iff v[p_t] == u[p_t+1] for every consecutive pair of its path (a path of 0 or 1 elements is valid).
+ *   reads[r] (may be NULL): n_hits, the first hit (e0, j0, i0) and the last hit (e1, j1, i1) — all -1 without a hit —, valid, n_path.
+ *   with_hits != 0: every hit is kept for cf_monomap_get.  *ms (may be NULL): device milliseconds of the call, copies included.
+ * The device concatenates the edges, then the reads, and runs the doubling rounds of cf_monokmers.hip over both: a read window and
+ * an edge window are the same k-mer iff they fall into one class.  The sort is stable and the edges lie in front, so a class is
+ * indexed iff its first record is an edge position and its second, if any, a read position.  Then streaming passes: the edge
+ * position to every read record of an indexed class, (e, j) by binary search in the offsets, hit flags, a scan and a compaction,
+ * run heads, a scan and a compaction into the paths, flags of broken joins and a scan, one pass over the reads.  The call keeps
+ * nothing on the device.  Nothing is added to cf_times or cf_stats.  Errors (-22: k < 1, null pointers where a count is positive,
+ * offsets that do not ascend or are negative, N >= 2^31, a gap outside 0 .. 255, counts outside 0 .. 2^31 - 1) are raised before
+ * anything is allocated and leave the context, the results of the call before and hbm_bytes_live as they were.  -12: no host
+ * memory for the results (52 bytes per read, 4 per path element, 12 per kept hit); the results of the call before stay as well.
+ * cf_monomap_get: the last run's paths as a CSR over the reads — path_ptr[R + 1] and the edge indices (path_cap >= their number) —
+ * and, when it kept them, the hits: hit_ptr[R + 1] and the hits (hit_cap >= their number).  Every pointer may be NULL; *n_path and
+ * *n_hits (-1: no hits kept) give the sizes.  Refused (-22) before any run.
+ * cf_monomap_info: the shape constants the tests straddle and the last run's figures: n_edge_windows = the valid edge windows,
+ * n_indexed = the indexed k-mers, n_rounds and n_sorts as for cf_monokmers_info.  phase_ms: copies to and from the device, the sorts,
+ * everything else, the whole call; by HIP events. */
+typedef struct cf_monomap_read {
+    int32_t n_hits, e0, j0, i0, e1, j1, i1, valid, n_path;
+} cf_monomap_read;
+typedef struct cf_monomap_hit {
+    int32_t e, j, i;
+} cf_monomap_hit;
+typedef struct cf_monomap_shape {
+    int64_t sort_tile, scan_tile;         /* records per tile of the record sort; values per tile of the scan           */
+    int64_t block, launch_cap;            /* threads per workgroup of the streaming passes; their workgroups at most    */
+    int64_t n_edges, n_reads, k, with_hits; /* of the last run                                                          */
+    int64_t n_edge_letters, n_read_letters, n_edge_windows, n_indexed, n_hits, n_path, n_rounds, n_sorts;
+    float phase_ms[4];
+} cf_monomap_shape;
+int cf_monomap_run(cf_ctx* ctx, const uint8_t* edge_bytes, const int64_t* edge_off, const int32_t* u, const int32_t* v, int64_t n_edges,
+                   const uint8_t* read_bytes, const int64_t* read_off, int64_t n_reads, int64_t k, int32_t gap, int32_t with_hits,
+                   cf_monomap_read* reads, float* ms);
+int cf_monomap_get(cf_ctx* ctx, int64_t* path_ptr, int32_t* path, int64_t path_cap, int64_t* n_path, int64_t* hit_ptr, cf_monomap_hit* hits,
+                   int64_t hit_cap, int64_t* n_hits);
+int cf_monomap_info(cf_ctx* ctx, cf_monomap_shape* out);
+
 int cf_get_stats(cf_ctx* ctx, cf_stats* out);
 int cf_get_times(cf_ctx* ctx, cf_times* out);
 
