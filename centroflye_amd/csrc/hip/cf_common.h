@@ -48,6 +48,16 @@ __device__ __forceinline__ uint32_t cf_base2(uint32_t c) { return ((c >> 1) ^ (c
 // the device paths skip it (what the reference does with such windows: centroflye_amd/_host.py exotic_summary)
 __device__ __forceinline__ bool cf_is_acgt(uint32_t c) { const uint32_t x = c - 0x41u; return x < 20u && ((0x80045u >> x) & 1u); }
 __device__ __forceinline__ bool cf_is_acgt_nocase(uint32_t c) { return cf_is_acgt(c & 0xDFu); }
+// the string that holds the absolute position p of a concatenation with the offsets off[0 .. n_strings]: the s with
+// off[s] <= p < off[s + 1] (empty strings hold nothing)
+__device__ __forceinline__ int64_t cf_string_of(const int64_t* __restrict__ off, int64_t n_strings, int64_t p) {
+    int64_t lo = 0, hi = n_strings;      // off[lo] <= p < off[hi]
+    while (hi - lo > 1) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (off[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
 
 // bit 63 marks an occupied slot in every k-mer keyed table (k <= 31 -> key < 2^62)
 #define CF_OCC (1ull << 63)

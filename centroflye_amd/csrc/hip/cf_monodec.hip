@@ -6,10 +6,9 @@
 // is NO reference function behind it and it is NOT String Decomposer: the rule is written out at cf_monodec_run in include/cfhip.h
 // and restated in tests/monodeccheck.py.
 //
-//   cf_md_kernel<MOVES>   ONE WORKGROUP PER PAIR (read, strand), pairs taken by a ticket in descending number of rows.  The monomers
-//                         stand side by side as L = sum of their lengths columns; thread t holds the columns 16 t .. 16 t + 15 of the
-//                         current row in registers (256 threads x 16 = 4 096 columns; a launch takes the multiple of 64 threads that
-//                         holds L), the read goes through LDS in chunks of 1 024 bytes.  A row is
+//   cf_md_kernel<MOVES>   The frame is that of cf_rowdp.h (a workgroup per pair, 16 columns per thread, the read through LDS, the two
+//                         passes, the packed moves, the walk by runs of diagonals); the monomers stand side by side as L = sum of
+//                         their lengths columns.  A row is
 //                         (1) the element-wise step A = max(diagonal, vertical): the diagonal input of a monomer's first column is
 //                             the block-uniform E[i - 1], that of a thread's first column otherwise the final value of its left
 //                             neighbour's last column, which the thread knows from its own carry of the row before;
@@ -21,38 +20,26 @@
 //                             carry-in applied to the columns in front of the thread's first start;
 //                         (3) E[i] = max(the largest V' of an end column, E[i - 1] - G): a wave reduction by lane exchanges, the
 //                             wave maxima through LDS [barrier 2]; then V = max(V', E[i] - (j + 1) G), the fed-back term.
-//                         Two LDS-only barriers per row, as in cf_ualign.hip.  No value is clamped: every value a cell takes lies
-//                         in [-(n + L + 1) max(M, X, G), n M], which the host keeps inside int32; what a lane computes and then
-//                         throws away (a carry across a monomer start) may wrap and is subtracted without signed overflow.
-//                         MOVES = false (score pass): E[n] goes out.  Nothing is stored per cell.
-//                         MOVES = true (moves pass, the winning strand): a thread packs the moves of its 16 cells (1 rule a, 2 rule b,
-//                         3 rule c) into one word; the row's words are one coalesced store to the pair's area: word (i - 1) (RW + 1)
-//                         + t, RW = ceil(L / 16); word RW of the row holds the boundary's entry: the smallest end column whose V
-//                         equals E[i], or -1 (the reduction of (3) carries the column next to the value).  Wave 0 then walks back
-//                         from boundary n, a run of diagonal moves per round, and writes one record per instance (last first;
-//                         the host turns them round) to the pair's own room, then moves them to the batch's dense list.
-//   Every loop is bounded by the rows of the pair, the block, or the walk's cap 2 n + floor(n M / G) + 4 rounds (the path scores at
-//   least -n G, so it has at most n + n M / G deleted columns next to its at most n read bytes).  The only atomics are the ticket and,
-//   once per pair of the moves pass, the cursor of the batch's dense list of records (ticket[1]).
-#include "cf_common.h"
+//                         No value is clamped: every value a cell takes lies in [-(n + L + 1) max(M, X, G), n M], which the host
+//                         keeps inside int32; what a lane computes and then throws away (a carry across a monomer start) may wrap
+//                         and is subtracted without signed overflow.
+//                         MOVES = false (score pass): E[n] goes out.
+//                         MOVES = true (moves pass): the moves are 1 rule a, 2 rule b, 3 rule c; a row of the area has RW + 1 words,
+//                         RW = ceil(L / 16); word RW of the row holds the boundary's entry: the smallest end column whose V equals
+//                         E[i], or -1 (the reduction of (3) carries the column next to the value).  The walk goes back from
+//                         boundary n and writes one record per instance (last first; the host turns them round) to the pair's own
+//                         room, then moves them to the batch's dense list.
+//   The walk's cap is 2 n + floor(n M / G) + 4 rounds (the path scores at least -n G, so it has at most n + n M / G deleted columns
+//   next to its at most n read bytes).  The only atomics are the ticket and, once per pair of the moves pass, the cursor of the
+//   batch's dense list of records (ticket[1]).
+#include "cf_rowdp.h"
 
-#define CF_MD_MAX_COLS 4096
-#define CF_MD_CPT 16                   // columns of a row per thread
-#define CF_MD_BLOCK 256
-#define CF_MD_WGS_PER_CU 8
-#define CF_MD_CHUNK 1024               // read bytes staged in LDS at a time
-// LDS window: the ticket, the wave totals [2][4], the wave flags [4], the end-column maxima [2][4] (8 bytes each), the read chunk
-#define CF_MD_LDS_TOT 16
+// LDS window behind the wave totals: the wave flags [4], the end-column maxima [2][4] (8 bytes each), the read chunk
 #define CF_MD_LDS_FLAG 48
 #define CF_MD_LDS_END 64
 #define CF_MD_LDS_READ 128
-#define CF_MD_LDS_BYTES (CF_MD_LDS_READ + CF_MD_CHUNK)
+#define CF_MD_LDS_BYTES (CF_MD_LDS_READ + CF_RD_CHUNK)
 #define CF_MD_NEG ((int32_t)0x80000000)
-
-#ifndef cf_barrier_lds
-// workgroup barrier that orders LDS traffic only: the stores of the move words need not have landed before the next row
-__device__ __forceinline__ void cf_barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-#endif
 
 struct cf_md_pair {
     int64_t r_begin;             // first byte of the read
@@ -63,44 +50,37 @@ struct cf_md_pair {
     int32_t strand;
 };
 
-__device__ __forceinline__ int32_t cf_md_sat(int64_t x) { return x < (int64_t)0x7fffffff ? (int32_t)x : 0x7fffffff; }
-__device__ __forceinline__ int32_t cf_md_max(int32_t a, int32_t b) { return a > b ? a : b; }
-// a - b modulo 2^32: the result is used only where the true difference fits
-__device__ __forceinline__ int32_t cf_md_sub(int32_t a, int32_t b) { return (int32_t)((uint32_t)a - (uint32_t)b); }
-
 template <bool MOVES>
-__global__ void __launch_bounds__(CF_MD_BLOCK)
+__global__ void __launch_bounds__(CF_RD_BLOCK)
 cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_t* __restrict__ reads, const uint8_t* __restrict__ monos,
              const int32_t* __restrict__ colj, const int32_t* __restrict__ colk, int32_t L, int32_t M, int32_t X, int32_t G,
              int32_t* __restrict__ out, uint32_t* __restrict__ area, int32_t* __restrict__ recs, int32_t* __restrict__ dense,
              unsigned long long* __restrict__ ticket, int32_t* __restrict__ fault) {
-    volatile int64_t* head = (volatile int64_t*)cf_lds;
-    volatile int32_t* tot = (volatile int32_t*)(cf_lds + CF_MD_LDS_TOT);
+    volatile int32_t* tot = (volatile int32_t*)(cf_lds + CF_RD_LDS_TOT);
     volatile int32_t* wflag = (volatile int32_t*)(cf_lds + CF_MD_LDS_FLAG);
     volatile int64_t* wend = (volatile int64_t*)(cf_lds + CF_MD_LDS_END);
     volatile int32_t* wend32 = (volatile int32_t*)(cf_lds + CF_MD_LDS_END);      // the score pass's maxima carry no column
     volatile uint8_t* lr = (volatile uint8_t*)(cf_lds + CF_MD_LDS_READ);
     const int tid = threadIdx.x, nth = blockDim.x, lane = tid & 63, wave = tid >> 6, n_waves = nth >> 6;
-    const int32_t j0 = tid * CF_MD_CPT;
-    const int32_t RW = (L + CF_MD_CPT - 1) / CF_MD_CPT, RW1 = RW + 1;
+    const int32_t j0 = tid * CF_RD_CPT;
+    const int32_t RW = (L + CF_RD_CPT - 1) / CF_RD_CPT, RW1 = RW + 1;
     // where the monomers start and end among this thread's columns (a column beyond L is a monomer of its own that ends nowhere)
     uint32_t stmask = 0, endmask = 0;
 #pragma unroll
-    for (int k = 0; k < CF_MD_CPT; ++k) {
+    for (int k = 0; k < CF_RD_CPT; ++k) {
         const int32_t c = j0 + k;
         if (c >= L || colj[c] == 0) stmask |= 1u << k;
         if (c < L && (c == L - 1 || colj[c + 1] == 0)) endmask |= 1u << k;
     }
-    const int32_t fs = stmask ? (int32_t)__ffs((int)stmask) - 1 : CF_MD_CPT;      // the columns in front of it take the carry-in
+    const int32_t fs = stmask ? (int32_t)__ffs((int)stmask) - 1 : CF_RD_CPT;      // the columns in front of it take the carry-in
     const int32_t jfirst = j0 < L ? colj[j0] : 0;                                  // the first column's index in its monomer
     const int32_t jleft = (tid > 0 && j0 - 1 < L) ? colj[j0 - 1] : 0;              // ... and that of the left neighbour's last column
-    const int32_t gfirst = cf_md_sat((int64_t)G * jfirst), gleft = cf_md_sat((int64_t)G * (jleft + 1));
-    int32_t gsh[6];
+    const int32_t gfirst = cf_rd_gap(G, jfirst), gleft = cf_rd_gap(G, jleft + 1);
+    int32_t gsh[6], gw[3];
 #pragma unroll
-    for (int s = 0; s < 6; ++s) gsh[s] = cf_md_sat((int64_t)G * CF_MD_CPT * (1 << s));
-    int32_t gw[3];                                                // from the last column of wave w to the column in front of this thread
+    for (int s = 0; s < 6; ++s) gsh[s] = cf_rd_gap(G, CF_RD_CPT << s);
 #pragma unroll
-    for (int w = 0; w < 3; ++w) gw[w] = cf_md_sat((int64_t)G * (j0 > 1024 * (w + 1) ? j0 - 1024 * (w + 1) : 0));
+    for (int w = 0; w < 3; ++w) gw[w] = cf_rd_gap(G, j0 > 1024 * (w + 1) ? j0 - 1024 * (w + 1) : 0);
     // the flags of the segmented scan, once: bit s of `use` = this lane takes the wave scan's step s; bit w of `wuse` = the carry-in
     // takes the total of wave w
     uint32_t use = 0, wuse = 0;
@@ -124,22 +104,17 @@ cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_
         }
     }
     for (;;) {
-        if (tid == 0) {
-            const unsigned long long x = atomicAdd(ticket, 1ull);
-            head[0] = x < (unsigned long long)n_pairs ? (int64_t)x : -1;
-        }
-        __syncthreads();
-        const int64_t idx = head[0];
+        const int64_t idx = cf_rd_take(ticket, n_pairs);
         if (idx < 0) break;
         const cf_md_pair pr = pairs[idx];
         const uint8_t* __restrict__ gu = monos + (pr.strand ? L : 0);
         const uint8_t* __restrict__ gr = reads + pr.r_begin;
         uint32_t* __restrict__ mv_area = area + (MOVES ? pr.area_off : 0);
         const int32_t n_rows = pr.n_rows;
-        uint32_t ub[CF_MD_CPT];      // 0xFF beyond L: no upper-cased byte equals it
-        int32_t S[CF_MD_CPT];
+        uint32_t ub[CF_RD_CPT];      // 0xFF beyond L: no upper-cased byte equals it
+        int32_t S[CF_RD_CPT];
 #pragma unroll
-        for (int k = 0; k < CF_MD_CPT; ++k) {
+        for (int k = 0; k < CF_RD_CPT; ++k) {
             const int32_t c = j0 + k;
             ub[k] = c < L ? (uint32_t)gu[c] : 0xFFu;
             S[k] = c < L ? -G * (colj[c] + 1) : -G;      // V[0][k][j] = -(j + 1) G
@@ -147,23 +122,18 @@ cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_
         int32_t left = -gleft;                // V[i - 1] of the column in front of this thread's first
         int32_t Eprev = 0;                    // E[i - 1]
         for (int32_t i = 1; i <= n_rows; ++i) {
-            if (((i - 1) & (CF_MD_CHUNK - 1)) == 0) {
-                // (every thread read its byte of the chunk before in front of barrier 1 of the row before)
-                for (int32_t x = tid; x < CF_MD_CHUNK && i - 1 + x < n_rows; x += nth) lr[x] = gr[i - 1 + x];
-                __syncthreads();
-            }
-            const uint32_t rb = (uint32_t)lr[(i - 1) & (CF_MD_CHUNK - 1)] & 0xDFu;      // bit 5 cleared: a, c, g, t meet A, C, G, T; no other byte does
+            const uint32_t rb = cf_rd_row_byte(lr, gr, i, n_rows, tid, nth);
             const int buf = i & 1;
             // (1) element-wise, and the serial scan of this thread's columns
-            int32_t P[CF_MD_CPT];
+            int32_t P[CF_RD_CPT];
             int32_t dprev = left, run = 0;
 #pragma unroll
-            for (int k = 0; k < CF_MD_CPT; ++k) {
+            for (int k = 0; k < CF_RD_CPT; ++k) {
                 const bool st = (stmask >> k) & 1u;
                 const int32_t d = (st ? Eprev : dprev) + (rb == ub[k] ? M : -X), v = S[k] - G;
                 dprev = S[k];
-                const int32_t a = cf_md_max(d, v);
-                run = (k == 0 || st) ? a : cf_md_max(a, run - G);
+                const int32_t a = cf_rd_max(d, v);
+                run = (k == 0 || st) ? a : cf_rd_max(a, run - G);
                 P[k] = run;
             }
             // (2) the thread totals across the wave: T = the scan's value at this thread's last column, from this wave's columns
@@ -171,7 +141,7 @@ cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_
 #pragma unroll
             for (int s = 0; s < 6; ++s) {
                 const int32_t o = __shfl_up(T, 1u << s);
-                if ((use >> s) & 1u) T = cf_md_max(T, cf_md_sub(o, gsh[s]));
+                if ((use >> s) & 1u) T = cf_rd_max(T, cf_rd_sub(o, gsh[s]));
             }
             int32_t cin = __shfl_up(T, 1u);      // ... at the column in front of this thread's first
             if (lane == 0) cin = CF_MD_NEG;
@@ -179,12 +149,12 @@ cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_
             cf_barrier_lds();
 #pragma unroll
             for (int w = 2; w >= 0; --w)
-                if ((wuse >> w) & 1u) cin = cf_md_max(cin, cf_md_sub(tot[buf * 4 + w], gw[w]));
+                if ((wuse >> w) & 1u) cin = cf_rd_max(cin, cf_rd_sub(tot[buf * 4 + w], gw[w]));
             int32_t c = cin;
 #pragma unroll
-            for (int k = 0; k < CF_MD_CPT; ++k) {
-                c = cf_md_sub(c, G);
-                if (k < fs) P[k] = cf_md_max(P[k], c);      // P = V'
+            for (int k = 0; k < CF_RD_CPT; ++k) {
+                c = cf_rd_sub(c, G);
+                if (k < fs) P[k] = cf_rd_max(P[k], c);      // P = V'
             }
             // (3) E[i] from the end columns
             int32_t Ei, kstar = -1;
@@ -192,7 +162,7 @@ cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_
                 // the value above the column, the column counted down: the largest key is the largest value at the smallest column
                 int32_t ev = CF_MD_NEG, ec = 0;      // this thread's largest end-column value, at its smallest column
 #pragma unroll
-                for (int k = CF_MD_CPT - 1; k >= 0; --k)
+                for (int k = CF_RD_CPT - 1; k >= 0; --k)
                     if (((endmask >> k) & 1u) && P[k] >= ev) { ev = P[k]; ec = j0 + k; }
                 int64_t em = endmask ? (int64_t)ev * 4294967296ll + (int64_t)(0x7fffffff - ec) : INT64_MIN;
 #pragma unroll
@@ -208,42 +178,41 @@ cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_
                     best = o > best ? o : best;
                 }
                 const int32_t hi = (int32_t)(best >> 32);
-                Ei = cf_md_max(hi, Eprev - G);
+                Ei = cf_rd_max(hi, Eprev - G);
                 if (hi == Ei) kstar = 0x7fffffff - (int32_t)(uint32_t)(best & 0xffffffffll);
             } else {
                 int32_t em = CF_MD_NEG;
 #pragma unroll
-                for (int k = 0; k < CF_MD_CPT; ++k)
-                    if ((endmask >> k) & 1u) em = cf_md_max(em, P[k]);
+                for (int k = 0; k < CF_RD_CPT; ++k)
+                    if ((endmask >> k) & 1u) em = cf_rd_max(em, P[k]);
 #pragma unroll
-                for (int s = 0; s < 6; ++s) em = cf_md_max(em, __shfl_xor(em, 1 << s));
+                for (int s = 0; s < 6; ++s) em = cf_rd_max(em, __shfl_xor(em, 1 << s));
                 if (lane == 0) wend32[buf * 4 + wave] = em;
                 cf_barrier_lds();
                 Ei = Eprev - G;
-                for (int w = 0; w < n_waves; ++w) Ei = cf_md_max(Ei, wend32[buf * 4 + w]);
+                for (int w = 0; w < n_waves; ++w) Ei = cf_rd_max(Ei, wend32[buf * 4 + w]);
             }
             // V = max(V', E[i] - (j + 1) G), and the moves
             int32_t fb = Ei - gfirst;
             uint32_t word = 0;
             dprev = left;
 #pragma unroll
-            for (int k = 0; k < CF_MD_CPT; ++k) {
+            for (int k = 0; k < CF_RD_CPT; ++k) {
                 const bool st = (stmask >> k) & 1u;
                 fb = st ? Ei - G : fb - G;
-                const int32_t s_new = cf_md_max(P[k], fb);
+                const int32_t s_new = cf_rd_max(P[k], fb);
                 if (MOVES) {
                     const int32_t d = (st ? Eprev : dprev) + (rb == ub[k] ? M : -X), v = S[k] - G;
                     dprev = S[k];
-                    const uint32_t mv = d == s_new ? 1u : (v == s_new ? 2u : 3u);
-                    word |= mv << (2 * k);
+                    word = cf_rd_pack(word, d == s_new ? 1u : (v == s_new ? 2u : 3u), k);
                 }
                 S[k] = s_new;
             }
-            left = cf_md_max(cin, Ei - gleft);
+            left = cf_rd_max(cin, Ei - gleft);
             Eprev = Ei;
             if (MOVES) {
-                if (tid < RW) mv_area[(int64_t)(i - 1) * RW1 + tid] = word;
-                if (tid == 0) mv_area[(int64_t)(i - 1) * RW1 + RW] = (uint32_t)kstar;
+                if (tid < RW) cf_rd_row(mv_area, i, RW1)[tid] = word;
+                if (tid == 0) cf_rd_row(mv_area, i, RW1)[RW] = (uint32_t)kstar;
             }
         }
         if (!MOVES) {
@@ -251,16 +220,15 @@ cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_
         } else {
             __syncthreads();      // every move word of the pair is visible to the walking wave
             if (wave == 0) {
-                // Nearly every move is a diagonal: lane l looks at the cell l diagonal steps back from (i, j) inside the instance, the
-                // leading run of diagonal moves is taken in one round, then the one move that ended it.  Every value below is the
-                // same in all lanes.
+                // Nearly every move is a diagonal, so a round takes a run of them: lane l looks l diagonal steps back from (i, j)
+                // inside the instance.  Every value below is the same in all lanes.
                 int32_t* pr_rec = recs + 7 * pr.rec_off;
                 int32_t i = n_rows, j = 0, c = 0, k_in = 0, i_in = 0, n_inst = 0, prefix = 0, cnt0 = 0, cnt1 = 0, cnt2 = 0, cnt3 = 0;
                 bool inside = false, done = false;
                 for (int64_t round = 0; round <= pr.round_cap; ++round) {      // a round takes at least one column or ends the walk
                     if (!inside) {
                         if (i == 0) { done = true; break; }
-                        const int32_t ks = (int32_t)mv_area[(int64_t)(i - 1) * RW1 + RW];
+                        const int32_t ks = (int32_t)cf_rd_row(mv_area, i, RW1)[RW];
                         if (ks < 0) { prefix = i; done = true; break; }      // unassigned bases are a prefix of the read
                         if (ks >= L || n_inst >= n_rows) break;
                         c = ks; j = colj[ks]; k_in = colk[ks]; i_in = i; inside = true;
@@ -268,12 +236,11 @@ cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_
                     }
                     const int32_t il = i - lane, jl = j - lane, cl = c - lane;
                     uint32_t mv = 0u;
-                    if (il >= 1 && jl >= 0) mv = (mv_area[(int64_t)(il - 1) * RW1 + (cl >> 4)] >> (2 * (cl & 15))) & 3u;
-                    const unsigned long long diag = __ballot(mv == 1u);
-                    const int32_t run = diag == ~0ull ? 64 : (int32_t)__builtin_ctzll(~diag);
+                    if (il >= 1 && jl >= 0) mv = cf_rd_move(mv_area, il, RW1, cl);
+                    const int32_t run = cf_rd_diag_len(mv);
                     bool is_match = false;
-                    if (lane < run) is_match = ((uint32_t)gr[il - 1] & 0xDFu) == (uint32_t)gu[cl];
-                    const int32_t n_match = (int32_t)__popcll(__ballot(is_match));
+                    if (lane < run) is_match = cf_rd_match(gr, il, gu, cl);
+                    const int32_t n_match = cf_rd_count(is_match);
                     const uint32_t end = (uint32_t)__shfl((int)mv, run & 63);      // the move of the cell the run stopped at
                     cnt0 += n_match; cnt1 += run - n_match; i -= run; j -= run; c -= run;
                     bool emit = false;
@@ -308,26 +275,95 @@ cf_md_kernel(const cf_md_pair* __restrict__ pairs, int64_t n_pairs, const uint8_
     }
 }
 
-// move areas per batch unless the knob says otherwise: an eighth of the device's memory, 2^28 .. 2^34 bytes (a launch should have a
-// workgroup for every CU: a pair of 20 000 x 3 065 takes 15 MB)
-static int64_t cf_md_batch_bytes(const cf_ctx* ctx) {
-    if (ctx->monodec_batch_bytes > 0) return ctx->monodec_batch_bytes;
-    return std::min<int64_t>(std::max<int64_t>(ctx->hbm_total / 8, (int64_t)1 << 28), (int64_t)1 << 34);
-}
-static int cf_md_launch_cap(const cf_ctx* ctx) { return std::max(1, ctx->n_cu) * CF_MD_WGS_PER_CU; }
-static int cf_md_block_for(int32_t L) { return std::min(CF_MD_BLOCK, (((L + CF_MD_CPT - 1) / CF_MD_CPT + 63) / 64) * 64); }
+// what cf_rd_run (cf_rowdp.h) asks of the stage
+struct cf_md_stage {
+    typedef cf_md_pair pair;
+    typedef cf_monodec_inst item;
+    struct win { int64_t q; int32_t strand, score, rows; int64_t words, rounds, room; };      // room: records, one per read byte (an instance takes at least one)
+    static constexpr const char *name = "monodec", *kernel = "cf_md_kernel", *fault = "cf_monodec_run: a walk did not end inside its bounds (internal error)";
+    static constexpr int score_words = 1;
+    const uint8_t* mono;
+    const int64_t* mono_off;
+    int32_t n_monomers, L, M, X, G;
+    std::vector<cf_monodec_read> info;
+    uint8_t* d_monos = nullptr;
+    int32_t *d_colj = nullptr, *d_colk = nullptr, *d_recs = nullptr, *d_dense = nullptr, *d_res = nullptr;
+    unsigned long long n_dense = 0;
+    std::vector<int32_t> res, recs;
+
+    // both strands of the monomers, every monomer turned round in its own place; the column tables
+    int upload(cf_ctx* ctx, cf_scratch& tmp) {
+        std::vector<uint8_t> h_monos((size_t)2 * L);
+        std::vector<int32_t> h_colj((size_t)L), h_colk((size_t)L);
+        for (int32_t k = 0; k < n_monomers; ++k) {
+            const int32_t b = (int32_t)(mono_off[k] - mono_off[0]), len = (int32_t)(mono_off[k + 1] - mono_off[k]);
+            cf_rd_both_strands(mono + b, len, &h_monos[(size_t)b], &h_monos[(size_t)L + b]);
+            for (int32_t j = 0; j < len; ++j) {
+                h_colj[(size_t)b + j] = j;
+                h_colk[(size_t)b + j] = k;
+            }
+        }
+        CF_TRY(tmp.get(&d_monos, (size_t)2 * L + 16, "monodec monomers"));
+        CF_TRY(tmp.get(&d_colj, (size_t)L + 1, "monodec column table"));
+        CF_TRY(tmp.get(&d_colk, (size_t)L + 1, "monodec monomer table"));
+        CF_TRY(cf_copy_h2d(ctx, d_monos, h_monos.data(), (size_t)2 * L));
+        CF_TRY(cf_copy_h2d(ctx, d_colj, h_colj.data(), (size_t)L * 4));
+        return cf_copy_h2d(ctx, d_colk, h_colk.data(), (size_t)L * 4);
+    }
+    pair score_pair(int64_t r_begin, int32_t n, int s) const { return pair{r_begin, 0, 0, 0, n, s}; }
+    pair move_pair(const win& w, int64_t r_begin, int64_t area_off, int64_t rec_off) const { return pair{r_begin, area_off, rec_off, w.rounds, w.rows, w.strand}; }
+    template <bool MOVES> void launch(cf_ctx* ctx, unsigned grid, const pair* p, int64_t n, const cf_rd_dev& d) const {
+        hipLaunchKernelGGL(cf_md_kernel<MOVES>, dim3(grid), dim3((unsigned)cf_rd_block_for(L)), CF_MD_LDS_BYTES, ctx->stream, p, n, d.reads, (const uint8_t*)d_monos,
+                           (const int32_t*)d_colj, (const int32_t*)d_colk, L, M, X, G, MOVES ? d_res : d.score, d.area, d_recs, d_dense, d.ticket, d.fault);      // (no area and no records in the score pass)
+    }
+    // the winning strand of every read ("+" on a tie)
+    int pick(cf_ctx*, int64_t q, int32_t n, const int32_t* f, std::vector<win>& wins) const {
+        const int s = f[1] > f[0] ? 1 : 0;
+        wins.push_back(win{q, s, f[s], n, (int64_t)n * (cf_rd_row_words(L) + 1), 2 * (int64_t)n + (int64_t)n * M / G + 4, n});
+        return 0;
+    }
+    int batch_get(cf_scratch& tmp, int64_t n2, int64_t n_rec) {
+        CF_TRY(tmp.get(&d_recs, (size_t)7 * n_rec + 8, "monodec instances"));
+        CF_TRY(tmp.get(&d_dense, (size_t)7 * n_rec + 8, "monodec dense instances"));
+        return tmp.get(&d_res, (size_t)4 * n2, "monodec walk results");
+    }
+    int fetch(cf_ctx* ctx, const cf_rd_dev& d, int64_t n2, int64_t n_rec) {
+        CF_TRY(cf_copy_d2h(ctx, &n_dense, d.ticket + 1, 8));
+        if (n_dense > (unsigned long long)n_rec) return cf_fail(ctx, -5, "cf_monodec_run: more instances than read bytes (internal error)");
+        res.resize((size_t)4 * n2);
+        recs.resize((size_t)7 * n_dense + 8);
+        CF_TRY(cf_copy_d2h(ctx, res.data(), d_res, (size_t)4 * n2 * 4));
+        return n_dense > 0 ? cf_copy_d2h(ctx, recs.data(), d_dense, (size_t)7 * n_dense * 4) : 0;
+    }
+    int unpack(cf_ctx* ctx, const win* wins, const pair*, int64_t n2, std::vector<cf_monodec_inst>* per_read) {
+        for (int64_t x = 0; x < n2; ++x) {
+            const win& w = wins[x];
+            const int32_t n_inst = res[(size_t)4 * x], prefix = res[(size_t)4 * x + 1];
+            const int64_t base = (int64_t)(uint32_t)res[(size_t)4 * x + 2] | ((int64_t)res[(size_t)4 * x + 3] << 32);
+            if (n_inst < 0 || n_inst > w.rows || base < 0 || base + n_inst > (int64_t)n_dense)
+                return cf_fail(ctx, -5, "cf_monodec_run: a pair's instances lie outside the batch's list (internal error)");
+            info[(size_t)w.q] = cf_monodec_read{CF_MONODEC_DONE, w.strand, w.score, n_inst, prefix};
+            per_read[x].resize((size_t)n_inst);
+            for (int32_t a = 0; a < n_inst; ++a) {      // the walk wrote the last instance first
+                const int32_t* r = &recs[(size_t)7 * (base + (n_inst - 1 - a))];
+                per_read[x][(size_t)a] = cf_monodec_inst{r[0], r[1], r[2], r[3], r[4], r[5], r[6]};
+            }
+        }
+        return 0;
+    }
+};
 
 extern "C" {
 
 int cf_monodec_info(cf_ctx* ctx, cf_monodec_shape* out) {
     if (!ctx || !out) return -22;
     *out = ctx->monodec_last;
-    out->max_cols = CF_MD_MAX_COLS;
-    out->cols_per_thread = CF_MD_CPT;
-    out->block = CF_MD_BLOCK;
-    out->row_chunk = CF_MD_CHUNK;
-    out->launch_cap = cf_md_launch_cap(ctx);
-    out->batch_bytes = cf_md_batch_bytes(ctx);
+    out->max_cols = CF_RD_MAX_COLS;
+    out->cols_per_thread = CF_RD_CPT;
+    out->block = CF_RD_BLOCK;
+    out->row_chunk = CF_RD_CHUNK;
+    out->launch_cap = cf_rd_launch_cap(ctx);
+    out->batch_bytes = cf_rd_batch_bytes(ctx, ctx->monodec_batch_bytes);
     return 0;
 }
 
@@ -349,14 +385,14 @@ int cf_monodec_run(cf_ctx* ctx, const uint8_t* monomers, const int64_t* mono_off
     if (ms_out) *ms_out = 0.f;
     if (n_reads < 0 || n_reads >= (int64_t)1 << 30) return cf_fail(ctx, -22, "cf_monodec_run: the number of reads is outside 0 .. 2^30 - 1");
     if (n_monomers < 1) return cf_fail(ctx, -22, "cf_monodec_run: no monomer");
-    if (n_monomers > CF_MD_MAX_COLS)
-        return cf_fail(ctx, -22, "cf_monodec_run: " + std::to_string(n_monomers) + " monomers have more than " + std::to_string(CF_MD_MAX_COLS) + " bases");
+    if (n_monomers > CF_RD_MAX_COLS)
+        return cf_fail(ctx, -22, "cf_monodec_run: " + std::to_string(n_monomers) + " monomers have more than " + std::to_string(CF_RD_MAX_COLS) + " bases");
     if (!monomers || !mono_off || !read_off || (n_reads > 0 && !info)) return cf_fail(ctx, -22, "cf_monodec_run: null pointer");
     if (mono_off[0] < 0) return cf_fail(ctx, -22, "cf_monodec_run: negative monomer offset");
     for (int32_t k = 0; k < n_monomers; ++k) {
         if (mono_off[k + 1] <= mono_off[k]) return cf_fail(ctx, -22, "cf_monodec_run: monomer " + std::to_string(k) + " is empty (or its offsets decrease)");
-        if (mono_off[k + 1] - mono_off[0] > CF_MD_MAX_COLS)
-            return cf_fail(ctx, -22, "cf_monodec_run: the monomers have more than " + std::to_string(CF_MD_MAX_COLS) + " bases in all");
+        if (mono_off[k + 1] - mono_off[0] > CF_RD_MAX_COLS)
+            return cf_fail(ctx, -22, "cf_monodec_run: the monomers have more than " + std::to_string(CF_RD_MAX_COLS) + " bases in all");
     }
     const int32_t L = (int32_t)(mono_off[n_monomers] - mono_off[0]);
     const uint8_t* mono = monomers + mono_off[0];
@@ -367,182 +403,21 @@ int cf_monodec_run(cf_ctx* ctx, const uint8_t* monomers, const int64_t* mono_off
     const int64_t worst = std::max<int64_t>(match, std::max<int64_t>(mismatch, gap));
     if (read_off[0] < 0) return cf_fail(ctx, -22, "cf_monodec_run: negative read offset");
     if ((int64_t)(L + 1) * worst >= (int64_t)1 << 31) return cf_fail(ctx, -22, "cf_monodec_run: (L + 1) max(M, X, G) is 2^31 or more");
-    for (int64_t q = 0; q < n_reads; ++q) {
-        if (read_off[q + 1] < read_off[q]) return cf_fail(ctx, -22, "cf_monodec_run: offsets of read " + std::to_string(q) + " decrease");
-        const int64_t n = read_off[q + 1] - read_off[q];
-        if (n >= (int64_t)1 << 31 || (n + L + 1) * worst >= (int64_t)1 << 31)
-            return cf_fail(ctx, -22, "cf_monodec_run: read " + std::to_string(q) + " of " + std::to_string(n) + " bytes: (n + L + 1) max(M, X, G) is 2^31 or more");
-    }
-    const int64_t r_total = read_off[n_reads] - read_off[0];
-    if (r_total > 0 && !reads) return cf_fail(ctx, -22, "cf_monodec_run: null bytes");
+    // (n + L + 1) worst < 2^31 holds up to n = ceil(2^31 / worst) - L - 2
+    CF_TRY(cf_rd_check_reads(ctx, "cf_monodec_run", reads, read_off, n_reads, (((int64_t)1 << 31) + worst - 1) / worst - L - 1, ": (n + L + 1) max(M, X, G) is 2^31 or more"));
 
     // the results of this call, handed to the context only when everything worked
-    std::vector<cf_monodec_read> res_info((size_t)n_reads, cf_monodec_read{});
-    std::vector<int64_t> res_ptr((size_t)n_reads + 1, 0);
+    cf_md_stage st{mono, mono_off, n_monomers, L, match, mismatch, gap, std::vector<cf_monodec_read>((size_t)n_reads, cf_monodec_read{})};
+    std::vector<int64_t> res_ptr;
     std::vector<cf_monodec_inst> res_inst;
     cf_monodec_shape shape{};
     shape.n_reads = n_reads;
     shape.n_monomers = n_monomers;
     shape.n_cols = L;
-
-    // both strands of the monomers, every monomer turned round in its own place; the column tables
-    std::vector<uint8_t> h_monos((size_t)2 * L);
-    std::vector<int32_t> h_colj((size_t)L), h_colk((size_t)L);
-    for (int32_t k = 0; k < n_monomers; ++k) {
-        const int32_t b = (int32_t)(mono_off[k] - mono_off[0]), len = (int32_t)(mono_off[k + 1] - mono_off[k]);
-        for (int32_t j = 0; j < len; ++j) {
-            const uint8_t x = mono[b + len - 1 - j];
-            h_monos[(size_t)b + j] = mono[b + j];
-            h_monos[(size_t)L + b + j] = x == 'A' ? 'T' : x == 'C' ? 'G' : x == 'G' ? 'C' : 'A';
-            h_colj[(size_t)b + j] = j;
-            h_colk[(size_t)b + j] = k;
-        }
-    }
-    std::vector<int64_t> by_len;
-    for (int64_t q = 0; q < n_reads; ++q)
-        if (read_off[q + 1] > read_off[q]) by_len.push_back(q);
-    std::stable_sort(by_len.begin(), by_len.end(), [&](int64_t x, int64_t y) { return read_off[x + 1] - read_off[x] > read_off[y + 1] - read_off[y]; });
-    std::vector<cf_md_pair> p1(2 * by_len.size());
-    for (size_t o = 0; o < by_len.size(); ++o)
-        for (int s = 0; s < 2; ++s) {
-            const int64_t q = by_len[o];
-            p1[2 * o + s] = cf_md_pair{read_off[q] - read_off[0], 0, 0, 0, (int32_t)(read_off[q + 1] - read_off[q]), s};
-        }
-    const int64_t n1 = (int64_t)p1.size();
-    shape.n_score_pairs = n1;
-
-    CF_HIP(hipSetDevice(ctx->device));
-    hipEvent_t e0 = ctx->ev0, e1 = ctx->ev1, e2 = ctx->ev2;
-    float t = 0.f;
-    cf_scratch tmp(ctx);
-    uint8_t *d_reads = nullptr, *d_monos = nullptr;
-    cf_md_pair* d_p1 = nullptr;
-    int32_t *d_colj = nullptr, *d_colk = nullptr, *d_score = nullptr, *d_fault = nullptr;
-    unsigned long long* d_ticket = nullptr;
-    CF_HIP(hipEventRecord(e0, ctx->stream));
-    CF_TRY(tmp.get(&d_reads, (size_t)r_total + 16, "monodec reads"));
-    CF_TRY(tmp.get(&d_monos, (size_t)2 * L + 16, "monodec monomers"));
-    CF_TRY(tmp.get(&d_colj, (size_t)L + 1, "monodec column table"));
-    CF_TRY(tmp.get(&d_colk, (size_t)L + 1, "monodec monomer table"));
-    CF_TRY(tmp.get(&d_p1, (size_t)n1 + 1, "monodec score pairs"));
-    CF_TRY(tmp.get(&d_score, (size_t)n1 + 4, "monodec scores"));
-    CF_TRY(tmp.get(&d_fault, 1, "monodec fault flag"));
-    CF_TRY(tmp.get(&d_ticket, 2, "monodec ticket and cursor"));
-    if (r_total > 0) CF_TRY(cf_copy_h2d(ctx, d_reads, reads + read_off[0], (size_t)r_total));
-    CF_TRY(cf_copy_h2d(ctx, d_monos, h_monos.data(), (size_t)2 * L));
-    CF_TRY(cf_copy_h2d(ctx, d_colj, h_colj.data(), (size_t)L * 4));
-    CF_TRY(cf_copy_h2d(ctx, d_colk, h_colk.data(), (size_t)L * 4));
-    if (n1 > 0) CF_TRY(cf_copy_h2d(ctx, d_p1, p1.data(), (size_t)n1 * sizeof(cf_md_pair)));
-    CF_HIP(hipMemsetAsync(d_fault, 0, 4, ctx->stream));
-    CF_HIP(hipMemsetAsync(d_ticket, 0, 16, ctx->stream));
-    CF_HIP(hipEventRecord(e1, ctx->stream));
-    const int cap = cf_md_launch_cap(ctx), block = cf_md_block_for(L);
-    if (n1 > 0) {
-        hipLaunchKernelGGL(cf_md_kernel<false>, dim3((unsigned)std::min<int64_t>(n1, cap)), dim3((unsigned)block), CF_MD_LDS_BYTES, ctx->stream,
-                           (const cf_md_pair*)d_p1, n1, (const uint8_t*)d_reads, (const uint8_t*)d_monos, (const int32_t*)d_colj, (const int32_t*)d_colk, L,
-                           match, mismatch, gap, d_score, (uint32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, d_ticket, d_fault);
-        CF_KERNEL_CHECK("cf_md_kernel (score pass)");
-    }
-    CF_HIP(hipEventRecord(e2, ctx->stream));
-    CF_HIP(hipEventSynchronize(e2));
-    (void)hipEventElapsedTime(&t, e0, e1); shape.phase_ms[0] += t;
-    (void)hipEventElapsedTime(&t, e1, e2); shape.phase_ms[1] += t;
-
-    CF_HIP(hipEventRecord(e0, ctx->stream));
-    std::vector<int32_t> score((size_t)n1 + 4);
-    if (n1 > 0) CF_TRY(cf_copy_d2h(ctx, score.data(), d_score, (size_t)n1 * 4));
-    CF_HIP(hipEventRecord(e1, ctx->stream));
-    CF_HIP(hipEventSynchronize(e1));
-    (void)hipEventElapsedTime(&t, e0, e1); shape.phase_ms[0] += t;
-
-    // the winning strand of every read ("+" on a tie); the moves pass's pairs in descending rows (by_len's order), cut into batches
-    struct win { int64_t q; int32_t strand, score, n; int64_t words, rounds; };
-    std::vector<win> wins;
-    const int64_t RW1 = (L + CF_MD_CPT - 1) / CF_MD_CPT + 1;
-    for (size_t o = 0; o < by_len.size(); ++o) {
-        const int s = score[2 * o + 1] > score[2 * o] ? 1 : 0;
-        const int64_t q = by_len[o], n = read_off[q + 1] - read_off[q];
-        wins.push_back(win{q, s, score[2 * o + s], (int32_t)n, n * RW1, 2 * n + n * (int64_t)match / gap + 4});
-    }
-    const int64_t batch_bytes = cf_md_batch_bytes(ctx);
-    shape.n_move_pairs = (int64_t)wins.size();
-    std::vector<std::vector<cf_monodec_inst>> per_read(wins.size());
-    for (size_t first = 0; first < wins.size();) {
-        size_t last = first;
-        int64_t words = 0, n_rec = 0;
-        std::vector<cf_md_pair> p2;
-        while (last < wins.size()) {
-            const win& w = wins[last];
-            if (last > first && (words + w.words) * 4 > batch_bytes) break;
-            p2.push_back(cf_md_pair{read_off[w.q] - read_off[0], words, n_rec, w.rounds, w.n, w.strand});
-            words += w.words;
-            n_rec += w.n;      // an instance takes at least one read byte
-            ++last;
-        }
-        const int64_t n2 = (int64_t)(last - first);
-        CF_HIP(hipEventRecord(e0, ctx->stream));
-        cf_scratch batch_tmp(ctx);
-        cf_md_pair* d_p2 = nullptr;
-        uint32_t* d_area = nullptr;
-        int32_t *d_recs = nullptr, *d_dense = nullptr, *d_res = nullptr;
-        CF_TRY(batch_tmp.get(&d_p2, (size_t)n2, "monodec move pairs"));
-        CF_TRY(batch_tmp.get(&d_area, (size_t)words + 1, "monodec move areas"));
-        CF_TRY(batch_tmp.get(&d_recs, (size_t)7 * n_rec + 8, "monodec instances"));
-        CF_TRY(batch_tmp.get(&d_dense, (size_t)7 * n_rec + 8, "monodec dense instances"));
-        CF_TRY(batch_tmp.get(&d_res, (size_t)4 * n2, "monodec walk results"));
-        CF_TRY(cf_copy_h2d(ctx, d_p2, p2.data(), (size_t)n2 * sizeof(cf_md_pair)));
-        CF_HIP(hipMemsetAsync(d_ticket, 0, 16, ctx->stream));
-        CF_HIP(hipEventRecord(e1, ctx->stream));
-        hipLaunchKernelGGL(cf_md_kernel<true>, dim3((unsigned)std::min<int64_t>(n2, cap)), dim3((unsigned)block), CF_MD_LDS_BYTES, ctx->stream,
-                           (const cf_md_pair*)d_p2, n2, (const uint8_t*)d_reads, (const uint8_t*)d_monos, (const int32_t*)d_colj, (const int32_t*)d_colk, L,
-                           match, mismatch, gap, d_res, d_area, d_recs, d_dense, d_ticket, d_fault);
-        CF_KERNEL_CHECK("cf_md_kernel (moves pass)");
-        CF_HIP(hipEventRecord(e2, ctx->stream));
-        CF_HIP(hipEventSynchronize(e2));
-        (void)hipEventElapsedTime(&t, e0, e1); shape.phase_ms[0] += t;
-        (void)hipEventElapsedTime(&t, e1, e2); shape.phase_ms[2] += t;
-        CF_HIP(hipEventRecord(e0, ctx->stream));
-        int32_t h_fault = 0;
-        CF_TRY(cf_copy_d2h(ctx, &h_fault, d_fault, 4));
-        if (h_fault) return cf_fail(ctx, -5, "cf_monodec_run: a walk did not end inside its bounds (internal error)");
-        unsigned long long n_dense = 0;
-        CF_TRY(cf_copy_d2h(ctx, &n_dense, d_ticket + 1, 8));
-        if (n_dense > (unsigned long long)n_rec) return cf_fail(ctx, -5, "cf_monodec_run: more instances than read bytes (internal error)");
-        std::vector<int32_t> res((size_t)4 * n2), recs((size_t)7 * n_dense + 8);
-        CF_TRY(cf_copy_d2h(ctx, res.data(), d_res, (size_t)4 * n2 * 4));
-        if (n_dense > 0) CF_TRY(cf_copy_d2h(ctx, recs.data(), d_dense, (size_t)7 * n_dense * 4));
-        CF_HIP(hipEventRecord(e1, ctx->stream));
-        CF_HIP(hipEventSynchronize(e1));
-        (void)hipEventElapsedTime(&t, e0, e1); shape.phase_ms[0] += t;
-        for (int64_t x = 0; x < n2; ++x) {
-            const win& w = wins[first + (size_t)x];
-            const int32_t n_inst = res[(size_t)4 * x], prefix = res[(size_t)4 * x + 1];
-            const int64_t base = (int64_t)(uint32_t)res[(size_t)4 * x + 2] | ((int64_t)res[(size_t)4 * x + 3] << 32);
-            if (n_inst < 0 || n_inst > w.n || base < 0 || base + n_inst > (int64_t)n_dense)
-                return cf_fail(ctx, -5, "cf_monodec_run: a pair's instances lie outside the batch's list (internal error)");
-            res_info[(size_t)w.q] = cf_monodec_read{CF_MONODEC_DONE, w.strand, w.score, n_inst, prefix};
-            std::vector<cf_monodec_inst>& dst = per_read[first + (size_t)x];
-            dst.resize((size_t)n_inst);
-            for (int32_t a = 0; a < n_inst; ++a) {      // the walk wrote the last instance first
-                const int32_t* r = &recs[(size_t)7 * (base + (n_inst - 1 - a))];
-                dst[(size_t)a] = cf_monodec_inst{r[0], r[1], r[2], r[3], r[4], r[5], r[6]};
-            }
-        }
-        ++shape.n_batches;
-        first = last;
-    }
-    // the instances in read order
-    std::vector<size_t> slot_of((size_t)n_reads, (size_t)-1);
-    for (size_t x = 0; x < wins.size(); ++x) slot_of[(size_t)wins[x].q] = x;
-    for (int64_t q = 0; q < n_reads; ++q) {
-        res_ptr[(size_t)q] = (int64_t)res_inst.size();
-        if (slot_of[(size_t)q] != (size_t)-1) res_inst.insert(res_inst.end(), per_read[slot_of[(size_t)q]].begin(), per_read[slot_of[(size_t)q]].end());
-    }
-    res_ptr[(size_t)n_reads] = (int64_t)res_inst.size();
-    shape.phase_ms[3] = shape.phase_ms[0] + shape.phase_ms[1] + shape.phase_ms[2];
-    if (n_reads > 0) std::memcpy(info, res_info.data(), (size_t)n_reads * sizeof(cf_monodec_read));
+    CF_TRY(cf_rd_run(ctx, st, reads, read_off, n_reads, cf_rd_batch_bytes(ctx, ctx->monodec_batch_bytes), shape, res_ptr, res_inst));
+    if (n_reads > 0) std::memcpy(info, st.info.data(), (size_t)n_reads * sizeof(cf_monodec_read));
     if (ms_out) *ms_out = shape.phase_ms[3];
-    ctx->monodec_reads.swap(res_info);
+    ctx->monodec_reads.swap(st.info);
     ctx->monodec_ptr.swap(res_ptr);
     ctx->monodec_inst.swap(res_inst);
     ctx->monodec_last = shape;

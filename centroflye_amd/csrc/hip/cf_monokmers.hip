@@ -157,17 +157,6 @@ cf_mk_filter(cf_mk_rec* __restrict__ cls, const uint32_t* __restrict__ seg, int6
     }
 }
 
-// the string that holds position p of the concatenation: the s with off[s] <= p < off[s + 1] (empty strings hold nothing)
-__device__ __forceinline__ int64_t cf_mk_string_of(const int64_t* __restrict__ off, int64_t n_strings, int64_t p) {
-    const int64_t want = p + off[0];
-    int64_t lo = 0, hi = n_strings;      // off[lo] <= want < off[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= want) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(CF_MK_BLOCK)
 cf_mk_emit(const cf_mk_rec* __restrict__ cls, int64_t n_classes, uint32_t sentinel, const int64_t* __restrict__ off, int64_t n_strings,
            cf_monokmer* __restrict__ out, int32_t* __restrict__ rank, uint32_t* __restrict__ cnt, int64_t* __restrict__ n_kept) {
@@ -177,7 +166,7 @@ cf_mk_emit(const cf_mk_rec* __restrict__ cls, int64_t n_classes, uint32_t sentin
         if (r.w[3] < (uint64_t)n_classes) rank[r.w[3]] = kept ? (int32_t)j : -1;
         cnt[j] = kept ? r.w[2] : 0u;
         if (kept) {
-            const int64_t s = cf_mk_string_of(off, n_strings, r.w[0]);
+            const int64_t s = cf_string_of(off, n_strings, (int64_t)r.w[0] + off[0]);
             cf_monokmer o;
             o.s = (int32_t)s; o.i = (int32_t)((int64_t)r.w[0] + off[0] - off[s]); o.count = (int32_t)r.w[2]; o.pos = (int32_t)r.w[0];
             out[j] = o;
@@ -197,7 +186,7 @@ cf_mk_occ(const cf_mk_rec* __restrict__ rec, const uint32_t* __restrict__ head, 
         if (j < 0 || j >= n_kept) continue;
         const int64_t dst = ptr[j] + (i - (int64_t)seg[c]);
         if (dst < 0 || dst >= n_occ) continue;
-        const int64_t p = rec[i].w[2], s = cf_mk_string_of(off, n_strings, p);
+        const int64_t p = rec[i].w[2], s = cf_string_of(off, n_strings, p + off[0]);
         cf_monokmer_occ o;
         o.s = (int32_t)s; o.i = (int32_t)(p + off[0] - off[s]);
         occ[dst] = o;

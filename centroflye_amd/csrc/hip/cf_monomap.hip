@@ -64,16 +64,6 @@ cf_mm_scatter(const cf_mk_rec* __restrict__ rec, const uint32_t* __restrict__ he
     }
 }
 
-// the string that holds position p of the concatenation: the s with off[s] <= p < off[s + 1] (empty strings hold nothing; off[0] = 0)
-__device__ __forceinline__ int64_t cf_mm_string_of(const int64_t* __restrict__ off, int64_t n_strings, int64_t p) {
-    int64_t lo = 0, hi = n_strings;      // off[lo] <= p < off[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= p) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(CF_MM_BLOCK)
 cf_mm_compact(const uint32_t* __restrict__ flag, const int64_t* __restrict__ hs, const uint32_t* __restrict__ hit, const int64_t* __restrict__ off,
               int64_t n_edges, int64_t n_strings, cf_monomap_hit* __restrict__ hits, int32_t* __restrict__ hit_read, int64_t n, int64_t n_edge_letters,
@@ -83,7 +73,7 @@ cf_mm_compact(const uint32_t* __restrict__ flag, const int64_t* __restrict__ hs,
         if (!flag[p]) continue;
         const int64_t x = hs[p], ep = hit[p];
         if (x < 0 || x >= n_hits || ep >= n_edge_letters || n_edges < 1) continue;
-        const int64_t ed = cf_mm_string_of(off, n_edges, ep), s = cf_mm_string_of(off, n_strings, p);
+        const int64_t ed = cf_string_of(off, n_edges, ep), s = cf_string_of(off, n_strings, p);
         if (s < n_edges) continue;
         cf_monomap_hit h;
         h.e = (int32_t)ed; h.j = (int32_t)(ep - off[ed]); h.i = (int32_t)(p - off[s]);
