@@ -181,6 +181,8 @@ PROTOTYPES = {
     "cf_get_stats": (C.c_int, [_P, C.POINTER(Stats)]),
     "cf_get_times": (C.c_int, [_P, C.POINTER(Times)]),
     "cf_set_param": (C.c_int, [_P, C.c_char_p, _I64]),
+    "cf_get_param": (C.c_int, [_P, C.c_char_p, _PI64]),
+    "cf_param_name": (C.c_char_p, [_I32]),
     "cf_comm_init": (C.c_int, [_P, _I32, _I32, C.c_char_p]),
     "cf_comm_free": (C.c_int, [_P]),
     "cf_comm_info": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32)]),

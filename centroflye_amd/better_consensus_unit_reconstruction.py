@@ -91,11 +91,8 @@ def top_kmers(packed, k, n, times=None):
     t = time.perf_counter()
     e = session.ensure_loaded(packed, 1)
     t = _tick(times, "load", t)
-    e.set_param("count_skip_exotic", 1)
-    try:
+    with e.knobs(count_skip_exotic=1):
         e.count_occurrences(k)
-    finally:
-        e.set_param("count_skip_exotic", 0)
     t = _tick(times, "count", t)
     keys, counts = e.top_kmers(n)
     strs, cnts = km.decode(keys, k) if keys.size else [], [int(c) for c in counts]

@@ -3,6 +3,7 @@
 
 #include <atomic>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <thread>
 
@@ -493,149 +494,49 @@ int cf_get_times(cf_ctx* ctx, cf_times* out) {
     return 0;
 }
 
+// The knobs: cf_knobs.h as one entry per name, and the three entry points that go through them.
+static inline bool cf_in(int64_t v, int64_t lo, int64_t hi) { return lo <= v && v <= hi; }
+struct cf_knob {
+    const char* name;
+    const char* refusal;
+    bool (*accepted)(int64_t v);
+    void (*store)(cf_ctx* ctx, int64_t v);
+    int64_t (*load)(const cf_ctx* ctx);
+};
+static const cf_knob cf_knobs[] = {
+#define CF_KNOB(name, type, def, accepted, stored, refusal) \
+    {#name, refusal, [](int64_t v) -> bool { (void)v; return accepted; }, [](cf_ctx* ctx, int64_t v) { ctx->name = stored; }, [](const cf_ctx* ctx) -> int64_t { return ctx->name; }},
+#include "cf_knobs.h"
+#undef CF_KNOB
+};
+static const int cf_n_knobs = (int)(sizeof(cf_knobs) / sizeof(cf_knobs[0]));
+
+static const cf_knob* cf_find_knob(cf_ctx* ctx, const char* name) {
+    for (const cf_knob& k : cf_knobs)
+        if (!std::strcmp(k.name, name)) return &k;
+    cf_fail(ctx, -22, std::string("unknown parameter ") + name);
+    return nullptr;
+}
+
 int cf_set_param(cf_ctx* ctx, const char* name, int64_t value) {
     if (!ctx || !name) return -22;
-    const std::string n(name);
-    if (n == "dist_block") {
-        if (value != 0 && (value < 64 || value > 1024 || value % 64)) return cf_fail(ctx, -22, "dist_block must be 0 (auto) or a multiple of 64 in [64, 1024]");
-        ctx->dist_block = (int)value;
-    } else if (n == "dist_wgs") {
-        if (value < 0 || value > 8) return cf_fail(ctx, -22, "dist_wgs out of range (0 = auto, 1 .. 8)");
-        ctx->dist_wgs = (int)value;
-    } else if (n == "dist_slots") {
-        if (value != 0 && (value < 256 || value > 19200)) return cf_fail(ctx, -22, "dist_slots out of range (0 = auto, 256 .. 19200: table + work lists must fit the 160 KiB LDS)");
-        ctx->dist_slots = (int)value;
-    } else if (n == "dist_wide") {
-        ctx->dist_wide = value != 0;
-    } else if (n == "dist_post_atomics") {
-        ctx->dist_post_atomics = value != 0;
-    } else if (n == "dist_hot_cap") {
-        if (value < 0) return cf_fail(ctx, -22, "dist_hot_cap must be >= 0");
-        ctx->dist_hot_cap = (int)value;
-    } else if (n == "dist_hot_entries") {
-        if (value < -1 || value > 0x7FFFFFFF) return cf_fail(ctx, -22, "dist_hot_entries out of range (-1 = always keep the list, 0 .. 2^31 - 1)");
-        ctx->dist_hot_entries = (int)value;
-    } else if (n == "lut_shift") {
-        if (value < -1 || value > 3) return cf_fail(ctx, -22, "lut_shift out of range (-1 = by the set's size, 0 .. 3)");
-        ctx->lut_shift = (int)value;
-    } else if (n == "dist_regions") {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8) return cf_fail(ctx, -22, "dist_regions must be 0 (auto), 1, 2, 4 or 8");
-        ctx->dist_regions = (int)value;
-    } else if (n == "dist_dbits") {
-        if (value != 0 && (value < 5 || value > 8)) return cf_fail(ctx, -22, "dist_dbits must be 0 (auto) or 5 .. 8");
-        ctx->dist_dbits = (int)value;
-    } else if (n == "dist_fill_pct") {
-        if (value < 10 || value > 90) return cf_fail(ctx, -22, "dist_fill_pct out of range (10 .. 90)");
-        ctx->dist_fill_pct = (int)value;
-    } else if (n == "dist_edge_chunk") {
-        if (value < 0 || value > (1 << 20)) return cf_fail(ctx, -22, "dist_edge_chunk out of range (0 = default, 1 .. 2^20)");
-        ctx->dist_edge_chunk = (int)value;
-    } else if (n == "dist_int_thr") {
-        ctx->dist_int_thr = value != 0;
-    } else if (n == "dist_sketch_bits") {
-        if (value != 0 && value != 4 && value != 8) return cf_fail(ctx, -22, "dist_sketch_bits must be 0 (by min_cov), 4 or 8");
-        ctx->dist_sketch_bits = (int)value;
-    } else if (n == "dist_sketch_tail") {
-        ctx->dist_sketch_tail = value != 0;
-    } else if (n == "dist_classes") {
-        ctx->dist_classes = value != 0;
-    } else if (n == "dist_class_bits") {
-        if (value < 1 || value > 16) return cf_fail(ctx, -22, "dist_class_bits out of range (1 .. 16)");
-        ctx->dist_class_bits = (int)value;
-    } else if (n == "dist_groups") {
-        ctx->dist_groups = value != 0;
-    } else if (n == "dist_group_cap") {
-        if (value < 1 || value > 32) return cf_fail(ctx, -22, "dist_group_cap out of range (1 .. 32)");
-        ctx->dist_group_cap = (int)value;
-    } else if (n == "dist_filter_once") {
-        ctx->dist_filter_once = value != 0;
-    } else if (n == "dist_sketch") {
-        ctx->dist_sketch = value != 0;
-    } else if (n == "dist_est_pct") {
-        if (value < 5 || value > 100) return cf_fail(ctx, -22, "dist_est_pct out of range (5 .. 100)");
-        ctx->dist_est_pct = (int)value;
-    } else if (n == "dist_stage") {
-        if (value < 0 || value > 2048) return cf_fail(ctx, -22, "dist_stage out of range (0 .. 2048)");
-        ctx->dist_stage = (int)value;
-    } else if (n == "place_fused") {
-        ctx->place_fused = value != 0;
-    } else if (n == "dist_region_bytes") {
-        ctx->dist_region_bytes = value != 0;
-    } else if (n == "place_mode") {
-        if (value < 1 || value > 3) return cf_fail(ctx, -22, "place_mode out of range (1 = hash map, 2 = per-read regions unless min_inters < 4, 3 = per-read regions always)");
-        ctx->place_mode = (int)value;
-    } else if (n == "place_block") {
-        if (value != 0 && (value < 128 || value > 1024 || value % 128)) return cf_fail(ctx, -22, "place_block must be 0 or a multiple of 128 in 128 .. 1024");
-        ctx->place_block = (int)value;
-    } else if (n == "place_row_words") {
-        if (value != 0 && value != 32 && value != 64) return cf_fail(ctx, -22, "place_row_words must be 0 (auto), 32 or 64");
-        ctx->place_row_words = (int)value;
-    } else if (n == "place_l3") {
-        if (value < 0 || value > 2) return cf_fail(ctx, -22, "place_l3 must be 0 (auto), 1 (always) or 2 (never)");
-        ctx->place_l3 = (int)value;
-    } else if (n == "place_l3_shift") {
-        if (value < 0 || value > 6) return cf_fail(ctx, -22, "place_l3_shift must be 0 (= 6) .. 6");
-        ctx->place_l3_shift = (int)value;
-    } else if (n == "place_long_rescans") {
-        if (value < -1 || value > 1000000) return cf_fail(ctx, -22, "place_long_rescans out of range (-1, 0 .. 1000000)");
-        ctx->place_long_rescans = (int)value;
-    } else if (n == "place_cmap_bits") {
-        if (value < 0 || value > 30) return cf_fail(ctx, -22, "place_cmap_bits out of range (0 = default, 1 .. 30)");
-        ctx->place_cmap_bits = (int)value;
-    } else if (n == "place_slots_per_unit") {
-        if (value < 0 || value > 65536) return cf_fail(ctx, -22, "place_slots_per_unit out of range (0 = default, 1 .. 65536)");
-        ctx->place_slots_per_unit = (int)value;
-    } else if (n == "place_chunk") {
-        if (value < 1 || value > 64) return cf_fail(ctx, -22, "place_chunk out of range (1 .. 64)");
-        ctx->place_chunk = (int)value;
-    } else if (n == "place_grid") {
-        if (value < 0 || value > 4096) return cf_fail(ctx, -22, "place_grid out of range (0 = auto, 1 .. 4096)");
-        ctx->place_grid = (int)value;
-    } else if (n == "map_window") {
-        if (value < 0 || value > 4096) return cf_fail(ctx, -22, "map_window out of range (0 = default, 1 .. 4096: 12 bytes of LDS per slot)");
-        ctx->map_window = (int)value;
-    } else if (n == "edit_lds_diags") {
-        if (value < 0 || value > 16384) return cf_fail(ctx, -22, "edit_lds_diags out of range (0 = default, 1 .. 16384: 8 bytes of LDS per diagonal)");
-        ctx->edit_lds_diags = (int)value;
-    } else if (n == "tandem_key_mode") {
-        if (value < 0 || value > 2) return cf_fail(ctx, -22, "tandem_key_mode out of range (0 = auto, 1 = 64-bit keys, 2 = 16-byte records)");
-        ctx->tandem_key_mode = (int)value;
-    } else if (n == "tandem_batch_windows") {
-        if (value < 0 || value > ((int64_t)1 << 31)) return cf_fail(ctx, -22, "tandem_batch_windows out of range (0 = default, 1 .. 2^31)");
-        ctx->tandem_batch_windows = value;
-    } else if (n == "cons_batch_bytes") {
-        if (value < 0 || value > ((int64_t)1 << 36)) return cf_fail(ctx, -22, "cons_batch_bytes out of range (0 = default, 1 .. 2^36)");
-        ctx->cons_batch_bytes = value;
-    } else if (n == "ualign_batch_bytes") {
-        if (value < 0 || value > ((int64_t)1 << 36)) return cf_fail(ctx, -22, "ualign_batch_bytes out of range (0 = default, 1 .. 2^36)");
-        ctx->ualign_batch_bytes = value;
-    } else if (n == "monodec_batch_bytes") {
-        if (value < 0 || value > ((int64_t)1 << 36)) return cf_fail(ctx, -22, "monodec_batch_bytes out of range (0 = default, 1 .. 2^36)");
-        ctx->monodec_batch_bytes = value;
-    } else if (n == "count_mode") {
-        ctx->count_mode = value != 0;
-    } else if (n == "count_bits") {
-        if (value < 0 || value > 27) return cf_fail(ctx, -22, "count_bits out of range (0 = auto, 1 .. 27)");
-        ctx->count_bits = (int)value;
-    } else if (n == "count_slots") {
-        if (value < 256 || (value & (value - 1)) || value * 8 > 128 * 1024) return cf_fail(ctx, -22, "count_slots must be a power of two in [256, 16384]");
-        ctx->count_slots = (int)value;
-    } else if (n == "count_tile") {
-        if (value < 1 || value > 64) return cf_fail(ctx, -22, "count_tile out of range");
-        ctx->count_tile = (int)value;
-    } else if (n == "count_skip_exotic") {
-        if (value < 0 || value > 1) return cf_fail(ctx, -22, "count_skip_exotic must be 0 or 1");
-        ctx->count_skip_exotic = (int)value;
-    } else if (n == "comm_round_bytes") {
-        if (value < 16 || value > ((int64_t)1 << 30) || value % 16) return cf_fail(ctx, -22, "comm_round_bytes must be a multiple of 16 in [16, 2^30]");
-        ctx->comm_round_bytes = value;
-        cf_comm_apply_params(ctx);
-    } else if (n == "comm_self_p2p") {
-        ctx->comm_self_p2p = value != 0;
-        cf_comm_apply_params(ctx);
-    } else return cf_fail(ctx, -22, "unknown parameter " + n);
+    const cf_knob* k = cf_find_knob(ctx, name);
+    if (!k) return -22;
+    if (!k->accepted(value)) return cf_fail(ctx, -22, k->refusal);
+    k->store(ctx, value);
+    if (!std::strncmp(name, "comm_", 5)) cf_comm_apply_params(ctx);      // the transport keeps its own copy of its knobs
     return 0;
 }
+
+int cf_get_param(cf_ctx* ctx, const char* name, int64_t* value) {
+    if (!ctx || !name || !value) return -22;
+    const cf_knob* k = cf_find_knob(ctx, name);
+    if (!k) return -22;
+    *value = k->load(ctx);
+    return 0;
+}
+
+const char* cf_param_name(int32_t index) { return index >= 0 && index < cf_n_knobs ? cf_knobs[index].name : nullptr; }
 
 int cf_selftest_sort(cf_ctx* ctx, const uint64_t* keys, int64_t n, int32_t bits, uint64_t* out) {
     if (!ctx) return -22;

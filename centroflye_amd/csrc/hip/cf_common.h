@@ -220,55 +220,10 @@ struct cf_ctx {
     cf_stats stats{};
     cf_times times{};
 
-    // knobs
-    int dist_block = 0;      // threads per workgroup; 0 = chosen with dist_wgs
-    int dist_wgs = 0;        // workgroups per CU the LDS is split between; 0 = 2 x 512 threads or 1 x 1024, by the pair emissions per first k-mer
-    int dist_slots = 0;      // LDS budget of the (b,d) table in 8-byte units; 0 = all that is left next to the work lists
-    int dist_wide = 0;       // 1 forces the 8-byte-slot table layout (tests)
-    int dist_post_atomics = 0;   // 1 builds the postings with the histogram + fill passes of atomics instead of the sort (tests, A/B runs)
-    int dist_hot_cap = 0;    // > 0: cap on the filter's hot-slot list (tests)
-    int lut_shift = -1;      // the k-mer lookup table of A3 has (2 x k-mers, rounded up to a power of two) << lut_shift slots; -1 = by the set's size
-    int dist_hot_entries = 32768;   // first k-mers with more partner entries keep no hot-slot list (it would overflow: ~5 % of the pairs' keys reach min_cov); -1: always keep it
-    int dist_regions = 0;    // 1, 2, 4, 8: force the region layout of the 6-byte slots with at least that many regions (tests), 0 = only when the ranks need it
-    int dist_region_bytes = 0; // 1: the region layout streams rank and unit index apart (round 3) even where the 4-byte stream of cf_tab_region26 applies (tests)
-    int dist_dbits = 0;      // 5 .. 8: upper limit of the distance-field bits of the 6-byte-slot layout (tests), 0 = as many as the k-mer ranks leave
-    int dist_fill_pct = 70;  // a (b,d) table pass is split when more than this share of the slots is in use
-    int dist_edge_chunk = 0; // > 0: edge rows a workgroup reserves per global atomic (tests: small chunks cross often), 0 = 8192
-    int dist_int_thr = 1;    // 1: rel_threshold == 0.8 is tested as 5 cnt >= 4 total; 0: always the double division (tests)
-    int dist_sketch = 1;     // 0: every (b,d) pair goes to the exact table (no counting sketch first)
-    bool dist_sketch_tail = true;   // the sketch sweep skips the items beyond the largest distance at which min_cov postings still have a partner unit (0: every item, in the old order)
-    int dist_class_bits = 16;       // bits of the posting list's hash in the order key (1 .. 16; tests: few bits make different lists collide, which the comparison of the lists must undo)
-    bool dist_classes = true;       // first k-mers with equal posting lists share one sweep of cf_dist_kernel (0: every k-mer on its own, as before)
-    bool dist_groups = true;        // first k-mers with the same first posting unit share one sweep over the UNION of their lists, a 32-bit mask per (b, d); 0: classes only
-    bool dist_filter_once = true;   // the mask table's filter evaluates every (hot slot, member) pair of a group in one section, rows reserved per group; 0: the loop over the members, one filter each
-    int dist_group_cap = 32;        // postings of a group's union (1 .. 32: the mask's bits; tests: small caps close groups early)
-    int dist_sketch_bits = 0;   // bits of a sketch counter: 0 = 4 when min_cov <= 9, else 8; 8 forces bytes
-    int dist_est_pct = 80;   // expected distinct (b,d) keys per 100 pair emissions: sizes the initial number of table partitions
-    int dist_stage = 2048;   // edges of a pass whose rows do not fit the rest of the workgroup's output chunk, staged in LDS (more: a sweep of the marked slots)
-    int place_chunk = 2, place_grid = 0;     // cloud entries per wave step of that kernel (1 .. 64), its workgroups (0 = one per CU)
-    int place_fused = 1;         // 1: the greedy iteration is arg-max + (pick, add, score updates) = 2 kernels; 0: 3 kernels with an event list
-    int place_mode = 2;          // 2: per-read score regions, one kernel per greedy iteration (cf_place2.hip); 1: the hash-map path of rounds 1-3 (cf_place.hip)
-    int place_block = 0;         // cf_place2: threads per workgroup of the iteration kernel (128 .. 1024, a multiple of 128; 0 = 1024)
-    int place_row_words = 0;     // cf_place2: 32-bit words of a posting row (32 or 64); 0 = the smaller one that holds the longest posting list
-    int place_long_rescans = 2;  // cf_place2: long rescans (reads with more than four candidate rows) per greedy iteration above which the run goes to the hash-map path (-1: at the first look, tests)
-    int place_cmap_bits = 0;     // cf_place2: log2 of the first capacity of the contig's overflow map (0 = entries / 8, at least 2^21; tests force tiny maps that have to grow)
-    int place_slots_per_unit = 0; // cf_place2: score-region slots per unit of a read (0 = 48); doubled-up automatically when a region fills
-    int place_l3 = 0;            // cf_place2: third level of the arg-max (best candidate per group of 64-read blocks): 1 = on; 0 / 2 = off (measured: no gain at 500 000 reads)
-    int place_l3_shift = 0;      // cf_place2: log2 of the blocks per group (0 = 6: groups of 64 blocks = 4 096 reads; tests use small groups at small read sets)
-    int map_window = 0;          // cf_map: candidate starts (LDS score slots) a wave covers per pass over a read's entries (0 = 2048; tests force small windows)
-    int edit_lds_diags = 0;      // cf_edit: diagonals per wavefront array above which a pair's wavefronts live in HBM, not LDS (0 = 16384; tests force small values)
-    int tandem_key_mode = 0;     // cf_tandem: 0 = 64-bit keys where (read in batch, code, position) fit them, 1 = keys or an error, 2 = 16-byte records
-    int64_t tandem_batch_windows = 0;   // cf_tandem: windows per batch of whole reads (0 = 2^26; tests force borders inside small inputs)
-    int64_t cons_batch_bytes = 0;       // cf_consensus: bytes of move areas per batch of pairs (0 = 2^30; tests force borders inside one position's reads)
-    int64_t ualign_batch_bytes = 0;     // cf_ualign: bytes of move areas per batch of pairs of the moves pass (0 = an eighth of the device's memory, 2^28 .. 2^34; tests force one pair per batch)
-    int64_t monodec_batch_bytes = 0;    // cf_monodec: bytes of move areas per batch of pairs of the moves pass (0 = an eighth of the device's memory, 2^28 .. 2^34; tests force one pair per batch)
-    int count_mode = 1;         // 1: sort and reduce (cf_count2.hip) when it applies; 0: the atomic table of round 1 (cf_count.hip)
-    int count_bits = 0;          // bucket bits of the sort-and-reduce path; 0 = from the number of windows (tests force small / large values)
-    int count_slots = 4096;
-    int count_tile = 16;
-    int count_skip_exotic = 0;   // 1: cf_count_occurrences counts reads with other symbols too, skipping their windows (stage 4 adds them on the host)
-    int64_t comm_round_bytes = (int64_t)256 << 20;   // bytes per pair and round of the multi-GPU exchanges (tests force small rounds)
-    int comm_self_p2p = 0;       // 1: a rank's message to itself goes through ncclSend / ncclRecv too (tests: the p2p path on one GPU)
+    // the knobs of cf_set_param: one member per entry of cf_knobs.h, with its default
+#define CF_KNOB(name, type, def, accepted, stored, refusal) type name = def;
+#include "cf_knobs.h"
+#undef CF_KNOB
 };
 
 int cf_fail(cf_ctx* ctx, int code, const std::string& msg);

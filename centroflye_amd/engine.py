@@ -4,6 +4,7 @@ One ``Engine`` = one ``cf_ctx`` = one GPU.  Every method maps 1:1 onto a C entry
 mirrors of the reference's modules (``distance_based_kmer_recruitment``, ``read_kmer_cloud``,
 ``cloud_contig``, ``read_placer``) are written on top of this class.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -60,6 +61,32 @@ class Engine:
 
     def set_param(self, name, value):
         self._check(self._lib.cf_set_param(self._ctx, name.encode(), int(value)), f"cf_set_param({name})")
+
+    def get_param(self, name):
+        v = C.c_int64()
+        self._check(self._lib.cf_get_param(self._ctx, name.encode(), C.byref(v)), f"cf_get_param({name})")
+        return v.value
+
+    def param_names(self):
+        names = []
+        while (n := self._lib.cf_param_name(len(names))) is not None:
+            names.append(n.decode())
+        return names
+
+    @contextlib.contextmanager
+    def knobs(self, **settings):
+        """Run the body under these knob settings, set in the order given; on the way out, and when a setting is refused,
+        every knob set so far gets the value it had before, last set first."""
+        saved = [(name, self.get_param(name)) for name in settings]
+        done = 0
+        try:
+            for name, value in settings.items():
+                self.set_param(name, value)
+                done += 1
+            yield self
+        finally:
+            for name, value in reversed(saved[:done]):
+                self.set_param(name, value)
 
     def stats(self):
         s = _lib.Stats()

@@ -589,11 +589,138 @@ int cf_allgather_kmers(cf_ctx* ctx, int64_t* n_out);
 int cf_allgather_clouds(cf_ctx* ctx, int64_t* n_entries);
 int cf_allreduce_unique(cf_ctx* ctx, int64_t* n_unique);
 
-/* Tuning knobs (defaults are chosen for gfx950): name in {"dist_block" (threads per workgroup, 0 = auto), "dist_wgs"
- * (workgroups per CU the LDS is split between, 0 = auto: by the pair emissions per first k-mer), "dist_slots" (LDS budget of the (b,d) table in 8-byte units, 0 = all that
- * is left), "dist_sketch" (0: every pair goes to the exact table), "dist_sketch_tail" (1, the default: the sketch sweep leaves out the items beyond the largest distance at which min_cov postings of the first k-mer still have a partner unit; 0: it takes every item, in the order of the posting list), "dist_classes" (1, the default: first k-mers of a launch whose posting lists are equal share one sweep of the distance kernel, which writes the rows of each of them; 0: every first k-mer is swept on its own; the results are the same), "dist_class_bits" (1 .. 16, default 16: bits of the posting list's hash in the sort key that brings equal lists together; fewer bits only lose merges; a TEST knob: few bits make different lists collide, so that the comparison of the lists is what keeps them apart; the library never uses more bits than the 64-bit sort key leaves next to the unit and rank fields), "dist_groups" (1, the default: the first k-mers of a launch that share their first posting unit are cut into groups whose posting lists have a union of at most dist_group_cap postings; the distance kernel sweeps the union once into a table of 32-bit masks and every member reads its own counts out of it; 0: classes only, the launch it was before; needs dist_classes 1 and the 6-byte-slot layout, the other layouts keep the classes; the results are the same), "dist_group_cap" (1 .. 32, default 32: the postings of a group's union, the bits of a mask; a test and tuning knob), "dist_filter_once" (1, the default: in a launch with groups the distance kernel filters all members of a group in one section — a thread keeps its hot slot and the masks of its b in registers, loops over the members and the rows are reserved once per group; 0: one filter per member, the code it was before; the results are the same, the order of the rows in the output differs), "dist_fill_pct", "dist_est_pct", "dist_stage", "dist_edge_chunk" (edge rows a workgroup reserves in the output per global atomic, 0 = 8192; tests use small chunks), "dist_int_thr" (0: the dominance test always divides in doubles; 1, the default: the literal 0.8 is tested as 5 cnt >= 4 total, which is the same predicate),
- * "dist_wide", "dist_post_atomics" (1: postings by a histogram and a fill pass of atomics instead of the sort), "dist_hot_cap" (tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan), "dist_sketch_bits" (bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the counters in the same LDS —, else 8; 8 forces bytes), "lut_shift" (the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1, the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0), "dist_hot_entries" (default 32768: first k-mers with more partner entries than this keep no list of hot slots during their inserts — it would overflow — and their filter scans the count fields; -1: always keep it), "dist_regions" (1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long reads take by themselves), "dist_dbits" (5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks need), "place_mode" (2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4; smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the hash-map path of rounds 1-3, cf_place.hip), "place_grid" / "place_block" (workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024), "place_row_words" (32 or 64 words per posting row, 0 = by the longest posting list), "place_slots_per_unit" (score-region slots per unit of a read, 0 = 48; grown automatically when a region fills), "place_l3" / "place_l3_shift" (1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily — built in round 5, measured neutral at 500 000 reads, off by default), "dist_region_bytes" (1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond 128 units do by themselves), "place_long_rescans" (default 2: a run of the region path whose reads average more than this many rescans of reads with more than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is handed to the hash-map path; -1: at the first look, tests), "place_cmap_bits" (log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 = cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load), "place_chunk", "place_fused" (place_mode 1: cloud entries per wave step; 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list and a third kernel per greedy iteration), "count_mode" (1: A1 by sort and reduce, 0: the atomic table), "count_bits" (bucket bits of the former, 0 = auto), "count_slots", "count_tile", "count_skip_exotic" (1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads), "comm_round_bytes" (bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds), "map_window" (candidate starts — LDS score slots — that cf_map_reads covers per pass over a read's cloud entries, 0 = 2048, at most 4096; a read whose hits span more starts takes several passes, tests force that with tiny windows), "edit_lds_diags" (cf_edit_distances: diagonals per wavefront array up to which a pair's wavefronts stay in LDS, 0 = 16384, at most 16384; tests force the HBM path with small values), "comm_self_p2p" (1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a one-GPU box runs the whole p2p path), "tandem_key_mode" and "tandem_batch_windows" (cf_tandem_scan: see there), "cons_batch_bytes" (cf_consensus_run: bytes of move areas per batch of pairs, 0 = 2^30, at most 2^36; a batch holds at least one pair; tests force many batches with small values), "ualign_batch_bytes" (cf_ualign_run: bytes of move areas per batch of pairs of its moves pass, 0 = an eighth of the device's memory between 2^28 and 2^34, at most 2^36; a batch holds at least one pair), "monodec_batch_bytes" (cf_monodec_run: the same for its moves pass)}.  Results never depend on them (tests/test_gpu_parity.py). */
+/* Tuning knobs (defaults are chosen for gfx950), one paragraph per name, in the order of cf_param_name.  The default, the
+ * accepted values and the refusal of each stand in centroflye_amd/csrc/hip/cf_knobs.h, the one table cf_set_param, cf_get_param
+ * and cf_param_name are made of.  Results never depend on the knobs (tests/test_gpu_parity.py).
+ *
+ * "dist_block": threads per workgroup, 0 = auto.
+ *
+ * "dist_wgs": workgroups per CU the LDS is split between, 0 = auto: by the pair emissions per first k-mer.
+ *
+ * "dist_slots": LDS budget of the (b,d) table in 8-byte units, 0 = all that is left.
+ *
+ * "dist_wide": 1 forces the 8-byte-slot table layout (tests).
+ *
+ * "dist_post_atomics": 1: postings by a histogram and a fill pass of atomics instead of the sort.
+ *
+ * "dist_hot_cap": tests: a small cap on the filter's hot-slot list forces the evaluation inside the bucket scan.
+ *
+ * "lut_shift": the k-mer lookup table of cf_build_clouds gets (2 x k-mers rounded up to a power of two) << lut_shift slots; -1,
+ * the default: 2 for sets of up to 1.7e7 k-mers, 1 up to 1.3e8, else 0.
+ *
+ * "dist_hot_entries": default 32768: first k-mers with more partner entries than this keep no list of hot slots during their
+ * inserts — it would overflow — and their filter scans the count fields; -1: always keep it.
+ *
+ * "dist_regions": 1, 2, 4, 8: force the region layout of the 6-byte slots, which k-mer sets of 2^24 .. 2^27 ranks with long
+ * reads take by themselves.
+ *
+ * "dist_region_bytes": 1: the region layout streams rank and unit index apart, as k-mer sets beyond 2^26 ranks or reads beyond
+ * 128 units do by themselves.
+ *
+ * "dist_dbits": 5 .. 8: cap on the distance-field bits of the 6-byte table slots [d | b]; 0 = 32 minus the bits the k-mer ranks
+ * need.
+ *
+ * "dist_fill_pct": a (b,d) table pass is split when more than this share of the slots is in use.
+ *
+ * "dist_edge_chunk": edge rows a workgroup reserves in the output per global atomic, 0 = 8192; tests use small chunks.
+ *
+ * "dist_int_thr": 0: the dominance test always divides in doubles; 1, the default: the literal 0.8 is tested as 5 cnt >= 4
+ * total, which is the same predicate.
+ *
+ * "dist_sketch": 0: every pair goes to the exact table.
+ *
+ * "dist_sketch_tail": 1, the default: the sketch sweep leaves out the items beyond the largest distance at which min_cov
+ * postings of the first k-mer still have a partner unit; 0: it takes every item, in the order of the posting list.
+ *
+ * "dist_class_bits": 1 .. 16, default 16: bits of the posting list's hash in the sort key that brings equal lists together;
+ * fewer bits only lose merges; a TEST knob: few bits make different lists collide, so that the comparison of the lists is what
+ * keeps them apart; the library never uses more bits than the 64-bit sort key leaves next to the unit and rank fields.
+ *
+ * "dist_classes": 1, the default: first k-mers of a launch whose posting lists are equal share one sweep of the distance kernel,
+ * which writes the rows of each of them; 0: every first k-mer is swept on its own; the results are the same.
+ *
+ * "dist_groups": 1, the default: the first k-mers of a launch that share their first posting unit are cut into groups whose
+ * posting lists have a union of at most dist_group_cap postings; the distance kernel sweeps the union once into a table of
+ * 32-bit masks and every member reads its own counts out of it; 0: classes only, the launch it was before; needs dist_classes 1
+ * and the 6-byte-slot layout, the other layouts keep the classes; the results are the same.
+ *
+ * "dist_filter_once": 1, the default: in a launch with groups the distance kernel filters all members of a group in one section
+ * — a thread keeps its hot slot and the masks of its b in registers, loops over the members and the rows are reserved once per
+ * group; 0: one filter per member, the code it was before; the results are the same, the order of the rows in the output
+ * differs.
+ *
+ * "dist_group_cap": 1 .. 32, default 32: the postings of a group's union, the bits of a mask; a test and tuning knob.
+ *
+ * "dist_sketch_bits": bits of a counter of the distance stage's counting sketch: 0, the default: 4 when min_cov <= 9 — twice the
+ * counters in the same LDS —, else 8; 8 forces bytes.
+ *
+ * "dist_est_pct": expected distinct (b,d) keys per 100 pair emissions: sizes the initial number of table partitions.
+ *
+ * "dist_stage": edges of a pass whose rows do not fit the rest of the workgroup's output chunk, staged in LDS.
+ *
+ * "place_chunk": place_mode 1: cloud entries per wave step.
+ *
+ * "place_grid" / "place_block": workgroups and threads per workgroup of the iteration kernel, 0 = 128 x 1024.
+ *
+ * "place_fused": place_mode 1: 1: score updates applied by the waves that lay a read onto the contig, 0: through an event list
+ * and a third kernel per greedy iteration.
+ *
+ * "place_mode": 2, the default: per-read score regions and one kernel per greedy iteration, cf_place2.hip — for min_inters >= 4;
+ * smaller thresholds make nearly every score row a candidate row and take path 1; 3: the regions whatever the threshold; 1: the
+ * hash-map path of rounds 1-3, cf_place.hip.
+ *
+ * "place_row_words": 32 or 64 words per posting row, 0 = by the longest posting list.
+ *
+ * "place_long_rescans": default 2: a run of the region path whose reads average more than this many rescans of reads with more
+ * than four candidate score rows per greedy iteration — k-mers that are not unique to one place of the array, thin coverage — is
+ * handed to the hash-map path; -1: at the first look, tests.
+ *
+ * "place_cmap_bits": log2 of the first capacity of the contig's overflow map — the positions of a k-mer beyond its fourth —, 0 =
+ * cloud entries / 8, at least 2^21; grown automatically, times four, when it passes half load.
+ *
+ * "place_slots_per_unit": score-region slots per unit of a read, 0 = 48; grown automatically when a region fills.
+ *
+ * "place_l3" / "place_l3_shift": 1: the third level of the placement arg-max, groups of 2^shift blocks of 64 reads kept lazily —
+ * built in round 5, measured neutral at 500 000 reads, off by default.
+ *
+ * "map_window": candidate starts — LDS score slots — that cf_map_reads covers per pass over a read's cloud entries, 0 = 2048, at
+ * most 4096; a read whose hits span more starts takes several passes, tests force that with tiny windows.
+ *
+ * "edit_lds_diags": cf_edit_distances: diagonals per wavefront array up to which a pair's wavefronts stay in LDS, 0 = 16384, at
+ * most 16384; tests force the HBM path with small values.
+ *
+ * "tandem_key_mode" and "tandem_batch_windows": cf_tandem_scan: see there.
+ *
+ * "cons_batch_bytes": cf_consensus_run: bytes of move areas per batch of pairs, 0 = 2^30, at most 2^36; a batch holds at least
+ * one pair; tests force many batches with small values.
+ *
+ * "ualign_batch_bytes": cf_ualign_run: bytes of move areas per batch of pairs of its moves pass, 0 = an eighth of the device's
+ * memory between 2^28 and 2^34, at most 2^36; a batch holds at least one pair.
+ *
+ * "monodec_batch_bytes": cf_monodec_run: the same for its moves pass.
+ *
+ * "count_mode": 1: A1 by sort and reduce, 0: the atomic table.
+ *
+ * "count_bits": bucket bits of the former, 0 = auto.
+ *
+ * "count_slots" / "count_tile": count_mode 0: 8-byte slots of the LDS set a hash class of a read's windows has to fit, and reads
+ * per tile of its launch.
+ *
+ * "count_skip_exotic": 1: cf_count_occurrences runs on reads with symbols other than upper-case A, C, G, T and skips the windows
+ * that hold one — the caller counts those on the host, cfh_exotic_occurrences; 0, the default: it refuses such reads.
+ *
+ * "comm_round_bytes": bytes per pair of ranks and round of the multi-GPU exchanges, default 2^28; tests force many rounds.
+ *
+ * "comm_self_p2p": 1: the message a rank sends to itself goes through ncclSend / ncclRecv like every other one, so that a
+ * one-GPU box runs the whole p2p path.
+ *
+ * cf_set_param stores an accepted value (-22 and a message for a refused one or an unknown name; the knob keeps its value).
+ * cf_get_param: *value = what is stored (1 for any non-zero value of an on / off knob); an unknown name is refused in the same
+ * way, a NULL pointer with -22.  cf_param_name: the name of knob number index, NULL from the number of knobs on; it needs no
+ * context. */
 int cf_set_param(cf_ctx* ctx, const char* name, int64_t value);
+int cf_get_param(cf_ctx* ctx, const char* name, int64_t* value);
+const char* cf_param_name(int32_t index);
 
 /* Self-tests of the device primitives against host results (used by tests/ only). */
 int cf_selftest_sort(cf_ctx* ctx, const uint64_t* keys, int64_t n, int32_t bits, uint64_t* out);

@@ -127,27 +127,26 @@ def check_record(engine, pk, rec, loaded=False, through_exchange=False, rendezvo
         n, r = part["n_parts"], part["part"]
         rare = engine.kmers().copy()                       # the union set: what the all-gather of every owner's list installs
         lo, hi = r * pk.n_reads // n, (r + 1) * pk.n_reads // n
-        engine.set_param("comm_self_p2p", 1)
-        engine.comm_init(0, 1, rendezvous or os.path.join(os.environ.get("TMPDIR", "/tmp"), f"cf_bigparity_{os.getpid()}.id"))
-        try:
-            t0 = time.perf_counter(); engine.count_kmers(p["k"], lo, hi); secs["count_shard"] = time.perf_counter() - t0
-            t0 = time.perf_counter(); got["exchange_bytes"] = int(engine.exchange_table()); secs["table_exchange_self"] = time.perf_counter() - t0
-            t0 = time.perf_counter(); engine.select_rare(p["max_nonuniq"], p["lo"], p["hi"]); engine.allgather_kmers(); secs["select_gather_self"] = time.perf_counter() - t0
-            engine.set_kmers(rare, p["k"])
-            t0 = time.perf_counter(); engine.build_clouds(); secs["clouds_all_reads"] = time.perf_counter() - t0
-            ok["cloud_checksum_again"] = engine.checksum("clouds")[0] == rec["cloud_checksum"]
-            t0 = time.perf_counter(); got["gathered_cloud_entries"] = int(engine.allgather_clouds()); secs["cloud_gather_self"] = time.perf_counter() - t0
-            ok["gathered_view"] = got["gathered_cloud_entries"] == rec["n_cloud_entries"]
-            engine.reset_unique()
-            t0 = time.perf_counter()
-            ne = engine.dist_edges(0, 2 ** 62, p["min_d"], p["max_d"], p["min_cov"], p["rel_threshold"], r, n, edge_cap=part["n_edges"] + 16)
-            secs["dist_part"] = time.perf_counter() - t0
-            s3 = engine.stats()
-            echk = engine.edges_checksum()
-            uchk, n_u = engine.checksum("unique")
-        finally:
-            engine.comm_free()
-            engine.set_param("comm_self_p2p", 0)
+        with engine.knobs(comm_self_p2p=1):
+            engine.comm_init(0, 1, rendezvous or os.path.join(os.environ.get("TMPDIR", "/tmp"), f"cf_bigparity_{os.getpid()}.id"))
+            try:
+                t0 = time.perf_counter(); engine.count_kmers(p["k"], lo, hi); secs["count_shard"] = time.perf_counter() - t0
+                t0 = time.perf_counter(); got["exchange_bytes"] = int(engine.exchange_table()); secs["table_exchange_self"] = time.perf_counter() - t0
+                t0 = time.perf_counter(); engine.select_rare(p["max_nonuniq"], p["lo"], p["hi"]); engine.allgather_kmers(); secs["select_gather_self"] = time.perf_counter() - t0
+                engine.set_kmers(rare, p["k"])
+                t0 = time.perf_counter(); engine.build_clouds(); secs["clouds_all_reads"] = time.perf_counter() - t0
+                ok["cloud_checksum_again"] = engine.checksum("clouds")[0] == rec["cloud_checksum"]
+                t0 = time.perf_counter(); got["gathered_cloud_entries"] = int(engine.allgather_clouds()); secs["cloud_gather_self"] = time.perf_counter() - t0
+                ok["gathered_view"] = got["gathered_cloud_entries"] == rec["n_cloud_entries"]
+                engine.reset_unique()
+                t0 = time.perf_counter()
+                ne = engine.dist_edges(0, 2 ** 62, p["min_d"], p["max_d"], p["min_cov"], p["rel_threshold"], r, n, edge_cap=part["n_edges"] + 16)
+                secs["dist_part"] = time.perf_counter() - t0
+                s3 = engine.stats()
+                echk = engine.edges_checksum()
+                uchk, n_u = engine.checksum("unique")
+            finally:
+                engine.comm_free()
     else:
         engine.reset_unique()
         t0 = time.perf_counter()

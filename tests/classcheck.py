@@ -223,25 +223,17 @@ def run(engine, c, knobs=None, n_parts=1, edge_cap=None, classes=(1, 0)):
     shapecheck._check_clouds(engine, nv, what)
     knobs = dict(knobs or {})
     stats = None
-    try:
-        for name, value in knobs.items():
-            engine.set_param(name, value[0] if isinstance(value, tuple) else value)
-        for on in classes:
-            engine.set_param("dist_classes", on)
+    for on in classes:
+        with engine.knobs(**knobs, dist_classes=on):
             _dist(engine, c, nv, f"{what} {knobs} n_parts={n_parts} dist_classes={on}", n_parts, edge_cap)
             if on:
                 stats = engine.stats()
-    finally:
-        engine.set_param("dist_classes", 1)
-        for name, value in knobs.items():
-            if isinstance(value, tuple):
-                engine.set_param(name, value[1])
     return stats
 
 
 # small chunks of the edge output, a stage and a hot list that overflow: the rows of a member cross chunks, the late rows take the
 # marked-slot sweep, the filter runs inside the bucket scan
-TIGHT = dict(dist_edge_chunk=(16, 0), dist_stage=(4, 2048), dist_hot_cap=(8, 0))
+TIGHT = dict(dist_edge_chunk=16, dist_stage=4, dist_hot_cap=8)
 LAYOUTS = {k: stc.LAYOUTS[k] for k in ("wide", "regions26", "region_bytes", "one_workgroup")}
 
 
@@ -285,8 +277,8 @@ def run_repeated_rank(engine, doubled=True):
     """The clouds above through cf_set_clouds with the knob at 1: the results are the oracle's, with the class (set-like rows) and without
     it (a rank twice in a row: the classes switch off on the device)."""
     prove_repeated_rank_clouds()
-    engine.set_param("dist_classes", 1)
-    edges = pathcheck.check_clouds(engine, *repeated_rank_clouds(doubled), 1, 150, 4, 0.8).tolist()
+    with engine.knobs(dist_classes=1):
+        edges = pathcheck.check_clouds(engine, *repeated_rank_clouds(doubled), 1, 150, 4, 0.8).tolist()
     assert ([2, 0, 1, 4] in edges and [2, 2, 1, 4] in edges) == doubled, "the edges that only the doubled rank makes"
 
 

@@ -415,15 +415,12 @@ def check_batches(engine):
     assert want[0][1][1:] == (0, 2)
     default = engine.consensus_info()
     for batch_bytes in (2048, 700, 1):
-        engine.set_param("cons_batch_bytes", batch_bytes)
-        try:
+        with engine.knobs(cons_batch_bytes=batch_bytes):
             assert engine.consensus_info()["batch_bytes"] == batch_bytes
             assert check(engine, positions[:1], 3) == [w[:1] for w in want]
             assert engine.consensus_info()["n_batches"] >= 3 * 3
             assert check(engine, positions, 3) == want
             assert engine.consensus_info()["n_batches"] > default["n_batches"]
-        finally:
-            engine.set_param("cons_batch_bytes", 0)
     assert engine.consensus_info()["batch_bytes"] == default["batch_bytes"]
 
 

@@ -234,19 +234,11 @@ def run(engine, c, knobs=None, n_parts=1, edge_cap=None, groups=(1, 0)):
     shapecheck._check_clouds(engine, nv, what)
     knobs = dict(knobs or {})
     stats = None
-    try:
-        for name, value in knobs.items():
-            engine.set_param(name, value[0] if isinstance(value, tuple) else value)
-        for on in groups:
-            engine.set_param("dist_groups", on)
+    for on in groups:
+        with engine.knobs(**knobs, dist_groups=on):
             cc._dist(engine, c, nv, f"{what} {knobs} n_parts={n_parts} dist_groups={on}", n_parts, edge_cap)
             if on:
                 stats = engine.stats()
-    finally:
-        engine.set_param("dist_groups", 1)
-        for name, value in knobs.items():
-            if isinstance(value, tuple):
-                engine.set_param(name, value[1])
     return stats
 
 
@@ -256,8 +248,8 @@ LAYOUTS = cc.LAYOUTS
 
 def run_repeated_rank(engine, doubled=True):
     """classcheck.repeated_rank_clouds through cf_set_clouds with the knob at 1: a rank twice in a row makes every first k-mer a group that counts."""
-    engine.set_param("dist_groups", 1)
-    cc.run_repeated_rank(engine, doubled)
+    with engine.knobs(dist_groups=1):
+        cc.run_repeated_rank(engine, doubled)
 
 
 def run_exchange(lib, rendezvous, knobs=None, n_reads=250):

@@ -170,14 +170,11 @@ def check_case(src, case, window=0, log=None):
     want = case["expect"]
     t0, t1 = case["threshold"]
     query = [row[r] for r in want["reads"]]
-    e.set_param("map_window", window)
-    try:
+    with e.knobs(map_window=window):
         e.contig_build(b_reads, b_pos, case["f"])
         info = e.contig_info()
         cov = e.contig_coverage()
         pos, s0, s1 = e.map_reads(np.array(query, np.int64), (t0, t1))
-    finally:
-        e.set_param("map_window", 0)
     c = contig(unit_ptr, cloud_ptr, entries, b_reads, b_pos, case["f"])
     tag = case["name"]
     assert (c["P"], c["max_pos"], c["n_freq_kmers"]) == (want["P"], want["max_pos"], want["n_freq_kmers"]), f"{tag}: numpy contig vs reference"

@@ -177,8 +177,7 @@ def check(engine, case, window=0, reverse=False):
     # ---- the device
     mapcheck.install_synthetic(engine, ref["spec"])
     q = np.asarray(case.queries, np.int64)
-    engine.set_param("map_window", window)
-    try:
+    with engine.knobs(map_window=window):
         for order in ((1, -1) if reverse else (1,)):
             what = tag + (" (backbone reversed)" if order < 0 else "")
             engine.contig_build(ref["b_reads"][::order], ref["b_pos"][::order], case.f)
@@ -195,8 +194,6 @@ def check(engine, case, window=0, reverse=False):
                 got = _triples(*engine.score_reads(q, None, None, t0, t1))
                 bad = [(n, g, w) for n, g, w in zip(case.q_name, got, ref["score"][t]) if g != w]
                 assert not bad, f"{what}: score_reads under {(t0, t1)}: {len(bad)} of {len(got)} differ (name, device, numpy), first {bad[:3]}"
-    finally:
-        engine.set_param("map_window", 0)
     return ref
 
 
@@ -519,15 +516,12 @@ def check_past_the_launch_cap(engine):
     mapcheck.install_synthetic(engine, ref["spec"])
     engine.contig_build(ref["b_reads"], ref["b_pos"], case.f)
     assert engine.contig_info()["n_positions"] == ref["c"]["P"]
-    try:
-        for window in (64, 0):
-            engine.set_param("map_window", window)
+    for window in (64, 0):
+        with engine.knobs(map_window=window):
             got = _triples(*engine.map_reads(q, (t0, t1)))
             bad = [i for i in range(n) if got[i] != want[i]]
             assert not bad, (f"{case.name} (window {window}): {len(bad)} of {n} queries differ from mapcheck, first at query {bad[0]} "
                              f"(the {bad[0] // stride + 1}. of its workgroup, read {list(case.q_name)[draw[bad[0]]]}): {got[bad[0]]} for {want[bad[0]]}")
-    finally:
-        engine.set_param("map_window", 0)
     return dict(n_cu=n_cu, queries=n, workgroups=stride, mapped=mapped, several_windows_after_one=follow,
                 distinct_answers=len({tuple(w) for w in want}))
 

@@ -15,7 +15,6 @@ import sketchtailcheck as stc
 
 BATCH = 32      # members to a batch of the section: a bit each in a lane's selection word
 
-BASE = {}       # knobs the test file's engine runs under (the emulator's small launch shape): what a case's own knob goes back to
 _cases = {}
 
 
@@ -192,19 +191,10 @@ def run(engine, c, knobs=None, n_parts=1, edge_cap=None, once=(1, 0)):
     shapecheck._check_clouds(engine, nv, what)
     knobs = dict(knobs or {})
     stats = {}
-    try:
-        for name, value in knobs.items():
-            engine.set_param(name, value[0] if isinstance(value, tuple) else value)
-        engine.set_param("dist_groups", 1)
-        for on in once:
-            engine.set_param("dist_filter_once", on)
+    for on in once:
+        with engine.knobs(**knobs, dist_groups=1, dist_filter_once=on):
             cc._dist(engine, c, nv, f"{what} {knobs} n_parts={n_parts} dist_filter_once={on}", n_parts, edge_cap)
             stats[on] = engine.stats()
-    finally:
-        engine.set_param("dist_filter_once", 1)
-        for name, value in knobs.items():
-            if isinstance(value, tuple):
-                engine.set_param(name, BASE.get(name, value[1]))
     return stats
 
 
@@ -217,8 +207,8 @@ CASES = {
     "core_min_cov_2": _core(2),
     "core_min_cov_4": _core(4),
     # 120 rows of one group over chunks of 16 rows: the rows of a batch cross several chunk borders and exceed a chunk; then rows beyond the cap
-    "rows_chunk_16": lambda e: run(e, cc.case("rows"), dict(dist_edge_chunk=(16, 0))),
-    "rows_edge_cap_50": lambda e: run(e, cc.case("rows"), dict(dist_edge_chunk=(16, 0)), edge_cap=50),
+    "rows_chunk_16": lambda e: run(e, cc.case("rows"), dict(dist_edge_chunk=16)),
+    "rows_edge_cap_50": lambda e: run(e, cc.case("rows"), dict(dist_edge_chunk=16), edge_cap=50),
     # the batch borders
     "members_32": lambda e: run(e, flat(32, 3)),
     "members_33": lambda e: run(e, flat(33, 3)),
@@ -227,21 +217,21 @@ CASES = {
     "members_256": lambda e: run(e, cc.case("big")),
     # a hot list longer than the workgroup (150 slots, 128 threads: a thread takes two); with a list cap of 8 the list overflows, the scan's
     # list overflows too (150 > 8) and the launch filters member by member whatever the knob says: the fall-back
-    "hot_150_block_128": lambda e: run(e, flat(3, 150), dict(dist_block=(128, 0))),
-    "hot_150_cap_8": lambda e: run(e, flat(3, 150), dict(dist_block=(128, 0), dist_hot_cap=(8, 0))),
+    "hot_150_block_128": lambda e: run(e, flat(3, 150), dict(dist_block=128)),
+    "hot_150_cap_8": lambda e: run(e, flat(3, 150), dict(dist_block=128, dist_hot_cap=8)),
     # ... and with no first k-mer keeping the inserts' list (dist_hot_entries 0): the filter's scan makes the list, over the insert queues, and
     # its 150 slots fit it — the section reads the scan's list
-    "hot_150_scan": lambda e: run(e, flat(3, 150), dict(dist_block=(128, 0), dist_hot_entries=(0, 32768))),
+    "hot_150_scan": lambda e: run(e, flat(3, 150), dict(dist_block=128, dist_hot_entries=0)),
     # one b at as many distances as a thread keeps masks in registers, and at one more (the walk per member): the total must be the whole one
     "keys_K": lambda e: run(e, keys(MEMBER_KEYS)),
     "keys_K_plus_1": lambda e: run(e, keys(MEMBER_KEYS + 1)),
     # the same with b's chain beginning in the last bucket of the table: the walk goes on in bucket 0
-    "keys_K_wrap": lambda e: run(e, keys(MEMBER_KEYS, wrap=True), dict(dist_slots=(WRAP_SLOTS, 0))),
-    "keys_K_plus_1_wrap": lambda e: run(e, keys(MEMBER_KEYS + 1, wrap=True), dict(dist_slots=(WRAP_SLOTS, 0))),
+    "keys_K_wrap": lambda e: run(e, keys(MEMBER_KEYS, wrap=True), dict(dist_slots=WRAP_SLOTS)),
+    "keys_K_plus_1_wrap": lambda e: run(e, keys(MEMBER_KEYS + 1, wrap=True), dict(dist_slots=WRAP_SLOTS)),
     # a member whose only hot slot is itself: no row, no unique bit, while the other member has its row
     "self_only": lambda e: run(e, self_only()),
     # rows of several groups over chunks of 16 rows, reserved by several workgroups at the same time
-    "many_chunks": lambda e: run(e, many_chunks(), dict(dist_edge_chunk=(16, 0))),
+    "many_chunks": lambda e: run(e, many_chunks(), dict(dist_edge_chunk=16)),
     # a union table that splits: rows of one group from more than one pass
     "split_table": lambda e: _split(e),
     # a group without a hot slot between groups with rows
@@ -257,5 +247,5 @@ CASES = {
 
 def _split(e):
     c = flat(3, 200)
-    st = run(e, c, dict(dist_slots=(256, 0)))
+    st = run(e, c, dict(dist_slots=256))
     assert st[1]["n_spilled"] > 0 and st[0]["n_spilled"] > 0, "200 keys do not fit 70 % of 256 slots: the table splits"

@@ -501,9 +501,8 @@ def check_batches(eng, L=300):
     rw1 = (L + 15) // 16 + 1
     areas = sorted(len(r) * rw1 * 4 for r in reads if r)
     want = None
-    try:
-        for bb, n_batches in ((0, 1), (areas[-1] + areas[-2], None), (areas[0], 7), (100, 7)):
-            eng.set_param("monodec_batch_bytes", bb)
+    for bb, n_batches in ((0, 1), (areas[-1] + areas[-2], None), (areas[0], 7), (100, 7)):
+        with eng.knobs(monodec_batch_bytes=bb):
             info, ptr, inst, want = check(eng, monos, reads, wants=want)
             got = eng.monodec_info()
             assert got["n_move_pairs"] == 7 and got["n_score_pairs"] == 14 and got["n_reads"] == 8
@@ -511,8 +510,6 @@ def check_batches(eng, L=300):
                 assert got["n_batches"] == n_batches, (bb, got)
             else:
                 assert 1 < got["n_batches"] < 7
-    finally:
-        eng.set_param("monodec_batch_bytes", 0)
 
 
 def check_more_pairs_than_the_launch_cap(eng):

@@ -22,8 +22,6 @@ import numpy as np
 from conftest import lines_from_placement
 from oracle import placer
 
-KNOB_DEFAULTS = {"place_mode": 2, "place_grid": 0, "place_block": 0, "place_row_words": 0, "place_slots_per_unit": 0, "place_fused": 1,
-                 "place_l3": 0, "place_l3_shift": 0, "place_cmap_bits": 0, "place_long_rescans": 2}
 MODES = (1, 2, 3)
 
 
@@ -170,13 +168,8 @@ def run(engine, case, mode, knobs=None, installed=False):
     k = dict(case.knobs, **(knobs or {}))
     k["place_mode"] = mode
     k.setdefault("place_long_rescans", 1000000)
-    try:
-        for name, v in k.items():
-            engine.set_param(name, v)
+    with engine.knobs(**k):
         out = engine.place_reads(case.classes, case.id_rank, *case.params)
-    finally:
-        for name in k:
-            engine.set_param(name, KNOB_DEFAULTS[name])
     return lines_from_placement(case.ids, *[x.tolist() for x in out])
 
 

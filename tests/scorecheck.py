@@ -165,8 +165,7 @@ def check_case(src, case, window=0):
     assert not bad, f"{tag}: {len(bad)} numpy rows differ from the reference, first {bad[:2]}"
     for m in SPREAD_MAX_NPOS:
         assert spread_figures(entries, c, m) == case["spread"][str(m)], f"{tag}: numpy spread k-mers, max_npos {m}"
-    e.set_param("map_window", window)
-    try:
+    with e.knobs(map_window=window):
         e.contig_build(b_reads, b_pos, case["f"])
         info = e.contig_info()
         assert info["max_pos"] == case["max_pos"] and e.contig_exact_info()["n_exact_pairs"] == case["n_exact_pairs"], tag
@@ -176,8 +175,6 @@ def check_case(src, case, window=0):
         sub = _triples(*e.score_reads(q, a, b, t0, t1))
         one = _triples(*e.score_reads(q, c0, c0, 0, 0))
         inner = e.score_reads(q, None, None, *INNER)
-    finally:
-        e.set_param("map_window", 0)
     from centroflye_amd.read_mapper import kept_by_map_reads
     keep = kept_by_map_reads(*inner, (t0, t1))
     verdicts = [[1] + t if k else [0] for t, k in zip(_triples(*inner), keep.tolist())]
@@ -252,8 +249,7 @@ def check_synthetic(engine, window=0):
     ref = synthetic_reference()
     mapcheck.install_synthetic(engine, ref["spec"])
     c, R, lo, hi, cut, q = (ref[k] for k in ("c", "R", "lo", "hi", "cut", "q"))
-    engine.set_param("map_window", window)
-    try:
+    with engine.knobs(map_window=window):
         engine.contig_build(ref["b_reads"], ref["b_pos"], ref["f"])
         assert engine.contig_info()["max_pos"] == c["max_pos"] and engine.contig_exact_info()["n_exact_pairs"] == c["n_exact_pairs"]
         full = _triples(*engine.score_reads(None, None, None, 2, 10))
@@ -264,8 +260,6 @@ def check_synthetic(engine, window=0):
         at_won = _triples(*engine.score_reads(None, won, won, 0, 0))
         some = _triples(*engine.score_reads(q, lo[q], hi[q], 1, 1))
         spreads = {m: engine.contig_spread(m) for m in ref["spread"]}
-    finally:
-        engine.set_param("map_window", 0)
     assert full == ref["full"], "full ranges"
     assert over == ref["over"], "overhang ranges"
     assert sub == ref["sub"], "sub-ranges"
@@ -325,13 +319,10 @@ def check_past_the_launch_cap(src, case):
     t0, t1 = case["threshold"]
     e.contig_build([row[r] for r, _ in case["backbone"]], [p for _, p in case["backbone"]], case["f"])
     assert e.contig_info()["max_pos"] == case["max_pos"]
-    try:
-        for window in (3, 0):
-            e.set_param("map_window", window)
+    for window in (3, 0):
+        with e.knobs(map_window=window):
             got = _triples(*e.score_reads(q, lo, hi, t0, t1))
             bad = [i for i in range(n) if got[i] != want[i]]
             assert not bad, (f"{case['name']} (window {window}): {len(bad)} of {n} queries differ from the reference, first at query {bad[0]} "
                              f"(the {bad[0] // stride + 1}. of its workgroup): {got[bad[0]]} for {want[bad[0]]}")
-    finally:
-        e.set_param("map_window", 0)
     return dict(n_cu=n_cu, queries=n, workgroups=stride, placed=placed, distinct_answers=len({tuple(w) for w in want}))

@@ -48,7 +48,7 @@ class Traced:
 
     def __getattr__(self, name):
         f = getattr(self.engine, name)
-        if not callable(f) or name in ("stats", "times", "set_param"):
+        if not callable(f) or name in ("stats", "times", "set_param", "get_param", "knobs"):
             return f
 
         def call(*a, **kw):
@@ -106,11 +106,8 @@ def _place(e, case):
     cp, ent = e.clouds()
     want = placer.place_reads(ids, cls.astype(np.int64), unit_ptr, cp, ent, 2, 2, 10, 3)
     for mode in (1, 2):
-        e.set_param("place_mode", mode)
-        try:
+        with e.knobs(place_mode=mode):
             rd, pos, s0, s1 = e.place_reads(cls, np.arange(R, dtype=np.int32), 2, 2, 10, 3)
-        finally:
-            e.set_param("place_mode", 2)
         got = [f"{ids[a]} 0" if (c < 0 and b == 0) else (f"{ids[a]} None" if b < 0 else f"{ids[a]} {b} {c} {d}")
                for a, b, c, d in zip(rd.tolist(), pos.tolist(), s0.tolist(), s1.tolist())]
         assert got == want, f"{case['name']}: placement, place_mode {mode}"

@@ -265,20 +265,16 @@ def run(engine, c, cap=GROUP_MAX, n_parts=1, groups=True):
     assert engine.select_rare(c["max_nonuniq"], c["lo"], c["hi"]) == len(nv["rare_kmers"])
     assert np.array_equal(engine.kmers(), nv["set_codes"])
     shapecheck._check_clouds(engine, nv, what)
-    engine.set_param("dist_groups", 1)
-    engine.set_param("dist_group_cap", cap)
-    try:
+    with engine.knobs(dist_groups=1, dist_group_cap=cap):
         cc._dist(engine, c, nv, f"{what} cap={cap} n_parts={n_parts}", n_parts)
         st = engine.stats()
-        if groups:
-            if n_parts == 1:
-                check_passes(c, st, cap)
-                if cap == GROUP_MAX and gc.mixed_groups(c, cap):
-                    gc.check_ran_in_groups(c, st, cap)
-            else:      # (cc._dist leaves the stats of the last partition)
-                check_passes(c, st, cap, n_parts - 1, n_parts)
-    finally:
-        engine.set_param("dist_group_cap", GROUP_MAX)
+    if groups:
+        if n_parts == 1:
+            check_passes(c, st, cap)
+            if cap == GROUP_MAX and gc.mixed_groups(c, cap):
+                gc.check_ran_in_groups(c, st, cap)
+        else:      # (cc._dist leaves the stats of the last partition)
+            check_passes(c, st, cap, n_parts - 1, n_parts)
     return st
 
 

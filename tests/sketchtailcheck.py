@@ -168,27 +168,19 @@ def run(engine, c, knobs=None):
     assert np.array_equal(engine.kmers(), nv["set_codes"])
     shapecheck._check_clouds(engine, nv, what)
     knobs = dict(knobs or {})
-    try:
-        for name, value in knobs.items():
-            engine.set_param(name, value[0] if isinstance(value, tuple) else value)
-        for tail in (1, 0):
-            engine.set_param("dist_sketch_tail", tail)
+    for tail in (1, 0):
+        with engine.knobs(**knobs, dist_sketch_tail=tail):
             shapecheck._check_dist(engine, c, nv, f"{what} {knobs} dist_sketch_tail={tail}")
-    finally:
-        engine.set_param("dist_sketch_tail", 1)
-        for name, value in knobs.items():
-            if isinstance(value, tuple):
-                engine.set_param(name, value[1])
     return engine.stats()
 
 
-# (knob, (value, value to go back to)): the other table layouts, a table that splits, byte counters, one workgroup per CU
+# the other table layouts, a table that splits, byte counters, one workgroup per CU
 LAYOUTS = {
-    "wide": dict(dist_wide=(1, 0)),
-    "regions26": dict(dist_regions=(2, 0)),
-    "region_bytes": dict(dist_regions=(2, 0), dist_region_bytes=(1, 0)),
-    "sketch_bytes": dict(dist_sketch_bits=(8, 0)),
-    "one_workgroup": dict(dist_wgs=(1, 0)),
+    "wide": dict(dist_wide=1),
+    "regions26": dict(dist_regions=2),
+    "region_bytes": dict(dist_regions=2, dist_region_bytes=1),
+    "sketch_bytes": dict(dist_sketch_bits=8),
+    "one_workgroup": dict(dist_wgs=1),
 }
 PARAMS = [dict(min_cov=1), dict(min_cov=2), dict(min_cov=4), dict(max_d=12), dict(max_d=5), dict(min_d=2), dict(min_d=2, max_d=12, min_cov=2)]
 
@@ -216,11 +208,8 @@ def run_repeated_rank(engine):
     import pathcheck
     unit_ptr, cloud_ptr, entries, n_kmers = repeated_rank_clouds()
     for tail in (1, 0):
-        engine.set_param("dist_sketch_tail", tail)
-        try:
+        with engine.knobs(dist_sketch_tail=tail):
             edges = pathcheck.check_clouds(engine, unit_ptr, cloud_ptr, entries, n_kmers, 1, 150, 4, 0.8)
-        finally:
-            engine.set_param("dist_sketch_tail", 1)
         assert [2, 0, 1, 4] in edges.tolist(), "the case lost its edge"
 
 

@@ -32,8 +32,8 @@ def test_classes_of_2_and_3_members_that_select_each_other_and_near_misses(engin
 @pytest.mark.parametrize("bits", [1, 3])
 def test_different_lists_with_one_hash_are_not_merged(engine, bits):
     """One or three hash bits: the six different lists that begin in unit 0 of read 0 collide; the comparison of the lists decides."""
-    cc.run(engine, cc.case("core"), dict(dist_class_bits=(bits, 16)))
-    cc.run(engine, cc.case("big"), dict(dist_class_bits=(bits, 16)))
+    cc.run(engine, cc.case("core"), dict(dist_class_bits=bits))
+    cc.run(engine, cc.case("big"), dict(dist_class_bits=bits))
 
 
 def test_a_run_of_equal_lists_longer_than_the_member_cap(engine):
@@ -47,14 +47,14 @@ def test_core_reads_in_the_other_layouts(engine, layout):
 
 
 def test_a_class_whose_table_splits(engine):
-    st = cc.run(engine, cc.case("big", min_cov=2), dict(dist_slots=(256, BASE["dist_slots"])))
+    st = cc.run(engine, cc.case("big", min_cov=2), dict(dist_slots=256))
     assert st["n_spilled"] > 0
 
 
 @pytest.mark.parametrize("min_cov", [2, 4])
 def test_rows_of_a_class_across_edge_chunks_with_marked_slot_sweep_and_in_scan_filter(engine, min_cov):
     cc.run(engine, cc.case("rows", min_cov=min_cov), cc.TIGHT)
-    cc.run(engine, cc.case("rows", min_cov=min_cov), dict(dist_edge_chunk=(16, 0)))
+    cc.run(engine, cc.case("rows", min_cov=min_cov), dict(dist_edge_chunk=16))
 
 
 def test_edge_cap_below_the_rows(engine):

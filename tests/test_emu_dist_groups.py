@@ -49,7 +49,7 @@ def test_unions_of_32_and_33_postings_and_a_list_of_33_on_its_own(engine, name):
 @pytest.mark.parametrize("cap", [2, 5])
 def test_a_small_cap_closes_the_groups_early(engine, cap):
     for c in (gc.case("core"), gc.case("u32")):
-        gc.check_ran_in_groups(c, gc.run(engine, c, dict(dist_group_cap=(cap, 32))), cap)
+        gc.check_ran_in_groups(c, gc.run(engine, c, dict(dist_group_cap=cap)), cap)
 
 
 @pytest.mark.parametrize("layout", list(gc.LAYOUTS))
@@ -59,7 +59,7 @@ def test_core_reads_in_the_other_layouts(engine, layout):
 
 
 def test_a_union_table_that_splits(engine):
-    st = gc.run(engine, cc.case("big", min_cov=2), dict(dist_slots=(256, BASE["dist_slots"])))
+    st = gc.run(engine, cc.case("big", min_cov=2), dict(dist_slots=256))
     assert st["n_spilled"] > 0
     gc.check_ran_in_groups(cc.case("big", min_cov=2), st)      # (groups whose members differ, from the naive clouds; the passes are not pinned when a table split)
 
@@ -82,7 +82,7 @@ def test_tail_items_beyond_d_star_of_the_union(engine):
     (a,) = stc._ranks(c["naive"], stc.reads_of(stc.core_layout()[0], 500, 21)[2], [stc.A])
     assert [g for g in gc.mixed_groups(c) if a in g[0]], "A in a group with k-mers of other lists"
     gc.check_ran_in_groups(c, gc.run(engine, c))
-    gc.check_ran_in_groups(c, gc.run(engine, c, dict(dist_sketch_tail=(0, 1))))
+    gc.check_ran_in_groups(c, gc.run(engine, c, dict(dist_sketch_tail=0)))
 
 
 def test_two_partitions(engine):

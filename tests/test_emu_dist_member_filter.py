@@ -14,9 +14,7 @@ def engine(emu_lib):
     e = Engine(0, emu_lib)
     for name, value in BASE.items():
         e.set_param(name, value)
-    mf.BASE = dict(BASE)
     yield e
-    mf.BASE = {}
     e.close()
 
 
@@ -27,8 +25,5 @@ def test_member_filter_case(engine, name):
 
 def test_counting_groups_of_clouds_that_are_not_sets(engine):
     for once in (1, 0):
-        engine.set_param("dist_filter_once", once)
-        try:
+        with engine.knobs(dist_filter_once=once):
             gc.run_repeated_rank(engine)
-        finally:
-            engine.set_param("dist_filter_once", 1)

@@ -41,7 +41,7 @@ def test_core_reads_in_the_other_layouts(engine, layout):
 
 
 def test_core_reads_with_a_table_that_splits(engine):
-    st = stc.run(engine, stc.case("core", min_cov=2), dict(dist_slots=(256, BASE["dist_slots"])))
+    st = stc.run(engine, stc.case("core", min_cov=2), dict(dist_slots=256))
     assert st["n_spilled"] > 0
 
 

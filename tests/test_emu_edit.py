@@ -82,8 +82,7 @@ def test_the_limit(eng, small):
 @pytest.mark.parametrize("lds_diags", [64, 3, 1])
 def test_both_sides_of_the_lds_hbm_switch(eng, small, lds_diags):
     """The knob moves the switch point down so that the pairs around it stay small; the default one is taken on hardware."""
-    eng.set_param("edit_lds_diags", lds_diags)
-    try:
+    with eng.knobs(edit_lds_diags=lds_diags):
         assert eng.edit_info()["lds_diags"] == lds_diags
         cases = ec.switch_cases(max(lds_diags, 8))
         for name, a, b in cases:
@@ -97,8 +96,6 @@ def test_both_sides_of_the_lds_hbm_switch(eng, small, lds_diags):
         assert d.tolist() == [ec.nw(c[1], c[2]) for c in mixed]
         d, _ = eng.edit_distances(aa + bb, a_off, b_off, 100)
         assert d.tolist() == [w if w <= 100 else -1 for w in (ec.nw(c[1], c[2]) for c in mixed)]
-    finally:
-        eng.set_param("edit_lds_diags", 0)
     assert eng.edit_info()["lds_diags"] == G["shape"]["lds_diags"]
 
 

@@ -39,10 +39,9 @@ def test_placement_argmax_reduction(engine):
 def test_stage2_small(engine, report, oracle_stage2):
     # max_distance 2 keeps the emulated dist kernel to a few 10^5 emissions
     tup = oracle_stage2("lowcov", max_distance=2)
-    engine.set_param("dist_slots", 2048)
-    engine.set_param("dist_block", 128)
-    pathcheck.check_stage2(engine, report("lowcov"), tup)
-    assert engine.stats()["n_spilled"] == 0
+    with engine.knobs(dist_slots=2048, dist_block=128):
+        pathcheck.check_stage2(engine, report("lowcov"), tup)
+        assert engine.stats()["n_spilled"] == 0
 
 
 @pytest.mark.parametrize("bits", [4, 8])
@@ -51,15 +50,10 @@ def test_sketch_counters_of_four_bits_and_of_eight(engine, report, oracle_stage2
     takes itself back, the add that would wrap a field is seen and the first k-mer falls back to "every b marked") — same results as with
     bytes; the synthetic clouds give ONE k-mer 300 postings, i.e. pairs counted far beyond 15 and beyond 255."""
     tup = oracle_stage2("lowcov", max_distance=2)
-    engine.set_param("dist_slots", 2048)
-    engine.set_param("dist_block", 128)
-    engine.set_param("dist_sketch_bits", bits)
-    try:
+    with engine.knobs(dist_slots=2048, dist_block=128, dist_sketch_bits=bits):
         pathcheck.check_stage2(engine, report("lowcov"), tup)
-        engine.set_param("dist_slots", 4096)
-        pathcheck.check_synthetic_clouds(engine)
-    finally:
-        engine.set_param("dist_sketch_bits", 0)
+        with engine.knobs(dist_slots=4096):
+            pathcheck.check_synthetic_clouds(engine)
 
 
 @pytest.mark.parametrize("chunk", [1, 7, 64])
@@ -67,61 +61,39 @@ def test_edge_output_chunks_and_holes(engine, report, oracle_stage2, chunk):
     """Workgroups reserve the edge output in chunks; a pass that does not fit the rest of a chunk continues in the next one, the
     unused rest of every workgroup's last chunk is a hole that is closed after the kernel: tiny chunks make both happen often."""
     tup = oracle_stage2("lowcov", max_distance=2)
-    engine.set_param("dist_edge_chunk", chunk)
-    try:
+    with engine.knobs(dist_slots=4096, dist_block=128, dist_edge_chunk=chunk):
         pathcheck.check_stage2(engine, report("lowcov"), tup, n_parts=2, check_table=False)
-    finally:
-        engine.set_param("dist_edge_chunk", 0)
 
 
 def test_stage2_wide_table_layout(engine, report, oracle_stage2):
     # 8-byte slots (any k-mer set size); the default above is the 6-byte layout (ranks < 2^24, counts < 2^15)
     tup = oracle_stage2("lowcov", max_distance=2)
-    engine.set_param("dist_wide", 1)
-    try:
-        engine.set_param("dist_slots", 1024)
+    with engine.knobs(dist_wide=1, dist_slots=1024, dist_block=128):
         pathcheck.check_stage2(engine, report("lowcov"), tup, check_table=False)
-        engine.set_param("dist_slots", 256)   # spill path of the wide layout, every pair in the exact table (no sketch)
-        engine.set_param("dist_stage", 2)
-        engine.set_param("dist_sketch", 0)
-        pathcheck.check_stage2(engine, report("lowcov"), tup, n_parts=2, check_table=False)
-        assert engine.stats()["n_spilled"] > 0
-    finally:
-        engine.set_param("dist_wide", 0)
-        engine.set_param("dist_stage", 2048)
-        engine.set_param("dist_sketch", 1)
+        # spill path of the wide layout, every pair in the exact table (no sketch)
+        with engine.knobs(dist_slots=256, dist_stage=2, dist_sketch=0):
+            pathcheck.check_stage2(engine, report("lowcov"), tup, n_parts=2, check_table=False)
+            assert engine.stats()["n_spilled"] > 0
 
 
 def test_filter_falls_back_when_its_hot_list_is_full(engine, report, oracle_stage2):
     """The filter compacts the slots that reach min_cov into an LDS list and evaluates the list; more such slots than the
     list holds are evaluated inside the bucket scan instead (never seen with the sketch at real sizes: forced here)."""
     tup = oracle_stage2("lowcov", max_distance=2)
-    engine.set_param("dist_slots", 2048)
-    engine.set_param("dist_block", 128)
-    engine.set_param("dist_hot_cap", 3)
-    try:
+    with engine.knobs(dist_slots=2048, dist_block=128, dist_hot_cap=3):
         pathcheck.check_stage2(engine, report("lowcov"), tup, check_table=False)
-        engine.set_param("dist_wide", 1)
-        pathcheck.check_stage2(engine, report("lowcov"), tup, check_table=False)
-    finally:
-        engine.set_param("dist_wide", 0)
-        engine.set_param("dist_hot_cap", 0)
+        with engine.knobs(dist_wide=1):
+            pathcheck.check_stage2(engine, report("lowcov"), tup, check_table=False)
 
 
 def test_stage2_spill_and_partition(engine, report, oracle_stage2):
     tup = oracle_stage2("lowcov", max_distance=2)
-    engine.set_param("dist_slots", 256)   # forces the (b, d) table to be split by a second hash of b
-    engine.set_param("dist_block", 64)
-    engine.set_param("dist_stage", 3)     # with the small chunks of the edge output below: rows that do not fit the rest of a chunk are
-    engine.set_param("dist_edge_chunk", 16)   # often more than the staged list holds -> the marked-slot sweep writes them
-    engine.set_param("dist_sketch", 0)    # every (b, d) pair goes to the exact table
-    try:
+    # dist_slots 256 forces the (b, d) table to be split by a second hash of b; dist_stage 3 with the small chunks of the edge output:
+    # rows that do not fit the rest of a chunk are often more than the staged list holds -> the marked-slot sweep writes them;
+    # dist_sketch 0: every (b, d) pair goes to the exact table
+    with engine.knobs(dist_slots=256, dist_block=64, dist_stage=3, dist_edge_chunk=16, dist_sketch=0):
         pathcheck.check_stage2(engine, report("lowcov"), tup, n_parts=3, check_table=False)
         assert engine.stats()["n_spilled"] > 0
-    finally:
-        engine.set_param("dist_sketch", 1)
-        engine.set_param("dist_stage", 2048)
-        engine.set_param("dist_edge_chunk", 0)
 
 
 def test_postings_of_one_partition_by_sort_and_by_atomics(engine, report, oracle_stage2):
@@ -129,47 +101,31 @@ def test_postings_of_one_partition_by_sort_and_by_atomics(engine, report, oracle
     kept cloud entries per unit and sorting them on rank / n_parts; the histogram + fill passes of atomics stay behind a knob."""
     tup = oracle_stage2("lowcov", max_distance=2)
     for atomics in (0, 1):
-        engine.set_param("dist_post_atomics", atomics)
-        try:
+        with engine.knobs(dist_slots=256, dist_block=64, dist_post_atomics=atomics):
             pathcheck.check_stage2(engine, report("lowcov"), tup, n_parts=3, check_table=False)
-        finally:
-            engine.set_param("dist_post_atomics", 0)
 
 
 def test_long_posting_lists_take_the_multi_chunk_path(engine):
-    engine.set_param("dist_slots", 4096)
-    engine.set_param("dist_block", 128)
-    pathcheck.check_synthetic_clouds(engine)                      # 300 postings of k-mer 0 > 256 per chunk
-    pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=40, max_d=7, min_d=3, seed=5)
+    with engine.knobs(dist_slots=4096, dist_block=128):
+        pathcheck.check_synthetic_clouds(engine)                      # 300 postings of k-mer 0 > 256 per chunk
+        pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=40, max_d=7, min_d=3, seed=5)
 
 
 def test_max_distance_beyond_255_takes_the_16_bit_distance_layout(engine):
     """--max-distance > 255 (the reference has no limit): [b:32 | d:16 | sel:1 | cnt:15] slots; one read of 330 units, so
     distances up to 320 occur and unit indices pass 255."""
-    engine.set_param("dist_slots", 4096)
-    engine.set_param("dist_block", 128)
-    try:
+    with engine.knobs(dist_slots=4096, dist_block=128):
         pathcheck.check_synthetic_clouds(engine, n_reads=1, n_units=330, cloud=3, n_kmers=25, max_d=320, seed=3)
-    finally:
-        engine.set_param("dist_slots", 0)
-        engine.set_param("dist_block", 0)
 
 
 @pytest.mark.parametrize("dbits,n_units", [(5, 30), (6, 60), (7, 100)])
 def test_narrow_slots_with_fewer_distance_bits(engine, dbits, n_units):
     """6-byte slots [d : DB | b : 32 - DB]: k-mer sets beyond 2^24 keep them when the reads are short enough in units;
     here the split is forced on small sets, the longest read makes distances up to n_units - 1 (just inside DB bits)."""
-    engine.set_param("dist_slots", 4096)
-    engine.set_param("dist_block", 128)
-    engine.set_param("dist_dbits", dbits)
-    try:
+    with engine.knobs(dist_slots=4096, dist_block=128, dist_dbits=dbits):
         pathcheck.check_synthetic_clouds(engine, n_reads=3, n_units=n_units, cloud=4, n_kmers=50, max_d=150, seed=dbits)
         with pytest.raises(DeviceError, match="dist_dbits"):      # one unit more than DB bits can tell apart
             pathcheck.check_synthetic_clouds(engine, n_reads=1, n_units=(1 << dbits) + 1, cloud=2, n_kmers=20, max_d=150, seed=1)
-    finally:
-        engine.set_param("dist_dbits", 0)
-        engine.set_param("dist_slots", 0)
-        engine.set_param("dist_block", 0)
 
 
 @pytest.mark.parametrize("regions,stream_bytes", [(1, 0), (2, 0), (8, 0), (2, 1)])
@@ -179,28 +135,16 @@ def test_region_layout_of_the_six_byte_slots(engine, report, oracle_stage2, regi
     Both streams: four bytes per entry [unit index mod 64 | rank : 26] with the "64 or more" position in the item record
     (up to 2^26 ranks and 128 units per read: round 4) — the last case below has 250 units and takes the other one — and rank
     and unit index apart (round 3; stream_bytes = 1 forces it)."""
-    engine.set_param("dist_regions", regions)
-    engine.set_param("dist_region_bytes", stream_bytes)
-    engine.set_param("dist_block", 128)
-    try:
-        engine.set_param("dist_slots", 2048)
+    with engine.knobs(dist_regions=regions, dist_region_bytes=stream_bytes, dist_block=128, dist_slots=2048):
         pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov", max_distance=2), check_table=False)
-        engine.set_param("dist_slots", 256)
-        engine.set_param("dist_sketch", 0)        # every pair in the exact table: full buckets, chains, partition splits
-        pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=40, cloud=6, n_kmers=60, max_d=7, min_d=1, seed=regions)
-        engine.set_param("dist_sketch", 1)
-        engine.set_param("dist_slots", 4096)
-        pathcheck.check_synthetic_clouds(engine, n_reads=1, n_units=250, cloud=3, n_kmers=25, max_d=240, seed=3)      # distances up to 240
-        # reads of 65 .. 128 units: distances on both sides of 64, items whose "64 or more" position lies inside, before and behind them
-        if (regions, stream_bytes) == (2, 0):
-            pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=128, cloud=4, n_kmers=30, max_d=127, seed=13)
-            pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=90, cloud=12, n_kmers=60, max_d=89, seed=23)      # long partner ranges: several items per posting
-    finally:
-        engine.set_param("dist_regions", 0)
-        engine.set_param("dist_region_bytes", 0)
-        engine.set_param("dist_sketch", 1)
-        engine.set_param("dist_slots", 0)
-        engine.set_param("dist_block", 0)
+        with engine.knobs(dist_slots=256, dist_sketch=0):       # every pair in the exact table: full buckets, chains, partition splits
+            pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=40, cloud=6, n_kmers=60, max_d=7, min_d=1, seed=regions)
+        with engine.knobs(dist_slots=4096):
+            pathcheck.check_synthetic_clouds(engine, n_reads=1, n_units=250, cloud=3, n_kmers=25, max_d=240, seed=3)      # distances up to 240
+            # reads of 65 .. 128 units: distances on both sides of 64, items whose "64 or more" position lies inside, before and behind them
+            if (regions, stream_bytes) == (2, 0):
+                pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=128, cloud=4, n_kmers=30, max_d=127, seed=13)
+                pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=90, cloud=12, n_kmers=60, max_d=89, seed=23)      # long partner ranges: several items per posting
 
 
 def test_stage3_against_reference_golden(engine, report, golden):
@@ -235,24 +179,18 @@ def test_stage3_launch_shapes_and_region_restart(engine, report, golden, knobs):
     # more than 2^32 slots give up BEFORE allocating — ADVICE round 4 — and the hash-map path takes over: the same lines)
     # ({"place_cmap_bits": 3}: the contig's overflow map starts with 8 slots and has to grow — round 5: a full map used to enlarge the score
     # regions instead, probing every slot at every add meanwhile; with regions that start too small on top, both kinds of restart in one run)
-    defaults = {"place_mode": 2, "place_grid": 0, "place_block": 0, "place_row_words": 0, "place_slots_per_unit": 0, "place_fused": 1, "place_l3": 0, "place_cmap_bits": 0}
     # (the emulated device is made small for that case — 65 536 slots per unit of this fixture's few reads are 1 GB, which a 64 GB device
     # takes: 46 s of clearing on the host — and place_mode 3, which never falls back, must say why it gives up)
     small_device = knobs.get("place_slots_per_unit") == 1 << 16
     try:
         if small_device:
             os.environ["CFEMU_TOTAL_MB"] = "256"
-            engine.set_param("place_mode", 3); engine.set_param("place_slots_per_unit", 1 << 16)
-            with pytest.raises(DeviceError, match="more than the device has free"):
+            with engine.knobs(place_mode=3, place_slots_per_unit=1 << 16), pytest.raises(DeviceError, match="more than the device has free"):
                 pathcheck.check_stage3(engine, pk, records, alns, lens, gk, g["stage3"], expect_lines=g["read_positions"])
-            engine.set_param("place_mode", 2)
-        for k, v in knobs.items():
-            engine.set_param(k, v)
-        pathcheck.check_stage3(engine, pk, records, alns, lens, gk, g["stage3"], expect_lines=g["read_positions"])
+        with engine.knobs(**knobs):
+            pathcheck.check_stage3(engine, pk, records, alns, lens, gk, g["stage3"], expect_lines=g["read_positions"])
     finally:
         os.environ.pop("CFEMU_TOTAL_MB", None)
-        for k, v in defaults.items():
-            engine.set_param(k, v)
 
 
 def test_placement_third_level_of_the_argmax_on_several_groups(engine):
@@ -264,8 +202,7 @@ def test_placement_third_level_of_the_argmax_on_several_groups(engine):
     from oracle import cport
     pk = _host.synth(seed=5, n_units=52, n_reads=130, var_len=8)
     up, _, _, _ = pk.units(1)
-    engine.set_param("dist_block", 128); engine.set_param("dist_slots", 2048)
-    try:
+    with engine.knobs(dist_block=128, dist_slots=2048):
         us, ue = pk.units(1)[1], pk.units(1)[2]
         _, a = cport.stage2(pk.bases, pk.read_off, up, us, ue, 19, 3, 10, 32, 0, 2 ** 62, 1, 2, 4, 0.8, want_arrays=True)      # (stage 2 by the C oracle: the
         gk = a["rare"][a["unique"]]                                                                                      # emulated count + dist kernels take a minute here)
@@ -281,16 +218,9 @@ def test_placement_third_level_of_the_argmax_on_several_groups(engine):
         # hash-map path starts over: round 5, reads with many candidate rows)
         for knobs in ({"place_l3": 1, "place_l3_shift": 1, "place_block": 256, "place_grid": 3, "place_long_rescans": 1000000},
                       {"place_l3": 1, "place_l3_shift": 2, "place_grid": 5, "place_long_rescans": 1000000}, {"place_long_rescans": -1}):
-            try:
-                for k, v in knobs.items():
-                    engine.set_param(k, v)
+            with engine.knobs(**knobs):
                 got = lines_from_placement(pk.ids, *[x.tolist() for x in engine.place_reads(cls, rank, 2, 2, 10, 3)])
-            finally:
-                for k in knobs:
-                    engine.set_param(k, 2 if k == "place_long_rescans" else 0)
             assert got == want, knobs
-    finally:
-        engine.set_param("dist_block", 0); engine.set_param("dist_slots", 0)
 
 
 @pytest.mark.parametrize("mode", [2, 3, 1])
@@ -306,11 +236,8 @@ def test_stage3_small_thresholds_on_both_paths(engine, report, golden, mode):
     records, alns, lens = ncrf.parse_report(report(name))
     pk = _host.parse_report(report(name))
     p3 = dict(g["stage3"], min_inters=2, min_unit=1, min_cloud_kmer_freq=1)
-    engine.set_param("place_mode", mode)
-    try:
+    with engine.knobs(place_mode=mode):
         pathcheck.check_stage3(engine, pk, records, alns, lens, gk, p3)
-    finally:
-        engine.set_param("place_mode", 2)
 
 
 def test_stage3_with_units_of_two_motifs(engine, report, golden):
@@ -335,11 +262,8 @@ def test_unit_kmer_occurrences_and_top_n(engine, report):
         g = json.load(f)
     pathcheck.check_unit_kmers(engine, report("lowcov"), g, 30)      # by sort and reduce (records without the read id)
     for mode, bits in ((1, 3), (0, 0)):                                     # few buckets (tiles of one k-mer, tables that fill up); the atomic table
-        engine.set_param("count_mode", mode); engine.set_param("count_bits", bits)
-        try:
+        with engine.knobs(count_mode=mode, count_bits=bits):
             pathcheck.check_unit_kmers(engine, report("lowcov"), g, 19)
-        finally:
-            engine.set_param("count_mode", 1); engine.set_param("count_bits", 0)
 
 
 def test_errors(engine):
@@ -410,8 +334,7 @@ def test_count_sort_and_reduce_buckets_spanning_tiles(engine, bits, mode):
     bases = np.frombuffer(b"".join(seqs), np.uint8)
     off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])])
     engine.load_arrays(bases, off, np.zeros(len(seqs) + 1, np.int64), [], [])
-    engine.set_param("count_mode", mode); engine.set_param("count_bits", bits)
-    try:
+    with engine.knobs(count_mode=mode, count_bits=bits):
         engine.count_kmers(19)
         keys, pres, multi = engine.table()
         wk, wp, wm, n_rk = _presence_oracle(seqs, 19)
@@ -422,5 +345,3 @@ def test_count_sort_and_reduce_buckets_spanning_tiles(engine, bits, mode):
         sel = (wm <= 3) & (wp >= 2) & (wp <= 14)
         assert n == int(sel.sum()) and np.array_equal(engine.kmers(), wk[sel])
         assert engine.stats()["n_distinct"] == wk.size and engine.stats()["n_kept"] == int((wm <= 3).sum())
-    finally:
-        engine.set_param("count_mode", 1); engine.set_param("count_bits", 0)

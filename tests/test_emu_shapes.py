@@ -69,11 +69,8 @@ def test_a1_lengths_alignments_and_symbols(engine, k):
         for symbols in (0, 1):
             case = shapecheck.a1_case(k, e, symbols)
             shapecheck.check_shapes(engine, case, dist=(e == 0))
-            engine.set_param("count_mode", 0)
-            try:
+            with engine.knobs(count_mode=0):
                 shapecheck.check_shapes(engine, case, upto="A2")
-            finally:
-                engine.set_param("count_mode", 1)
 
 
 # ------------------------------------------------------------------ family 3: few reads, repeats
@@ -86,11 +83,8 @@ def test_few_reads_with_repeats(engine, R, k):
         shapecheck.check_shapes(engine, shapecheck.repeats_case(R, k, max_nonuniq), dist=(max_nonuniq == 2))
     reads = shapecheck.repeats_case(R, k, 0)["reads"]
     shapecheck.check_occurrences(engine, reads, k, ns="few")
-    engine.set_param("count_mode", 0)
-    try:
+    with engine.knobs(count_mode=0):
         shapecheck.check_occurrences(engine, reads, k, ns="one")
-    finally:
-        engine.set_param("count_mode", 1)
 
 
 # ------------------------------------------------------------------ family 4: dense clouds through the distance stage

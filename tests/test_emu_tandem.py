@@ -79,8 +79,7 @@ def test_the_tiles_case_straddles_every_border_the_kernel_reports(eng):
 
 @pytest.mark.parametrize("mode", [1, 2])
 def test_both_key_modes(eng, mode):
-    eng.set_param("tandem_key_mode", mode)
-    try:
+    with eng.knobs(tandem_key_mode=mode):
         for name in SMALL:
             if mode == 1 and CASES[name]["k"] == 31 and CASES[name]["reads"]:
                 with pytest.raises(DeviceError, match="more than 64 key bits") as ei:      # 62 code bits leave no byte for a position
@@ -88,16 +87,13 @@ def test_both_key_modes(eng, mode):
                 assert "(-22)" in str(ei.value)
                 continue
             tc.check_case(eng, G, CASES[name], expect_mode=mode)
-    finally:
-        eng.set_param("tandem_key_mode", 0)
     tc.check_case(eng, G, CASES["k_31"], expect_mode=2)      # auto: records where the keys do not fit
     tc.check_case(eng, G, CASES["k_16"], expect_mode=1)
 
 
 @pytest.mark.parametrize("batch", [1, 37, 1000, 2996, 5992])
 def test_batch_borders_inside_the_list(eng, batch):
-    eng.set_param("tandem_batch_windows", batch)
-    try:
+    with eng.knobs(tandem_batch_windows=batch):
         assert eng.tandem_info()["batch_windows"] == batch
         for name in ("tiles", "noisy_k6_bin3", "read_border", "lengths_around_k", "exotic"):
             tc.check_case(eng, G, CASES[name])
@@ -105,8 +101,6 @@ def test_batch_borders_inside_the_list(eng, batch):
             wins = [max(len(s) - case["k"] + 1, 0) for s in case["reads"]]
             if sum(wins) > batch:
                 assert eng.tandem_info()["n_batches"] > 1
-    finally:
-        eng.set_param("tandem_batch_windows", 0)
     assert eng.tandem_info()["batch_windows"] == 1 << 26
 
 

@@ -140,8 +140,7 @@ def test_on_the_ubsan_build():
         rng = np.random.default_rng(17)
         u = uc.rand_seq(rng, 70)
         uc.check(e, u, [uc.tandem_read(rng, u, 90, 1, 4)], (1 << 20, 1 << 30, (1 << 31) - 1), uc.align_np)
-        e.set_param("ualign_batch_bytes", 100)
-        uc.check_hygiene(e, DeviceError)
+        uc.check_hygiene(e, DeviceError, batch_bytes=(100, 0))
     finally:
         e.close()
 

@@ -26,12 +26,10 @@ assert np.array_equal(e.selftest_sort(k, 38), np.sort(k))
 e.set_param("dist_slots", 2048); e.set_param("dist_block", 128)
 pathcheck.check_synthetic_clouds(e)                                                                            # 6-byte slots, multi-chunk postings
 pathcheck.check_synthetic_clouds(e, n_reads=1, n_units=330, cloud=3, n_kmers=25, max_d=320, seed=3)           # 16-bit distances
-e.set_param("dist_dbits", 6)
-pathcheck.check_synthetic_clouds(e, n_reads=3, n_units=60, cloud=4, n_kmers=50, max_d=150, seed=6)            # 6-bit distance field
-e.set_param("dist_dbits", 0)
-e.set_param("dist_wide", 1)
-pathcheck.check_synthetic_clouds(e, n_reads=2, n_units=40, max_d=7, min_d=3, seed=5)                          # 8-byte slots
-e.set_param("dist_wide", 0)
+with e.knobs(dist_dbits=6):
+    pathcheck.check_synthetic_clouds(e, n_reads=3, n_units=60, cloud=4, n_kmers=50, max_d=150, seed=6)        # 6-bit distance field
+with e.knobs(dist_wide=1):
+    pathcheck.check_synthetic_clouds(e, n_reads=2, n_units=40, max_d=7, min_d=3, seed=5)                      # 8-byte slots
 pk = _host.parse_report(fixtures.make_report("tiny", tempfile.mkdtemp()))
 e.load(pk, 1); e.count_kmers(19); n = e.select_rare(3, 3, 14); e.build_clouds()
 ne = e.dist_edges(0, 2 ** 62, 1, 3, 3, 0.8, 0, 1, 400000)

@@ -30,10 +30,9 @@ VARIANTS = {
 # (knob settings, run the random clouds too)
 SETTINGS = [(dict(dist_hot_entries=0, dist_sketch=0, dist_slots=1024), True),
             (dict(dist_slots=2048, dist_block=128), False)]
-RESET = dict(dist_hot_entries=32768, dist_sketch=1, dist_slots=0, dist_block=0)
 RUN = r"""
 import pickle, sys
-root, lib_path, report_path, oracle_path, settings, reset = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], eval(sys.argv[5]), eval(sys.argv[6])
+root, lib_path, report_path, oracle_path, settings = sys.argv[1], sys.argv[2], sys.argv[3], sys.argv[4], eval(sys.argv[5])
 sys.path[:0] = [root, root + "/tests"]
 import pathcheck
 from centroflye_amd import _lib
@@ -41,15 +40,12 @@ from centroflye_amd.engine import Engine
 tup = pickle.load(open(oracle_path, "rb"))
 e = Engine(0, _lib.load(lib_path))
 for knobs, clouds in settings:
-    for k, v in knobs.items():
-        e.set_param(k, v)
-    for thr in (0.8, 0.6, 0.0):
-        pathcheck.check_tie_clouds(e, thr)
-    if clouds:
-        assert pathcheck.check_synthetic_clouds(e, rel_threshold=0.05).shape[0] > 0
-    pathcheck.check_stage2(e, report_path, tup, check_table=False)
-    for k, v in reset.items():
-        e.set_param(k, v)
+    with e.knobs(**knobs):
+        for thr in (0.8, 0.6, 0.0):
+            pathcheck.check_tie_clouds(e, thr)
+        if clouds:
+            assert pathcheck.check_synthetic_clouds(e, rel_threshold=0.05).shape[0] > 0
+        pathcheck.check_stage2(e, report_path, tup, check_table=False)
 print("VARIANT-OK")
 """
 
@@ -66,7 +62,7 @@ def results(emu_lib, report, oracle_stage2, tmp_path_factory):
         if b.returncode:
             return "build failed: " + b.stderr[-3000:]
         lib = os.path.join(ROOT, "tests", "emu", f"libcfhip_emu_{name}.so")
-        r = subprocess.run([sys.executable, "-c", RUN, ROOT, lib, report_path, oracle_path, repr(SETTINGS), repr(RESET)],
+        r = subprocess.run([sys.executable, "-c", RUN, ROOT, lib, report_path, oracle_path, repr(SETTINGS)],
                            capture_output=True, text=True, timeout=900)
         return "ok" if r.returncode == 0 and "VARIANT-OK" in r.stdout else f"exit {r.returncode}: " + r.stdout[-2000:] + r.stderr[-3000:]
 

@@ -24,8 +24,5 @@ def test_member_filter_case(engine, name):
 
 def test_counting_groups_of_clouds_that_are_not_sets(engine):
     for once in (1, 0):
-        engine.set_param("dist_filter_once", once)
-        try:
+        with engine.knobs(dist_filter_once=once):
             gc.run_repeated_rank(engine)
-        finally:
-            engine.set_param("dist_filter_once", 1)

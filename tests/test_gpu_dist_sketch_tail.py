@@ -33,7 +33,7 @@ def test_core_reads_in_the_other_layouts(engine, layout):
 
 @pytest.mark.parametrize("block", [128, 0])
 def test_core_reads_with_a_table_that_splits(engine, block):
-    st = stc.run(engine, stc.case("core", min_cov=2), dict(dist_slots=(256, 0), dist_block=(block, 0)))
+    st = stc.run(engine, stc.case("core", min_cov=2), dict(dist_slots=256, dist_block=block))
     assert st["n_spilled"] > 0
 
 

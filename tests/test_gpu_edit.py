@@ -52,11 +52,8 @@ def test_unrelated_strings_and_both_sides_of_the_switch_point(eng):
     assert ec.one_pair(eng, a, b, w) == w and ec.one_pair(eng, a, b, w - 1) == -1
     # the same pairs with the wavefronts forced into HBM, and into LDS arrays of a few diagonals next to HBM ones
     for forced in (1, 4096):
-        eng.set_param("edit_lds_diags", forced)
-        try:
+        with eng.knobs(edit_lds_diags=forced):
             ec.check_singles(eng, G, cases[1:])
-        finally:
-            eng.set_param("edit_lds_diags", 0)
 
 
 def test_the_limit(eng, singles):

@@ -267,11 +267,8 @@ def test_config2_50k_reads_placement_vs_c_placer(engine):
     assert sum(1 for x in gl if not x.endswith("None")) > 45000
     assert gl == wl
     # the same with the third level of the arg-max that read sets of more than 131 072 reads get: 782 blocks in 98 groups of 8
-    engine.set_param("place_l3", 1); engine.set_param("place_l3_shift", 3)
-    try:
+    with engine.knobs(place_l3=1, place_l3_shift=3):
         again = engine.place_reads(cls, rank, 2, 2, 10, 3)
-    finally:
-        engine.set_param("place_l3", 0); engine.set_param("place_l3_shift", 0)
     assert all(np.array_equal(a, b) for a, b in zip(again, got))
 
 
@@ -299,17 +296,12 @@ def test_config0_1k_reads_full_stage2_vs_cpu(engine):
     # (2 and 8 regions), the 8-byte slots, one 1 024-thread workgroup per CU, the filter's in-scan evaluation — the same edges
     # and unique set
     for knobs in ({"dist_int_thr": 0}, {"dist_dbits": 7}, {"dist_regions": 2}, {"dist_regions": 8}, {"dist_regions": 2, "dist_region_bytes": 1}, {"dist_wide": 1}, {"dist_wgs": 1, "dist_block": 1024}, {"dist_hot_cap": 5}):
-        try:
-            for name, v in knobs.items():
-                engine.set_param(name, v)
+        with engine.knobs(**knobs):
             engine.reset_unique()
             ne2 = engine.dist_edges(0, 2 ** 62, P["min_d"], P["max_d"], P["min_cov"], P["rel_threshold"], 0, 1, edge_cap=c["n_edges"])
             assert (ne2, engine.stats()["n_emissions"]) == (c["n_edges"], c["n_emissions"]), knobs
             assert cport.edge_checksum(engine.edges(ne2)) == c["edge_checksum"], knobs
             assert np.array_equal(engine.unique_mask(), a["unique"]), knobs
-        finally:
-            for name in knobs:
-                engine.set_param(name, 1 if name == "dist_int_thr" else 0)
 
 
 @pytest.mark.timeout(900)
@@ -347,19 +339,11 @@ def test_placement_3k_reads_vs_c_placer(engine):
     # hash-map path takes over)
     # ("place_long_rescans": 1 000 000 keeps the region path on these shapes whatever this read set's candidate rows look like — round 5: runs
     # whose reads keep having more than four candidate rows are handed to the hash-map path; -1: handed over at the first look, at iteration 64)
-    defaults = {"place_mode": 2, "place_grid": 0, "place_block": 0, "place_row_words": 0, "place_slots_per_unit": 0, "place_fused": 1, "place_chunk": 2, "place_l3": 0, "place_l3_shift": 0,
-                "place_long_rescans": 1000000}
-    engine.set_param("place_long_rescans", 1000000)
-    for knobs in ({"place_grid": 13, "place_block": 256}, {"place_long_rescans": -1}, {"place_row_words": 32, "place_grid": 7}, {"place_row_words": 64}, {"place_slots_per_unit": 2},
-                  {"place_l3": 1, "place_l3_shift": 2}, {"place_l3": 1, "place_l3_shift": 1, "place_block": 256, "place_grid": 13}, {"place_slots_per_unit": 1 << 16},
-                  {"place_mode": 1}, {"place_mode": 1, "place_fused": 0}, {"place_mode": 1, "place_chunk": 7, "place_grid": 13},
-                  {"place_mode": 1, "place_chunk": 64, "place_grid": 512}):
-        try:
-            for k, v in knobs.items():
-                engine.set_param(k, v)
-            again = engine.place_reads(cls, rank, 2, 2, 10, 3)
-        finally:
-            for k, v in defaults.items():
-                engine.set_param(k, v)
-        assert all(np.array_equal(a, b) for a, b in zip(again, got)), knobs
-    engine.set_param("place_long_rescans", 2)
+    with engine.knobs(place_long_rescans=1000000):
+        for knobs in ({"place_grid": 13, "place_block": 256}, {"place_long_rescans": -1}, {"place_row_words": 32, "place_grid": 7}, {"place_row_words": 64}, {"place_slots_per_unit": 2},
+                      {"place_l3": 1, "place_l3_shift": 2}, {"place_l3": 1, "place_l3_shift": 1, "place_block": 256, "place_grid": 13}, {"place_slots_per_unit": 1 << 16},
+                      {"place_mode": 1}, {"place_mode": 1, "place_fused": 0}, {"place_mode": 1, "place_chunk": 7, "place_grid": 13},
+                      {"place_mode": 1, "place_chunk": 64, "place_grid": 512}):
+            with engine.knobs(**knobs):
+                again = engine.place_reads(cls, rank, 2, 2, 10, 3)
+            assert all(np.array_equal(a, b) for a, b in zip(again, got)), knobs

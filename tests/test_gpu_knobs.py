@@ -16,8 +16,6 @@ from centroflye_amd.engine import Engine
 
 pytestmark = pytest.mark.gpu
 PART, N_PARTS = 5, 64
-DEFAULTS = dict(dist_hot_entries=32768, dist_fill_pct=70, dist_slots=0, dist_est_pct=80, dist_int_thr=1, lut_shift=-1, count_mode=1,
-                count_slots=4096, count_tile=16, dist_sketch_bits=0, count_bits=0, place_cmap_bits=0)
 SETTINGS = [dict(dist_hot_entries=-1), dict(dist_hot_entries=0), dict(dist_hot_entries=1),
             dict(dist_fill_pct=10), dict(dist_fill_pct=90, dist_slots=256),
             dict(dist_est_pct=5), dict(dist_est_pct=100), dict(dist_int_thr=0),
@@ -40,11 +38,6 @@ def reads():
     return pk, bigparity.oracle_record(pk, PART, N_PARTS)
 
 
-def set_knobs(engine, knobs):
-    for k, v in knobs.items():
-        engine.set_param(k, v)
-
-
 @pytest.fixture(scope="module")
 def default_run(engine, reads):
     pk, rec = reads
@@ -57,11 +50,8 @@ def default_run(engine, reads):
 @pytest.mark.parametrize("knobs", SETTINGS, ids=lambda k: ",".join(f"{a}={b}" for a, b in k.items()))
 def test_knob_setting_equals_the_oracle(engine, reads, default_run, knobs):
     pk, rec = reads
-    set_knobs(engine, knobs)
-    try:
+    with engine.knobs(**knobs):
         r = bigparity.check_record(engine, pk, rec)
-    finally:
-        set_knobs(engine, {k: DEFAULTS[k] for k in knobs})
     assert r["identical"], (knobs, r)
     if knobs.get("dist_fill_pct") == 10:      # (tables split at a tenth of their slots: more passes)
         assert r["got"]["n_dist_passes"] > default_run["got"]["n_dist_passes"], (r["got"], default_run["got"])
@@ -70,15 +60,11 @@ def test_knob_setting_equals_the_oracle(engine, reads, default_run, knobs):
 @pytest.mark.parametrize("int_thr", [1, 0])
 def test_dominance_ties_and_near_misses(engine, int_thr):
     """pathcheck.tie_clouds at every threshold of test_emu_knobs.py, with the hot list and by the filter's scan."""
-    try:
-        engine.set_param("dist_int_thr", int_thr)
-        for hot in (32768, 0):
-            engine.set_param("dist_hot_entries", hot)
+    for hot in (32768, 0):
+        with engine.knobs(dist_int_thr=int_thr, dist_hot_entries=hot):
             for thr in (0.5, 0.6, 0.75, 0.3, 1.0, 0.8, 0.7, 0.9, 1.5, 0.0, -0.25):
                 pathcheck.check_tie_clouds(engine, thr)
             pathcheck.check_tie_clouds(engine, 0.8, copies=3)
-    finally:
-        set_knobs(engine, dict(dist_int_thr=1, dist_hot_entries=32768))
 
 
 @pytest.mark.parametrize("bits", [3, 5])
@@ -98,9 +84,6 @@ def test_placement_with_a_tiny_contig_map_equals_the_c_placer(engine, bits):
     rank = np.argsort(np.argsort(np.array(pk.ids, dtype=object), kind="stable"), kind="stable").astype(np.int32)
     want = lines_from_placement(pk.ids, *[x.tolist() for x in cport.place_reads(cls, rank, up, cp, ent, gk.size, 2, 2, 10, 3)])
     assert sum(1 for x in want if not x.endswith("None")) > 90
-    try:
-        engine.set_param("place_cmap_bits", bits)
+    with engine.knobs(place_cmap_bits=bits):
         got = lines_from_placement(pk.ids, *[x.tolist() for x in engine.place_reads(cls, rank, 2, 2, 10, 3)])
-    finally:
-        engine.set_param("place_cmap_bits", 0)
     assert got == want

@@ -83,11 +83,8 @@ def test_50k_bench_reads_onto_the_contig_of_their_greedy_placement():
         assert [tuple(int(a[r]) for a in got) for r in sample] == want
         assert sum(1 for w in want if w[0] >= 0) > 400
         # the same with a window of 64 starts, queries given as the sample in reverse
-        e.set_param("map_window", 64)
-        try:
+        with e.knobs(map_window=64):
             small = e.map_reads(sample[::-1], (5, 10))
-        finally:
-            e.set_param("map_window", 0)
         assert [tuple(int(a[i]) for a in small) for i in range(sample.size)] == want[::-1]
         spans = [mapcheck.hit_span(up, cp, ent, c, int(r)) for r in sample]
         greedy = np.full(pk.n_reads, -1, np.int64)

@@ -61,44 +61,29 @@ def test_stage3_fixture_against_reference_golden(engine, name, report, golden):
 
 def test_wide_table_layout(engine, report, oracle_stage2):
     """The 8-byte-slot layout used for k-mer sets of 2^24 ranks or more (default: 6-byte slots)."""
-    engine.set_param("dist_wide", 1)
-    try:
+    with engine.knobs(dist_wide=1):
         pathcheck.check_stage2(engine, report("tiny"), oracle_stage2("tiny"), check_table=False)
-        engine.set_param("dist_slots", 512)
-        engine.set_param("dist_sketch", 0)      # every (b, d) pair in the exact table: forces the spill path
-        pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov"), n_parts=2, check_table=False)
-        assert engine.stats()["n_spilled"] > 0
-        engine.set_param("dist_sketch", 1)
-        pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov"), n_parts=2, check_table=False)
-        pathcheck.check_synthetic_clouds(engine, n_reads=4, n_units=150, cloud=8, n_kmers=60)
-    finally:
-        engine.set_param("dist_wide", 0)
-        engine.set_param("dist_slots", 0)
-        engine.set_param("dist_sketch", 1)
+        with engine.knobs(dist_slots=512):
+            with engine.knobs(dist_sketch=0):       # every (b, d) pair in the exact table: forces the spill path
+                pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov"), n_parts=2, check_table=False)
+                assert engine.stats()["n_spilled"] > 0
+            pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov"), n_parts=2, check_table=False)
+            pathcheck.check_synthetic_clouds(engine, n_reads=4, n_units=150, cloud=8, n_kmers=60)
 
 
 def test_partitions_spill_and_slices(engine, report, oracle_stage2):
     # first k-mers split 3 ways (the multi-GPU partition), tiny LDS table (forces the spill path)
-    engine.set_param("dist_slots", 1024)
-    engine.set_param("dist_stage", 5)           # with chunks of 32 rows of the edge output: late rows beyond the staged list -> marked-slot sweep
-    engine.set_param("dist_edge_chunk", 32)
-    try:
-        engine.set_param("dist_sketch", 0)      # every (b, d) pair in the exact table
+    # dist_stage 5 with chunks of 32 rows of the edge output: late rows beyond the staged list -> marked-slot sweep
+    with engine.knobs(dist_slots=1024, dist_stage=5, dist_edge_chunk=32):
+        with engine.knobs(dist_sketch=0):           # every (b, d) pair in the exact table
+            pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov"), n_parts=3, check_table=False)
+            assert engine.stats()["n_spilled"] > 0
+        # counting sketch first (the default), same tiny LDS budget
         pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov"), n_parts=3, check_table=False)
-        assert engine.stats()["n_spilled"] > 0
-        engine.set_param("dist_sketch", 1)      # counting sketch first (the default), same tiny LDS budget
-        pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov"), n_parts=3, check_table=False)
-        engine.set_param("dist_post_atomics", 1)    # the partition's postings by histogram + fill passes of atomics (default: compaction + sort)
-        pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov"), n_parts=3, check_table=False)
-        engine.set_param("dist_post_atomics", 0)
-        engine.set_param("dist_slots", 256)     # 2048 8-bit counters: they wrap -> falls back to "every b marked"
-        pathcheck.check_stage2(engine, report("hor2055"), oracle_stage2("hor2055"), check_table=False)
-    finally:
-        engine.set_param("dist_slots", 0)
-        engine.set_param("dist_post_atomics", 0)
-        engine.set_param("dist_stage", 2048)
-        engine.set_param("dist_edge_chunk", 0)
-        engine.set_param("dist_sketch", 1)
+        with engine.knobs(dist_post_atomics=1):     # the partition's postings by histogram + fill passes of atomics (default: compaction + sort)
+            pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov"), n_parts=3, check_table=False)
+        with engine.knobs(dist_slots=256):          # 2048 8-bit counters: they wrap -> falls back to "every b marked"
+            pathcheck.check_stage2(engine, report("hor2055"), oracle_stage2("hor2055"), check_table=False)
     # --min-nreads / --max-nreads slice and --min-distance 0 (kmer_clouds[:-0] is empty) and a narrow d window
     for ov in (dict(min_nreads=3, max_nreads=11), dict(min_distance=0, max_distance=4), dict(min_distance=2, max_distance=3)):
         pathcheck.check_stage2(engine, report("lowcov"), oracle_stage2("lowcov", **ov), check_table=False)
@@ -110,11 +95,8 @@ def test_unit_kmer_occurrences_and_top_n(engine, report, name, k):
     with open(os.path.join(ROOT, "tests", "golden", f"{name}.unit_kmers.json")) as f:
         g = json.load(f)
     pathcheck.check_unit_kmers(engine, report(name), g, k)
-    engine.set_param("count_mode", 0)      # the atomic table of round 1 instead of sort and reduce: the same table and top n
-    try:
+    with engine.knobs(count_mode=0):       # the atomic table of round 1 instead of sort and reduce: the same table and top n
         pathcheck.check_unit_kmers(engine, report(name), g, k)
-    finally:
-        engine.set_param("count_mode", 1)
 
 
 def test_long_posting_lists_take_the_multi_chunk_path(engine):
@@ -135,28 +117,19 @@ def test_kmer_sets_beyond_2_pow_24_keep_the_six_byte_slots(engine):
     100 / 30 units; the same clouds through the 8-byte layout give the same edges (pathcheck compares both with the oracle)."""
     pathcheck.check_synthetic_clouds(engine, n_reads=3, n_units=100, cloud=4, n_kmers=40, seed=7, kmer_base=1 << 24)      # DB = 7
     pathcheck.check_synthetic_clouds(engine, n_reads=3, n_units=30, cloud=4, n_kmers=40, seed=8, kmer_base=1 << 26)       # DB = 5
-    engine.set_param("dist_wide", 1)
-    try:
+    with engine.knobs(dist_wide=1):
         pathcheck.check_synthetic_clouds(engine, n_reads=3, n_units=100, cloud=4, n_kmers=40, seed=7, kmer_base=1 << 24)
-    finally:
-        engine.set_param("dist_wide", 0)
     # long reads (200 units: distances need 8 bits) with 2^24 + 40 and 2^26 + 40 k-mers: the region layout (2 and 8 regions)
     pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=200, cloud=4, n_kmers=40, seed=9, kmer_base=1 << 24)
     pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=200, cloud=4, n_kmers=40, seed=10, kmer_base=1 << 26)
     for regions, stream_bytes in ((1, 0), (4, 0), (4, 1)):      # (the 4-byte stream of round 4; rank and unit index apart)
-        engine.set_param("dist_regions", regions); engine.set_param("dist_region_bytes", stream_bytes)
-        try:
+        with engine.knobs(dist_regions=regions, dist_region_bytes=stream_bytes):
             pathcheck.check_synthetic_clouds(engine, n_reads=3, n_units=100, cloud=4, n_kmers=50, seed=regions)
             pathcheck.check_synthetic_clouds(engine, n_reads=3, n_units=128, cloud=5, n_kmers=30, max_d=127, seed=11 + regions)
             pathcheck.check_synthetic_clouds(engine, n_reads=2, n_units=100, cloud=40, n_kmers=300, max_d=99, seed=21 + regions)
-        finally:
-            engine.set_param("dist_regions", 0); engine.set_param("dist_region_bytes", 0)
     for dbits in (5, 6, 7):
-        engine.set_param("dist_dbits", dbits)
-        try:
+        with engine.knobs(dist_dbits=dbits):
             pathcheck.check_synthetic_clouds(engine, n_reads=3, n_units=min(100, (1 << dbits) - 2), cloud=4, n_kmers=50, seed=dbits)
-        finally:
-            engine.set_param("dist_dbits", 0)
 
 
 def test_against_c_oracle_on_bench_like_sample(engine):
@@ -197,31 +170,25 @@ def test_full_size_properties(engine):
     assert np.all((np.diff(ent) > 0) | ~inner[1:])           # every cloud sorted-unique
     ref = None
     for slots, parts, sketch in ((0, 1, 1), (6000, 1, 0), (4096, 2, 1), (2048, 1, 1)):
-        engine.set_param("dist_slots", slots)
-        engine.set_param("dist_sketch", sketch)
-        engine.reset_unique()
-        tot_e = tot_n = 0
-        chk = 0
-        for p in range(parts):
-            ne = engine.dist_edges(0, 2 ** 62, 1, 150, 4, 0.8, p, parts, edge_cap=60_000_000)
-            assert ne <= 60_000_000
-            chk = (chk + cport.edge_checksum(engine.edges(ne))) % 2 ** 64
-            tot_e += engine.stats()["n_emissions"]; tot_n += ne
-        got = (tot_n, tot_e, chk, engine.unique_mask().tobytes())
+        with engine.knobs(dist_slots=slots, dist_sketch=sketch):
+            engine.reset_unique()
+            tot_e = tot_n = 0
+            chk = 0
+            for p in range(parts):
+                ne = engine.dist_edges(0, 2 ** 62, 1, 150, 4, 0.8, p, parts, edge_cap=60_000_000)
+                assert ne <= 60_000_000
+                chk = (chk + cport.edge_checksum(engine.edges(ne))) % 2 ** 64
+                tot_e += engine.stats()["n_emissions"]; tot_n += ne
+            got = (tot_n, tot_e, chk, engine.unique_mask().tobytes())
         if ref is None:
             ref = got
         assert got == ref
-    engine.set_param("dist_slots", 0)
-    engine.set_param("dist_sketch", 1)
     # launch shape (chosen by the library from the pair emissions per first k-mer): both shapes forced
-    try:
-        for block, wgs in ((1024, 1), (512, 2)):
-            engine.set_param("dist_block", block); engine.set_param("dist_wgs", wgs)
+    for block, wgs in ((1024, 1), (512, 2)):
+        with engine.knobs(dist_block=block, dist_wgs=wgs):
             engine.reset_unique()
             ne = engine.dist_edges(0, 2 ** 62, 1, 150, 4, 0.8, 0, 1, edge_cap=60_000_000)
             assert (ne, engine.stats()["n_emissions"], cport.edge_checksum(engine.edges(ne)), engine.unique_mask().tobytes()) == ref
-    finally:
-        engine.set_param("dist_block", 0); engine.set_param("dist_wgs", 0)
     engine.reset_unique()
     ne = engine.dist_edges(0, 2 ** 62, 1, 150, 4, 0.8, 0, 1, edge_cap=60_000_000)
     full = {tuple(r) for r in engine.edges(ne).tolist()}

@@ -24,16 +24,13 @@ def engine():
 def test_cloud_size_regimes(engine, lut_shift):
     """Counting rank (<= 512), bitonic network in the 2048-slot set (<= 1536), the 8192-slot retry (<= 6144), the refusal at
     6145 with the context usable afterwards, a launch whose retry repeats units that had fitted, the staging-tile borders."""
-    engine.set_param("lut_shift", lut_shift)
-    try:
+    with engine.knobs(lut_shift=lut_shift):
         for n in shapecheck.CLOUD_SIZES:
             shapecheck.check_shapes(engine, shapecheck.cloud_size_case(n))
         shapecheck.check_shapes(engine, shapecheck.cloud_size_case(6145))
         shapecheck.check_shapes(engine, shapecheck.cloud_size_case(1536))
         shapecheck.check_shapes(engine, shapecheck.cloud_mixed_case())
         shapecheck.check_shapes(engine, shapecheck.cloud_staging_case())
-    finally:
-        engine.set_param("lut_shift", -1)
 
 
 # ------------------------------------------------------------------ family 2: A1's first pass
@@ -49,15 +46,8 @@ def test_a1_lengths_alignments_and_symbols(engine, k):
             case = shapecheck.a1_case(k, e, symbols)
             shapecheck.check_shapes(engine, case)
             for knobs in TABLE_KNOBS:
-                try:
-                    engine.set_param("count_mode", 0)
-                    for name, value in knobs.items():
-                        engine.set_param(name, value)
+                with engine.knobs(count_mode=0, **knobs):
                     shapecheck.check_shapes(engine, case, upto="A2")
-                finally:
-                    engine.set_param("count_mode", 1)
-                    engine.set_param("count_tile", 16)
-                    engine.set_param("count_slots", 4096)
 
 
 # ------------------------------------------------------------------ family 3: few reads, repeats
@@ -69,18 +59,12 @@ def test_few_reads_with_repeats(engine, R, k):
     for max_nonuniq in (0, 1, 2):
         case = shapecheck.repeats_case(R, k, max_nonuniq)
         shapecheck.check_shapes(engine, case)
-        engine.set_param("count_mode", 0)
-        try:
+        with engine.knobs(count_mode=0):
             shapecheck.check_shapes(engine, case, upto="A2")
-        finally:
-            engine.set_param("count_mode", 1)
     reads = shapecheck.repeats_case(R, k, 0)["reads"]
     shapecheck.check_occurrences(engine, reads, k)
-    engine.set_param("count_mode", 0)
-    try:
+    with engine.knobs(count_mode=0):
         shapecheck.check_occurrences(engine, reads, k)
-    finally:
-        engine.set_param("count_mode", 1)
 
 
 # ------------------------------------------------------------------ family 4: dense clouds through the distance stage
@@ -92,14 +76,9 @@ def test_dense_clouds(engine, name):
 def test_dense_clouds_spill_under_a_small_table(engine):
     """The first dense case with 512 slots and every (b, d) pair in the exact table: first k-mers whose table has to be
     partitioned (n_spilled > 0)."""
-    engine.set_param("dist_slots", 512)
-    engine.set_param("dist_sketch", 0)
-    try:
+    with engine.knobs(dist_slots=512, dist_sketch=0):
         shapecheck.check_dense(engine, "dense_2x5")
         assert engine.stats()["n_spilled"] > 0
-    finally:
-        engine.set_param("dist_slots", 0)
-        engine.set_param("dist_sketch", 1)
 
 
 # ------------------------------------------------------------------ the generic radix sort and scan

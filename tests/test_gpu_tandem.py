@@ -35,27 +35,21 @@ def test_every_small_case(eng, name):
 @pytest.mark.parametrize("mode", [1, 2])
 def test_both_key_modes(eng, mode):
     from centroflye_amd.engine import DeviceError
-    eng.set_param("tandem_key_mode", mode)
-    try:
+    with eng.knobs(tandem_key_mode=mode):
         for name in SMALL + ["hor64"]:
             if mode == 1 and CASES[name]["k"] == 31 and CASES[name]["reads"]:
                 with pytest.raises(DeviceError, match="more than 64 key bits"):
                     tc.check_case(eng, G, CASES[name])
                 continue
             tc.check_case(eng, G, CASES[name], expect_mode=mode)
-    finally:
-        eng.set_param("tandem_key_mode", 0)
     tc.check_case(eng, G, CASES["k_31"], expect_mode=2)
 
 
 @pytest.mark.parametrize("batch", [1, 37, 1000, 2996, 5992])
 def test_batch_borders_inside_the_list(eng, batch):
-    eng.set_param("tandem_batch_windows", batch)
-    try:
+    with eng.knobs(tandem_batch_windows=batch):
         for name in ("tiles", "noisy_k6_bin3", "read_border", "lengths_around_k", "exotic"):
             tc.check_case(eng, G, CASES[name])
-    finally:
-        eng.set_param("tandem_batch_windows", 0)
 
 
 def test_the_hor_like_reads_in_one_batch_and_in_seven(eng):
@@ -63,12 +57,9 @@ def test_the_hor_like_reads_in_one_batch_and_in_seven(eng):
     assert np.all(np.abs(rows["period"] - 2055) <= 10)
     info = eng.tandem_info()
     assert info["n_batches"] == 1 and info["n_records"] == 64 * (20000 - 14) and info["phase_ms"]["total"] > 0.0
-    eng.set_param("tandem_batch_windows", 200000)
-    try:
+    with eng.knobs(tandem_batch_windows=200000):
         again = tc.check_case(eng, G, CASES["hor64"])
         assert eng.tandem_info()["n_batches"] == 7 and np.array_equal(again, rows)
-    finally:
-        eng.set_param("tandem_batch_windows", 0)
 
 
 def test_a_refusal_leaves_the_results_of_the_call_before(eng):

@@ -385,15 +385,12 @@ def check_batches(eng):
     areas = sorted(w["r_en"] * 3 * 4 for w in wants)
     default = eng.ualign_info()["batch_bytes"]
     assert 1 << 28 <= default <= 1 << 34
-    try:
-        for bytes_, n_batches in ((0, 1), (sum(areas), 1), (areas[-1] + areas[-2], None), (areas[-1], 6), (100, 6), (1, 6)):
-            eng.set_param("ualign_batch_bytes", bytes_)
+    for bytes_, n_batches in ((0, 1), (sum(areas), 1), (areas[-1] + areas[-2], None), (areas[-1], 6), (100, 6), (1, 6)):
+        with eng.knobs(ualign_batch_bytes=bytes_):
             check(eng, u, reads, wants=wants)
             info = eng.ualign_info()
             assert info["batch_bytes"] == (bytes_ or default) and info["n_move_pairs"] == 6
             assert info["n_batches"] == n_batches or (n_batches is None and 1 < info["n_batches"] < 6), (bytes_, info)
-    finally:
-        eng.set_param("ualign_batch_bytes", 0)
 
 
 def workload_pair(seed, m, n_body, flank=500):
@@ -469,20 +466,20 @@ def check_refusals(eng, DeviceError):
     assert eng.stats()["hbm_bytes_live"] == live
 
 
-def check_hygiene(eng, DeviceError):
-    """two rounds of calls, refusals among them, leave the same live bytes and the same results"""
+def check_hygiene(eng, DeviceError, batch_bytes=(0, 0)):
+    """two rounds of calls, refusals among them, leave the same live bytes and the same results; a round begins under its ualign_batch_bytes"""
     import pytest
     rng = np.random.default_rng(21)
     u = rand_seq(rng, 70)
     reads = [tandem_read(rng, u, 150, q & 1, 10) for q in range(5)] + [b""]
     rounds = []
-    for _ in range(2):
-        wants = check(eng, u, reads)
-        with pytest.raises(DeviceError):
-            eng.ualign_run(b"ACGN", np.frombuffer(b"ACGT", np.uint8), [0, 4])
-        eng.set_param("ualign_batch_bytes", 500)
-        check(eng, u, reads, wants=wants)
-        eng.set_param("ualign_batch_bytes", 0)
+    for first in batch_bytes:
+        with eng.knobs(ualign_batch_bytes=first):
+            wants = check(eng, u, reads)
+            with pytest.raises(DeviceError):
+                eng.ualign_run(b"ACGN", np.frombuffer(b"ACGT", np.uint8), [0, 4])
+        with eng.knobs(ualign_batch_bytes=500):
+            check(eng, u, reads, wants=wants)
         hits, ptr, ops = device(eng, u, reads)
         rounds.append((eng.stats()["hbm_bytes_live"], hits.tobytes(), ptr.tobytes(), ops.tobytes()))
     assert rounds[0] == rounds[1]

@@ -192,12 +192,9 @@ def check_table_case(engine, case, worlds=WORLDS, wrong=None):
             assert (sizes > 0).all(), f"{what}: an owner of {W} has no key"
         if W == 257 and case["empty_at_257"]:
             assert (sizes == 0).any() and (sizes > 0).any()
-    engine.set_param("count_mode", case["count_mode"])
-    try:
+    with engine.knobs(count_mode=case["count_mode"]):
         engine.load_arrays(*shapecheck.to_arrays(case["reads"], [[] for _ in case["reads"]]))
         engine.count_kmers(case["k"])
-    finally:
-        engine.set_param("count_mode", 1)
     keys, pres, multi = engine.table()
     want = sorted(table)
     assert np.array_equal(keys, np.array(want, np.uint64)), f"{what}: A1 keys"

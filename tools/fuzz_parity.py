@@ -22,10 +22,7 @@ def arg(name, default, conv=int):
 
 
 BASE = dict(bigparity.P)
-KNOB_DEFAULTS = dict(dist_slots=0, dist_block=0, dist_wgs=0, dist_sketch=1, dist_wide=0, dist_regions=0, dist_region_bytes=0, dist_dbits=0, dist_hot_cap=0,
-                     dist_post_atomics=0, dist_fill_pct=70, dist_stage=2048, dist_int_thr=1, count_mode=1, count_bits=0, comm_round_bytes=1 << 28,
-                     dist_hot_entries=32768, lut_shift=-1, dist_sketch_bits=0, dist_est_pct=80, count_slots=4096, count_tile=16)
-# the values a knob case draws from (each knob with probability 0.18); every name and value here and in KNOB_DEFAULTS is one
+# the values a knob case draws from (each knob with probability 0.18); every name and value here is one
 # cf_set_param takes on its own (tests/test_fuzz_generator.py): a refusal of a case is then a combination, never a typo
 KNOB_CHOICES = (("dist_slots", [256, 512, 2048, 4096]), ("dist_block", [64, 128, 256, 512, 1024]), ("dist_wgs", [1, 2, 3, 4]), ("dist_sketch", [0]),
                 ("dist_wide", [1]), ("dist_regions", [1, 2, 4, 8]), ("dist_region_bytes", [1]), ("dist_dbits", [5, 6, 7, 8]), ("dist_hot_cap", [1, 8, 64]),
@@ -98,31 +95,27 @@ def main():
             try:
                 pk = _host.synth(**sy)
                 bigparity.P.clear(); bigparity.P.update(BASE); bigparity.P.update(p)
-                for kk, vv in KNOB_DEFAULTS.items():
-                    e.set_param(kk, vv)
-                for kk, vv in knobs.items():
-                    e.set_param(kk, vv)
-                # (a look at the size first, on the device: a case whose partition has more than 4e9 pair emissions or 2e8 edges is minutes of oracle time
-                # and gigabytes of edge rows — dropped, not run)
-                e.load(pk, 1); e.count_kmers(p["k"]); e.select_rare(p["max_nonuniq"], p["lo"], p["hi"]); e.build_clouds(); e.reset_unique()
-                ne0 = e.dist_edges(0, 2 ** 62, p["min_d"], p["max_d"], p["min_cov"], p["rel_threshold"], part, n_parts, edge_cap=0)
-                if e.stats()["n_emissions"] > 4e9 or ne0 > 2e8:
-                    raise DeviceError(f"case too large (-12): {e.stats()['n_emissions']} pair emissions, {ne0} edges")
-                if exchange:
-                    # the way ONE rank of n_parts runs its partition: A1 on its read shard, table exchange / rare gather / cloud gather through a one-rank
-                    # communicator that sends to itself (bucketing, rounds of comm_round_bytes, merge, gathered view), A5 / A6 over the gathered view
-                    e.set_param("comm_round_bytes", int(rng.choice([1 << 12, 1 << 16, 1 << 28])))
-                    orec = bigparity.oracle_record(pk, part, n_parts)
-                    x = bigparity.check_record(e, pk, orec, through_exchange=True, rendezvous=tempfile.mkdtemp() if lib else None)      # (the emulator's file transport meets in a directory)
-                    e.set_param("comm_round_bytes", 1 << 28)
-                    r = dict(identical=x["identical"], checks=x["checks"], n_rare=orec["n_rare"], n_emissions_partition=x["got"]["n_emissions_partition"],
-                             n_edges_partition=x["got"]["n_edges_partition"], n_dist_passes=x["got"]["n_dist_passes"], n_bases=orec["n_bases"],
-                             dist_kernel_ms=x["got"]["dist_kernel_ms"], oracle_A1_A3_s=orec["oracle_A1_A3_s"], oracle_partition_s=orec["partition"]["oracle_s"])
-                else:
-                    r = bigparity.check(e, pk, part=part, n_parts=n_parts)
-                rec.update(identical=bool(r["identical"]), checks=r["checks"], n_rare=r["n_rare"], n_emissions=r["n_emissions_partition"], n_edges=r["n_edges_partition"],
-                           passes=r["n_dist_passes"], n_bases=r["n_bases"], dist_kernel_ms=r["dist_kernel_ms"], oracle_s=round(r["oracle_A1_A3_s"] + r["oracle_partition_s"], 1),
-                           device_ms={k: round(float(v), 1) for k, v in e.times().items() if k.endswith("_ms") and v})
+                with e.knobs(**knobs):
+                    # (a look at the size first, on the device: a case whose partition has more than 4e9 pair emissions or 2e8 edges is minutes of oracle time
+                    # and gigabytes of edge rows — dropped, not run)
+                    e.load(pk, 1); e.count_kmers(p["k"]); e.select_rare(p["max_nonuniq"], p["lo"], p["hi"]); e.build_clouds(); e.reset_unique()
+                    ne0 = e.dist_edges(0, 2 ** 62, p["min_d"], p["max_d"], p["min_cov"], p["rel_threshold"], part, n_parts, edge_cap=0)
+                    if e.stats()["n_emissions"] > 4e9 or ne0 > 2e8:
+                        raise DeviceError(f"case too large (-12): {e.stats()['n_emissions']} pair emissions, {ne0} edges")
+                    if exchange:
+                        # the way ONE rank of n_parts runs its partition: A1 on its read shard, table exchange / rare gather / cloud gather through a one-rank
+                        # communicator that sends to itself (bucketing, rounds of comm_round_bytes, merge, gathered view), A5 / A6 over the gathered view
+                        orec = bigparity.oracle_record(pk, part, n_parts)
+                        with e.knobs(comm_round_bytes=int(rng.choice([1 << 12, 1 << 16, 1 << 28]))):
+                            x = bigparity.check_record(e, pk, orec, through_exchange=True, rendezvous=tempfile.mkdtemp() if lib else None)      # (the emulator's file transport meets in a directory)
+                        r = dict(identical=x["identical"], checks=x["checks"], n_rare=orec["n_rare"], n_emissions_partition=x["got"]["n_emissions_partition"],
+                                 n_edges_partition=x["got"]["n_edges_partition"], n_dist_passes=x["got"]["n_dist_passes"], n_bases=orec["n_bases"],
+                                 dist_kernel_ms=x["got"]["dist_kernel_ms"], oracle_A1_A3_s=orec["oracle_A1_A3_s"], oracle_partition_s=orec["partition"]["oracle_s"])
+                    else:
+                        r = bigparity.check(e, pk, part=part, n_parts=n_parts)
+                    rec.update(identical=bool(r["identical"]), checks=r["checks"], n_rare=r["n_rare"], n_emissions=r["n_emissions_partition"], n_edges=r["n_edges_partition"],
+                               passes=r["n_dist_passes"], n_bases=r["n_bases"], dist_kernel_ms=r["dist_kernel_ms"], oracle_s=round(r["oracle_A1_A3_s"] + r["oracle_partition_s"], 1),
+                               device_ms={k: round(float(v), 1) for k, v in e.times().items() if k.endswith("_ms") and v})
             except DeviceError as ex:
                 refused = "(-22)" in str(ex) or "(-12)" in str(ex)      # (a knob combination the library does not take; a case too large for the device)
                 rec.update(identical=None if refused else False, refused=str(ex)[:200])

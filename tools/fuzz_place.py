@@ -25,7 +25,6 @@ budget = arg("--seconds", 10 ** 9, float)
 out = arg("--out", os.path.join(ROOT, "gpurun_out", "fuzz_place.json"), str)
 only = arg("--only", -1)
 rng = np.random.default_rng(seed)
-KNOB_DEFAULTS = dict(place_mode=2, place_grid=0, place_block=0, place_row_words=0, place_slots_per_unit=0, place_fused=1, place_l3=0, place_l3_shift=0)
 
 recs, t_start = [], time.time()
 lib = None
@@ -61,8 +60,6 @@ with Engine(0, lib) as e:
             cls = pk.classify(s["prefix_threshold"])
             rank = np.argsort(np.argsort(np.array(pk.ids, dtype=object), kind="stable"), kind="stable").astype(np.int32)
             up = pk.units(n_motif)[0]
-            for kk, vv in KNOB_DEFAULTS.items():
-                e.set_param(kk, vv)
             e.load(pk, 1); e.count_kmers(19); e.select_rare(3, 10, 32); e.build_clouds(); e.reset_unique()
             e.dist_edges(0, 2 ** 62, 1, 150, 4, 0.8, 0, 1, 0)
             gk = e.kmers()[e.unique_mask()]
@@ -78,9 +75,8 @@ with Engine(0, lib) as e:
                 tc = time.time()
                 want = lines_from_placement(pk.ids, *[x.tolist() for x in cport.place_reads(cls, rank, up, cp, ent, gk.size, s["freq"], s["min_unit"], s["min_inters"], 3)])
                 rec["oracle_s"] = round(time.time() - tc, 2)
-                for kk, vv in knobs.items():
-                    e.set_param(kk, vv)
-                got = lines_from_placement(pk.ids, *[x.tolist() for x in e.place_reads(cls, rank, s["freq"], s["min_unit"], s["min_inters"], 3)])
+                with e.knobs(**knobs):
+                    got = lines_from_placement(pk.ids, *[x.tolist() for x in e.place_reads(cls, rank, s["freq"], s["min_unit"], s["min_inters"], 3)])
                 rec.update(identical=got == want, placed=sum(1 for x in want if not x.endswith("None")), place_ms=round(float(e.times()["place_ms"]), 1))
                 if got != want:
                     rec["first_difference"] = next(((a, b) for a, b in zip(got, want) if a != b), (len(got), len(want)))

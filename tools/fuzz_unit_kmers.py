@@ -44,18 +44,16 @@ with Engine(0, lib) as e:
             ro = np.asarray(pk.read_off)
             seqs = [bytes(pk.bases[ro[r]:ro[r + 1]]) for r in range(pk.n_reads)]
             okeys, ocnt = unit_kmers.kmer_occurrences(seqs, k)
-            e.set_param("count_mode", 1); e.set_param("count_bits", 0)
-            for kk, vv in knobs.items():
-                e.set_param(kk, vv)
-            e.load(pk, 1); e.count_occurrences(k)
-            keys, lo, hi = e.table()
-            cnt = lo.astype(np.int64) | (hi.astype(np.int64) << 32)
-            ok = bool(np.array_equal(keys, okeys) and np.array_equal(cnt, ocnt))
-            tops = []
-            for n in (0, 1, int(rng.integers(2, 5000)), okeys.size, okeys.size + 7):
-                tk, tc = e.top_kmers(n)
-                w = unit_kmers.most_frequent(okeys, ocnt, n)
-                tops.append(bool(np.array_equal(tk, okeys[w]) and np.array_equal(tc.astype(np.int64), ocnt[w])))
+            with e.knobs(**knobs):
+                e.load(pk, 1); e.count_occurrences(k)
+                keys, lo, hi = e.table()
+                cnt = lo.astype(np.int64) | (hi.astype(np.int64) << 32)
+                ok = bool(np.array_equal(keys, okeys) and np.array_equal(cnt, ocnt))
+                tops = []
+                for n in (0, 1, int(rng.integers(2, 5000)), okeys.size, okeys.size + 7):
+                    tk, tc = e.top_kmers(n)
+                    w = unit_kmers.most_frequent(okeys, ocnt, n)
+                    tops.append(bool(np.array_equal(tk, okeys[w]) and np.array_equal(tc.astype(np.int64), ocnt[w])))
             rec.update(identical=ok and all(tops), table=ok, tops=tops, n_distinct=int(okeys.size), total=int(ocnt.sum()), max_count=int(ocnt.max()) if ocnt.size else 0)
         except DeviceError as ex:
             rec.update(identical=None if "(-22)" in str(ex) else False, refused=str(ex)[:200])

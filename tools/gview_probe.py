@@ -45,12 +45,11 @@ if lib_path:
     e.close(); sys.exit(0)
 if shapes:
     for wgs, block in ((2, 512), (3, 320), (4, 256), (2, 384), (1, 1024)):
-        e.set_param("dist_wgs", wgs); e.set_param("dist_block", block)
         try:
-            run(f"local clouds, 2^20 edges stored, {wgs} workgroups of {block} threads per CU", 1 << 20)
+            with e.knobs(dist_wgs=wgs, dist_block=block):
+                run(f"local clouds, 2^20 edges stored, {wgs} workgroups of {block} threads per CU", 1 << 20)
         except Exception as ex:      # a shape the LDS carve-up does not allow
             print(json.dumps(dict(case=f"{wgs} x {block}", error=str(ex)[:200])), flush=True)
-    e.set_param("dist_wgs", 0); e.set_param("dist_block", 0)
     json.dump(out, open(os.path.join(ROOT, "gpurun_out", "gview_probe_shapes.json"), "w"), indent=1)
     e.close(); sys.exit(0)
 run("local clouds, every edge stored", n + 16)

@@ -35,9 +35,9 @@ with Engine(0) as e:
         wl = lines_from_placement(pk.ids, *[x.tolist() for x in want])
         r = dict(params=s, placed=sum(1 for x in wl if not x.endswith("None")), oracle_s=round(t_cpu, 1))
         for mode in (2, 1) + ((3,) if s["min_inters"] < 4 else ()):      # (3: the regions forced where the default routes to the hash-map path)
-            e.set_param("place_mode", mode)
             try:
-                got = e.place_reads(cls, rank, s["freq"], s["min_unit"], s["min_inters"], 3)
+                with e.knobs(place_mode=mode):
+                    got = e.place_reads(cls, rank, s["freq"], s["min_unit"], s["min_inters"], 3)
             except Exception as ex:      # (place_mode 3 may refuse: regions that would need more than 2^32 slots; 2 and 1 must not)
                 if mode != 3:
                     raise
@@ -45,7 +45,6 @@ with Engine(0) as e:
                 continue
             r[f"mode{mode}_identical"] = lines_from_placement(pk.ids, *[x.tolist() for x in got]) == wl
             r[f"mode{mode}_ms"] = round(float(e.times()["place_ms"]), 1)
-        e.set_param("place_mode", 2)
         recs.append(r)
         print(json.dumps(r), flush=True)
 ok = all(v for r in recs for kk, v in r.items() if kk.endswith("_identical"))

@@ -32,8 +32,7 @@ with Engine(0) as e:
     print(json.dumps(dict(reads=int(pk.n_reads), bases=int(pk.n_bases), unique_kmers=int(gk.size), cloud_entries=int(ent.size), placed=sum(1 for x in want if not x.endswith("None")),
                           c_placer_s=round(time.time() - t0, 2))), flush=True)
     for mode in (2, 3, 1, 2):
-        e.set_param("place_mode", mode)
         t0 = time.time()
-        got = lines_from_placement(pk.ids, *[x.tolist() for x in e.place_reads(cls, rank, freq, 2, 10, 3)])
+        with e.knobs(place_mode=mode):
+            got = lines_from_placement(pk.ids, *[x.tolist() for x in e.place_reads(cls, rank, freq, 2, 10, 3)])
         print(json.dumps(dict(place_mode=mode, device_ms=round(float(e.times()["place_ms"]), 1), wall_s=round(time.time() - t0, 3), identical=got == want)), flush=True)
-    e.set_param("place_mode", 2)
