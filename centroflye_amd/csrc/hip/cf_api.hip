@@ -391,8 +391,9 @@ int cf_load_reads(cf_ctx* ctx, const uint8_t* bases, const int64_t* read_off, in
     ctx->n_bases = nb;
     ctx->h_read_off.assign(read_off, read_off + n_reads + 1);
     CF_TRY(cf_alloc_t(ctx, &ctx->d_bases, (size_t)nb + 64, "bases"));
-    // note: d_bases was allocated with +64 slack; account it under n_bases for release
-    ctx->live -= 64;
+    // note: d_bases was allocated with +64 slack; account it under n_bases for release (reads without bases — hand-made clouds — are
+    // released as the 16 bytes cf_release takes for an empty buffer: counted as 64 here, every such load took 16 bytes off hbm_bytes_live)
+    ctx->live -= nb ? 64 : 48;
     CF_TRY(cf_alloc_t(ctx, &ctx->d_read_off, (size_t)n_reads + 1, "read_off"));
     ctx->has_exotic = false;
     CF_TRY(cf_copy_h2d(ctx, ctx->d_bases, bases, (size_t)nb));      // (host or device memory: cf_copy_staged tells them apart)

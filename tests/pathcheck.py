@@ -87,13 +87,20 @@ def check_stage3(engine, pk, records, alns, lens, genomic_kmers, p3, expect_line
     return lines
 
 
-def check_clouds(engine, unit_ptr, cloud_ptr, entries, n_kmers, min_d, max_d, min_cov, rel_threshold=0.8):
+def clouds_histogram(unit_ptr, cloud_ptr, entries, n_kmers, min_d, max_d):
+    """The oracle's (a, b, d, cnt, E) of given clouds over all their reads: what check_clouds filters and compares with.  A caller
+    that runs one set of clouds through several launches computes it once and hands it to each of them."""
+    return recruit.dist_histogram(unit_ptr, cloud_ptr, entries, n_kmers, 0, unit_ptr.size - 1, min_d, max_d)
+
+
+def check_clouds(engine, unit_ptr, cloud_ptr, entries, n_kmers, min_d, max_d, min_cov, rel_threshold=0.8, hist=None):
     """A5 + A6 of the device on given clouds (cf_set_clouds; read i has the units unit_ptr[i] .. unit_ptr[i + 1]) against the
     oracle's histogram and filter (the dominance test as the reference does it: Python's int / int against the threshold).
+    hist: clouds_histogram of the same clouds and distances, computed before (None: computed here).
     Returns the oracle's edges (d, a, b, cnt), sorted."""
     n_reads = unit_ptr.size - 1
     U = int(unit_ptr[-1])
-    a, b, d, cnt, E = recruit.dist_histogram(unit_ptr, cloud_ptr, entries, n_kmers, 0, n_reads, min_d, max_d)
+    a, b, d, cnt, E = hist if hist is not None else clouds_histogram(unit_ptr, cloud_ptr, entries, n_kmers, min_d, max_d)
     edges, uniq = recruit.filter_edges(a, b, d, cnt, min_cov, rel_threshold)
     zeros = np.zeros(U, np.int64)
     engine.load_arrays(np.zeros(0, np.uint8), np.zeros(n_reads + 1, np.int64), unit_ptr, zeros, zeros)

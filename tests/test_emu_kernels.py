@@ -48,7 +48,10 @@ def test_stage2_small(engine, report, oracle_stage2):
 def test_sketch_counters_of_four_bits_and_of_eight(engine, report, oracle_stage2, bits):
     """Round 6: the counting sketch's counters have 4 bits when min_cov <= 9 (twice as many in the same LDS; an add that sees 12 or more
     takes itself back, the add that would wrap a field is seen and the first k-mer falls back to "every b marked") — same results as with
-    bytes; the synthetic clouds give ONE k-mer 300 postings, i.e. pairs counted far beyond 15 and beyond 255."""
+    bytes; the synthetic clouds give ONE k-mer 300 postings, i.e. pairs counted far beyond 15 and beyond 255.
+    Those random clouds select NO edge at the default threshold (pathcheck.check_synthetic_clouds says so itself): the wrap and the
+    fall-back run here only where the right answer is the empty set.  tests/test_emu_dist_counts.py (countcheck.py) holds the cases
+    whose counts pass 15 and 255 in pairs that ARE selected, with their exact counts."""
     tup = oracle_stage2("lowcov", max_distance=2)
     with engine.knobs(dist_slots=2048, dist_block=128, dist_sketch_bits=bits):
         pathcheck.check_stage2(engine, report("lowcov"), tup)
