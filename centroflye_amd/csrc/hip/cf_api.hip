@@ -504,16 +504,28 @@ struct cf_knob {
     void (*store)(cf_ctx* ctx, int64_t v);
     int64_t (*load)(const cf_ctx* ctx);
 };
-static const cf_knob cf_knobs[] = {
-#define CF_KNOB(name, type, def, accepted, stored, refusal) \
+#define CF_KNOB_ENTRY(name, type, def, accepted, stored, refusal) \
     {#name, refusal, [](int64_t v) -> bool { (void)v; return accepted; }, [](cf_ctx* ctx, int64_t v) { ctx->name = stored; }, [](const cf_ctx* ctx) -> int64_t { return ctx->name; }},
+static const cf_knob cf_knobs[] = {
+#define CF_KNOB CF_KNOB_ENTRY
+#define CF_KNOB_AB(...)
 #include "cf_knobs.h"
 #undef CF_KNOB
+#undef CF_KNOB_AB
+};
+static const cf_knob cf_ab_knobs[] = {      // the A/B switches: found by name, not listed by cf_param_name
+#define CF_KNOB(...)
+#define CF_KNOB_AB CF_KNOB_ENTRY
+#include "cf_knobs.h"
+#undef CF_KNOB
+#undef CF_KNOB_AB
 };
 static const int cf_n_knobs = (int)(sizeof(cf_knobs) / sizeof(cf_knobs[0]));
 
 static const cf_knob* cf_find_knob(cf_ctx* ctx, const char* name) {
     for (const cf_knob& k : cf_knobs)
+        if (!std::strcmp(k.name, name)) return &k;
+    for (const cf_knob& k : cf_ab_knobs)
         if (!std::strcmp(k.name, name)) return &k;
     cf_fail(ctx, -22, std::string("unknown parameter ") + name);
     return nullptr;

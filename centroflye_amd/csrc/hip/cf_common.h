@@ -222,8 +222,10 @@ struct cf_ctx {
 
     // the knobs of cf_set_param: one member per entry of cf_knobs.h, with its default
 #define CF_KNOB(name, type, def, accepted, stored, refusal) type name = def;
+#define CF_KNOB_AB(name, type, def, accepted, stored, refusal) type name = def;
 #include "cf_knobs.h"
 #undef CF_KNOB
+#undef CF_KNOB_AB
 };
 
 int cf_fail(cf_ctx* ctx, int code, const std::string& msg);

@@ -310,14 +310,38 @@ __device__ __forceinline__ unsigned long long cf_readlane64(unsigned long long v
 }
 #define DIST_WALK_ROW 33u      // words of a position's LDS row: DIST_GROUP_MAX postings and one of padding (lane l writes row l: 33 l + k takes every bank once)
 #define DIST_WALK_LDS(block) ((size_t)((block) / 64) * 64 * DIST_WALK_ROW * 4)
+// DESIGN.md 36 (knob dist_walk, kTab): the union of the group that is open lives in a hash table of the wave's LDS, unit -> bit: 64 slots of
+// 8 bytes (bit << 32 | unit; at most 32 are in use), home slot cf_walk_home(unit), linear probing that wraps.  A member's lanes probe for
+// their postings TOGETHER — one LDS round trip for the list where the lanes' copy of the union took a broadcast, a compare and a ballot
+// per posting — and the new postings are put in by their own lanes, numbered by their rank among the new ones (the order the __ffs loop
+// gives them).  The bits of the hits go into the member's word of o_or[] with an LDS `or` that nobody waits for: the mask is read when the
+// wave leaves the window.  The launch is what it was.  !kTab is the kernel as it was (the union in the lanes).
+#define DIST_WALK_TAB 64u      // slots of the union's table (a power of two, at least 2 x DIST_GROUP_MAX: a probe always meets an empty slot)
+#define DIST_WALK_WAVE_TAB (64u * DIST_WALK_ROW + DIST_WALK_TAB * 2u + 64u)      // words of a wave with the table: rows, table, o_or[]
+#define DIST_WALK_LDS_TAB(block) ((size_t)((block) / 64) * DIST_WALK_WAVE_TAB * 4)
+#define DIST_WALK_EMPTY 0xFFFFFFFFFFFFFFFFull
+__device__ __forceinline__ uint32_t cf_walk_home(uint32_t unit) { return (unit * 0x9E3779B1u) >> 26; }      // (tests/walkcheck.py restates it)
+#if defined(CF_WALK_STAMPS)
+// Diagnostic build only (-DCF_WALK_STAMPS, tools/walk_stamps.py): shader-clock sums per wave, added to dg[] once per wave: [0] cycles inside
+// the member loops (without the windows loaded there) [1] inside load_window [2] the waves' lifetimes [3] members walked [4] postings
+// tested against a union [5] waves; per workgroup b: [8 + 2 b] max of ~start, [9 + 2 b] max of end (its lifetime: the slowest wave's)
+#define WALK_CLOCK() ((unsigned long long)__builtin_amdgcn_s_memtime())
+#define WALK_STAMP(...) __VA_ARGS__
+#else
+#define WALK_STAMP(...)
+#endif
+template <bool kTab>
 __global__ void __launch_bounds__(256)
 cf_group_walk_kernel(const unsigned long long* __restrict__ keys, int64_t n, int kb, int ab, const int64_t* __restrict__ post_ptr, const int32_t* __restrict__ post,
                      const unsigned long long* __restrict__ not_a_set, uint32_t cap, const cf_dist_rec* __restrict__ urange, const int32_t* __restrict__ rend, int32_t min_d, int32_t max_d,
                      uint32_t* __restrict__ flags, uint32_t* __restrict__ member_mask, uint32_t* __restrict__ new_mask,
-                     unsigned long long* __restrict__ entries_out, unsigned long long* __restrict__ self_out) {
+                     unsigned long long* __restrict__ entries_out, unsigned long long* __restrict__ self_out, unsigned long long* __restrict__ dg) {
     // kb: the key's bits below the first unit (rank and order bits); ab: bits of the rank
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t* const rows = (uint32_t*)cf_lds + (size_t)(threadIdx.x >> 6) * (64u * DIST_WALK_ROW);      // the wave's 64 rows
+    uint32_t* const rows = (uint32_t*)cf_lds + (size_t)(threadIdx.x >> 6) * (kTab ? DIST_WALK_WAVE_TAB : 64u * DIST_WALK_ROW);      // the wave's 64 rows
+    unsigned long long* const tab = (unsigned long long*)(rows + 64u * DIST_WALK_ROW);      // kTab: the union's table ...
+    uint32_t* const o_or = (uint32_t*)(tab + DIST_WALK_TAB);      // ... and per position of the window the bits of the member's postings the union had
+    WALK_STAMP(const unsigned long long dg_t0 = WALK_CLOCK(); unsigned long long dg_mem = 0, dg_load = 0, dg_n = 0, dg_p = 0;)
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
     const unsigned long long rank_mask = (1ull << ab) - 1ull;
     const bool off = *not_a_set != 0ull;
@@ -331,11 +355,17 @@ cf_group_walk_kernel(const unsigned long long* __restrict__ keys, int64_t n, int
         uint32_t w_len = 0, o_mask = 0, o_new = 0;
         bool o_start = false, o_done = false;
         auto flush = [&]() {
+            if (kTab) {      // (the hits' bits: every `or` of the window has been issued, and the LDS takes a wave's operations in order)
+                __builtin_amdgcn_wave_barrier();
+                o_mask |= o_or[lane];
+                o_or[lane] = 0u;
+            }
             if (o_done) { const int64_t i = wb + (int64_t)lane; flags[i] = o_start ? 1u : 0u; member_mask[i] = o_mask; new_mask[i] = o_new; }
             o_done = false;
         };
         // all: every list of the window (else: the window a run goes on in — the lists of `fu` only).  own: the chunk of this wave — the emissions of its positions too.
         auto load_window = [&](int64_t b, bool all, bool own, unsigned long long fu) {
+            WALK_STAMP(const unsigned long long dg_l0 = WALK_CLOCK(); struct dg_scope { unsigned long long t0, &sum; __device__ ~dg_scope() { sum += WALK_CLOCK() - t0; } } dg_s{dg_l0, dg_load};)
             flush();
             wb = b; w_fu = ~0ull; w_p0 = 0; w_len = 0;
             const int64_t i = b + (int64_t)lane;
@@ -430,6 +460,7 @@ cf_group_walk_kernel(const unsigned long long* __restrict__ keys, int64_t n, int
                 }
             }
         };
+        if (kTab) o_or[lane] = 0u;      // (flush reads it, and load_window starts with one)
         load_window(c0, true, true, 0ull);
         const int64_t i_me = c0 + (int64_t)lane;
         if (off) { if (i_me < n) { flags[i_me] = 1u; member_mask[i_me] = 0u; new_mask[i_me] = 0u; } continue; }
@@ -442,18 +473,52 @@ cf_group_walk_kernel(const unsigned long long* __restrict__ keys, int64_t n, int
             if (wb != c0) load_window(c0, true, false, 0ull);      // (a run that went on beyond the chunk is the chunk's last: not taken)
             const unsigned long long fu = cf_readlane64(w_fu, s);
             uint32_t un = 0xFFFFFFFEu, nu = 0, members = 0;      // (no posting is 0xFFFFFFFE or 0xFFFFFFFF: unit numbers have 31 bits)
+            WALK_STAMP(const unsigned long long dg_r0 = WALK_CLOCK(), dg_rl = dg_load;)
             uint32_t L_next = rows[(uint32_t)s * DIST_WALK_ROW + (lane & 31u)];      // the list of the member to come, fetched while this one is tested
             for (int64_t j = c0 + s; j < n; ++j) {
                 if (j - wb == 64) { load_window(j, false, false, fu); L_next = rows[lane & 31u]; }
                 const int sl = (int)(j - wb);
                 if (cf_readlane64(w_fu, sl) != fu) break;
+                WALK_STAMP(++dg_n;)
                 const uint32_t len = (uint32_t)__builtin_amdgcn_readlane((int)w_len, sl);
                 const uint32_t L = lane < len ? L_next : 0xFFFFFFFFu;      // (len <= cap below: the list's lanes)
                 L_next = rows[(uint32_t)min(sl + 1, 63) * DIST_WALK_ROW + (lane & 31u)];
                 uint32_t mask = 0, fresh = 0;
                 bool start = true;
                 if (len > cap) { nu = 0; members = 0; }      // a group of its own (it counts); the next k-mer starts one too
+                else if (kTab) {
+                    WALK_STAMP(if (nu) dg_p += len;)
+                    bool hit = false;
+                    uint32_t bit = 0;
+                    if (nu && lane < len)      // (nu == 0: nothing to find, and the table may hold what a list of more than cap postings left standing)
+                        for (uint32_t h = cf_walk_home(L);; h = (h + 1u) & (DIST_WALK_TAB - 1u)) {
+                            const unsigned long long e = tab[h];
+                            if ((uint32_t)e == L) { hit = true; bit = (uint32_t)(e >> 32); break; }
+                            if (e == DIST_WALK_EMPTY) break;
+                        }
+                    const uint32_t found = nu ? (uint32_t)cf_ballot(hit) : 0u;
+                    const uint32_t mine = (uint32_t)((1ull << len) - 1ull);
+                    uint32_t nm = mine & ~found;
+                    start = members == 0u || members == DIST_CLASS_CAP || nu + (uint32_t)__popc(nm) > cap;
+                    if (start) {      // a cut: the table is empty again
+                        nu = 0; members = 0; nm = mine;
+                        __builtin_amdgcn_wave_barrier();
+                        tab[lane] = DIST_WALK_EMPTY;
+                        __builtin_amdgcn_wave_barrier();
+                    } else if (hit) atomicOr(&o_or[sl], 1u << bit);
+                    fresh = nm;
+                    if (lane < len && ((nm >> lane) & 1u)) {      // (len <= 32: the shifts stay below the word's width) the new postings take the bits nu, nu + 1, ... in the list's order
+                        const unsigned long long e = ((unsigned long long)(nu + (uint32_t)__popc(nm & ((1u << lane) - 1u))) << 32) | (unsigned long long)L;
+                        for (uint32_t h = cf_walk_home(L); atomicCAS(&tab[h], DIST_WALK_EMPTY, e) != DIST_WALK_EMPTY; h = (h + 1u) & (DIST_WALK_TAB - 1u)) {}
+                    }
+                    __builtin_amdgcn_wave_barrier();      // (the next member's probes come after these inserts)
+                    const uint32_t c = (uint32_t)__popc(nm);
+                    mask = (uint32_t)(((1ull << c) - 1ull) << nu);
+                    nu += c;
+                    ++members;
+                }
                 else {
+                    WALK_STAMP(if (nu) dg_p += len;)
                     uint32_t found = 0;      // the postings of the list that the union has
                     // eight postings to a trip, without a branch: the broadcasts and compares of a trip do not wait for each other.  A posting is in
                     // the union once at most, and the lane that holds it there IS its bit: the ballot goes into the mask as it is.  (The lanes of L
@@ -484,6 +549,7 @@ cf_group_walk_kernel(const unsigned long long* __restrict__ keys, int64_t n, int
                 }
                 if (lane == (uint32_t)sl) { o_start = start; o_mask = mask; o_new = fresh; o_done = true; }
             }
+            WALK_STAMP(dg_mem += (WALK_CLOCK() - dg_r0) - (dg_load - dg_rl);)
         }
         flush();
     }
@@ -491,6 +557,11 @@ cf_group_walk_kernel(const unsigned long long* __restrict__ keys, int64_t n, int
     if (lane == 0u) {
         if (ent) atomicAdd(entries_out, ent);
         if (self) atomicAdd(self_out, self);
+#if defined(CF_WALK_STAMPS)
+        const unsigned long long dg_t1 = WALK_CLOCK();
+        atomicAdd(dg + 0, dg_mem); atomicAdd(dg + 1, dg_load); atomicAdd(dg + 2, dg_t1 - dg_t0); atomicAdd(dg + 3, dg_n); atomicAdd(dg + 4, dg_p); atomicAdd(dg + 5, 1ull);
+        atomicMax(dg + 8 + 2 * (size_t)blockIdx.x, ~dg_t0); atomicMax(dg + 9 + 2 * (size_t)blockIdx.x, dg_t1);
+#endif
     }
 }
 // Per group g (the k-mers order[gfirst[g] .. gfirst[g + 1])): the union of the members' lists at upost[32 g ..] — every member's new postings, in
@@ -2070,11 +2141,30 @@ int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int3
         CF_TRY(tmp.get(&d_cfirst, (size_t)n_order + 1, "class starts"));
         CF_HIP(hipMemsetAsync(d_cflag, 0, (size_t)(n_order + 1) * 4, ctx->stream));
         if (groups) { CF_TRY(tmp.get(&d_mmask, (size_t)n_order + 1, "member masks")); CF_TRY(tmp.get(&d_newm, (size_t)n_order + 1, "members' new postings")); }
-        if (groups)      // the cut of the runs into groups, and the members' own emissions
-            hipLaunchKernelGGL(cf_group_walk_kernel, dim3(g_cls), dim3(256), DIST_WALK_LDS(256), ctx->stream, (const unsigned long long*)d_okeys, n_order, ab + hb, ab,
+        if (groups) {      // the cut of the runs into groups, and the members' own emissions
+            const bool tab = ctx->dist_walk;      // (the open group's union in an LDS table; 0: in the lanes)
+            const unsigned g_walk = g_cls;
+            unsigned long long* d_wdg = nullptr;
+#if defined(CF_WALK_STAMPS)
+            CF_TRY(tmp.get(&d_wdg, 8 + 2 * (size_t)g_walk, "walk stamps"));
+            CF_HIP(hipMemsetAsync(d_wdg, 0, (8 + 2 * (size_t)g_walk) * 8, ctx->stream));
+#endif
+            hipLaunchKernelGGL(tab ? cf_group_walk_kernel<true> : cf_group_walk_kernel<false>, dim3(g_walk), dim3(256), tab ? DIST_WALK_LDS_TAB(256) : DIST_WALK_LDS(256), ctx->stream,
+                               (const unsigned long long*)d_okeys, n_order, ab + hb, ab,
                                (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), (uint32_t)ctx->dist_group_cap,
-                               (const cf_dist_rec*)d_urange, (const int32_t*)d_rend, min_d_eff, max_d, d_cflag, d_mmask, d_newm, d_cnt + 1, d_cnt + 3);
-        else
+                               (const cf_dist_rec*)d_urange, (const int32_t*)d_rend, min_d_eff, max_d, d_cflag, d_mmask, d_newm, d_cnt + 1, d_cnt + 3, d_wdg);
+#if defined(CF_WALK_STAMPS)
+            {
+                std::vector<unsigned long long> dgh(8 + 2 * (size_t)g_walk);
+                if (hipMemcpy(dgh.data(), d_wdg, dgh.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
+                    unsigned long long wg = 0;      // the workgroups' lifetimes, a wave slot each for every wave of theirs
+                    for (size_t b = 0; b < g_walk; ++b) if (dgh[9 + 2 * b]) wg += (dgh[9 + 2 * b] - ~dgh[8 + 2 * b]) * 4ull;
+                    std::fprintf(stderr, "[cf_walk stamps] member=%llu load=%llu wave_life=%llu slot_life=%llu members=%llu postings=%llu waves=%llu (shader cycles summed over the waves of %u workgroups; dist_walk=%d)\n",
+                                 dgh[0], dgh[1], dgh[2], wg, dgh[3], dgh[4], dgh[5], g_walk, tab ? 1 : 0);
+                }
+            }
+#endif
+        } else
         hipLaunchKernelGGL(cf_class_mark_kernel, dim3(g_cls), dim3(256), 0, ctx->stream, (const unsigned long long*)d_okeys, n_order, ab,
                            (const int64_t*)d_post_ptr, (const int32_t*)d_post, (const unsigned long long*)(d_cnt + 144), d_cflag);
         CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_cflag, d_cidx, n_order, &n_heads));

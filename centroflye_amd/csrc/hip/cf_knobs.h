@@ -3,7 +3,8 @@
 //   CF_KNOB(name, member type, default, accepted, stored, refusal)
 // `accepted` and `stored` are expressions in the caller's int64_t v (cf_in(v, lo, hi): lo <= v <= hi).  cf_common.h expands the
 // table into the members of cf_ctx with their defaults; cf_api.hip into the entries cf_set_param, cf_get_param and cf_param_name
-// look a name up in, in this order.  A knob that takes every value (stored as v != 0) has no refusal.  What a knob means to a
+// look a name up in, in this order.  CF_KNOB_AB(...) has the same fields: an A/B switch that cf_set_param and cf_get_param know by name
+// and cf_param_name does not list (the listed knobs are the interface callers tune by; a switch between a kernel and the one it replaced is not).  A knob that takes every value (stored as v != 0) has no refusal.  What a knob means to a
 // caller stands in include/cfhip.h, in front of cf_set_param (tests/test_emu_params.py holds the two lists of names together).
 
 // threads per workgroup; 0 = chosen with dist_wgs
@@ -46,6 +47,8 @@ CF_KNOB(dist_classes, bool, true, true, v != 0, "")
 CF_KNOB(dist_groups, bool, true, true, v != 0, "")
 // the mask table's filter evaluates every (hot slot, member) pair of a group in one section, rows reserved per group; 0: the loop over the members, one filter each
 CF_KNOB(dist_filter_once, bool, true, true, v != 0, "")
+// the cut of the runs into groups keeps the open group's union in an LDS table unit -> bit that a member's lanes probe together; 0: the union in the lanes, a broadcast and a compare per posting
+CF_KNOB_AB(dist_walk, bool, true, true, v != 0, "")
 // postings of a group's union (1 .. 32: the mask's bits; tests: small caps close groups early)
 CF_KNOB(dist_group_cap, int, 32, cf_in(v, 1, 32), (int)v, "dist_group_cap out of range (1 .. 32)")
 // bits of a sketch counter: 0 = 4 when min_cov <= 9, else 8; 8 forces bytes

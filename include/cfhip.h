@@ -721,6 +721,12 @@ int cf_allreduce_unique(cf_ctx* ctx, int64_t* n_unique);
 int cf_set_param(cf_ctx* ctx, const char* name, int64_t value);
 int cf_get_param(cf_ctx* ctx, const char* name, int64_t* value);
 const char* cf_param_name(int32_t index);
+/* A/B switches: names that cf_set_param and cf_get_param know and cf_param_name does not list — a kernel against the one it
+ * replaced, for tests and measurements; not part of what callers tune by, and the results are the same either way.
+ *
+ * "dist_walk": 1, the default: the kernel that cuts the runs of first k-mers into groups keeps the open group's union in an LDS
+ * table from unit to bit, which the lanes of a member's list probe together; 0: the union in the lanes with a broadcast and a
+ * compare per posting, the kernel it was before. */
 
 /* Self-tests of the device primitives against host results (used by tests/ only). */
 int cf_selftest_sort(cf_ctx* ctx, const uint64_t* keys, int64_t n, int32_t bits, uint64_t* out);
