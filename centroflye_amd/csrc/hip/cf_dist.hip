@@ -1869,6 +1869,9 @@ int cf_edges_checksum(cf_ctx* ctx, int64_t n, uint64_t* out) {
 int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int32_t max_d, uint32_t min_cov,
                   double rel_threshold, int32_t part, int32_t n_parts, int64_t edge_cap, int64_t* n_edges) {
     if (!ctx) return -22;
+    // A call that fails leaves no launch behind (cfhip.h): no stored edge, and not the counters of the last launch that succeeded
+    ctx->n_edges_stored = 0;
+    ctx->stats.n_edges = 0; ctx->stats.n_emissions = 0; ctx->stats.n_spilled = 0; ctx->stats.n_dist_passes = 0;
     if (!ctx->have_clouds && !ctx->have_gview) return cf_fail(ctx, -22, "cf_dist_edges: no clouds built");
     // the clouds the stage works on: the all-gathered ones of every rank (multi-GPU) or the local ones
     const bool gv = ctx->have_gview;

@@ -133,7 +133,16 @@ int cf_set_clouds(cf_ctx* ctx, const int64_t* cloud_ptr, const int32_t* entries,
  * [min_n, max_n), then keep (d, a, b, cnt) with cnt >= min_cov and
  * (double)cnt / (double)sum_d cnt >= rel_threshold.  Up to edge_cap edges are stored on the
  * device (all are counted); the unique-k-mer bitmap accumulates across calls until
- * cf_reset_unique(). */
+ * cf_reset_unique().
+ * A call that fails leaves NO launch behind: n_edges, n_emissions, n_dist_passes, n_spilled and n_edges_stored of cf_stats are 0,
+ * cf_get_edges, cf_sort_edges and cf_edges_checksum see no stored edge (cf_get_edges copies nothing), *n_edges is not written, and
+ * the edges of an earlier call are gone too (a failed launch may have written over them).  The context stays usable and owns no
+ * more memory than after the same call failing once before.  Most failures (-22, -34: the input does not fit a layout or a field)
+ * come before anything runs.  One comes from the kernel itself, after it has run to its end: -34 "cf_dist_edges: (b,d) table could
+ * not be partitioned far enough" — one partner b has more distinct distances under one first k-mer than a partition of the LDS table
+ * may hold, and the table is split by bits of b, which keeps the keys of one b together however far it goes (a larger "dist_slots",
+ * or the default table, takes such an input).  After THAT failure the unique-k-mer bitmap may hold bits of the first k-mers that did
+ * fit: call cf_reset_unique() and run the parts again before the bitmap is used. */
 int cf_dist_edges(cf_ctx* ctx, int64_t min_n, int64_t max_n, int32_t min_d, int32_t max_d,
                   uint32_t min_cov, double rel_threshold, int32_t part, int32_t n_parts,
                   int64_t edge_cap, int64_t* n_edges);
