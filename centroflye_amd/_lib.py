@@ -166,6 +166,9 @@ PROTOTYPES = {
     "cf_consensus_run": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _P, C.POINTER(C.c_float)]),
     "cf_consensus_get": (C.c_int, [_P, _I32, _P, _P, _P, _P]),
     "cf_consensus_info": (C.c_int, [_P, C.POINTER(ConsensusShape)]),
+    "cf_consensus_run_support": (C.c_int, [_P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _I32, _P, C.POINTER(C.c_float)]),
+    "cf_consensus_support": (C.c_int, [_P, _I32, _P]),
+    "cf_consensus_reads": (C.c_int, [_P, _I32, _P, _P]),
     "cf_ualign_run": (C.c_int, [_P, _P, _I32, _P, _P, _I64, _I32, _I32, _I32, _P, C.POINTER(C.c_float)]),
     "cf_ualign_ops": (C.c_int, [_P, _P, _P, _I64, _PI64]),
     "cf_ualign_info": (C.c_int, [_P, C.POINTER(UalignShape)]),

@@ -1,6 +1,7 @@
-"""The cen6 pipeline's driver up to the pseudounits: the drop-in for the reference's ``scripts/centroFlyeMono.py`` as far as this project
-builds it.  It takes the reference's arguments and ``--stop-after {correction,graph,mapping,scaffolds,pseudounits}``; without
-``--stop-after`` it refuses at once (polishing is not built) and writes nothing.
+"""The cen6 pipeline's driver up to the polished scaffolds: the drop-in for the reference's ``scripts/centroFlyeMono.py`` as far as this
+project builds it.  It takes the reference's arguments and ``--stop-after {correction,graph,mapping,scaffolds,pseudounits,polishing}``;
+without ``--stop-after`` it refuses at once and writes nothing: what follows polishing in the reference, its hand-made join of the
+first two scaffolds, is not built.
 
 With it: the report is read (``SD_Report``), the monostrings are corrected (``error_correction``, verbose, on a copy), the iterative
 de Bruijn graph is built for k = --min-k .. --max-k, the corrected reads are mapped to the graph of --max-k (``map_reads``, one
@@ -15,33 +16,48 @@ written, each through ``.tmp`` and a rename (formats: INTEGRATION.md):
   OUTDIR/mappings.tsv          id, part, first hit, last hit (edge:letter:read position), valid, path as edge indices; '.' without a hit
   OUTDIR/scaffolds.tsv         index, edge indices, sequence
   OUTDIR/pseudounits.tsv       scaffold, unit, st, en, number of reads
-  OUTDIR/read_pseudounits.tsv  scaffold, unit, id, part, st, en, strand — sorted by id and part within a unit"""
+  OUTDIR/read_pseudounits.tsv  scaffold, unit, id, part, st, en, strand — sorted by id and part within a unit
+``--stop-after polishing`` then reads --centromeric-reads (FASTA or FASTQ, plain or gzip) and hands every scaffold to ``polish``
+(debruijn_graph.py), which writes OUTDIR/polishing: with ``--polisher flye`` (the default, as the reference) one Flye run per
+pseudounit, with ``--polisher consensus`` the built-in polisher and no external program.  A refusal of ``polish`` exits non-zero and
+leaves no polishing directory."""
 import argparse
 import os
 import sys
 
 import numpy as np
 
-from .debruijn_graph import cover_scaffolds_w_reads, extract_read_pseudounits, iterative_graph, read2scaffolds, scaffolding
+from .debruijn_graph import PolishError, cover_scaffolds_w_reads, extract_read_pseudounits, iterative_graph, polish, read2scaffolds, scaffolding
 from .mono_error_correction import error_correction
+from .read_recruitment import iter_seqs
 from .sd_parser import SD_Report
 
-STAGES = ('correction', 'graph', 'mapping', 'scaffolds', 'pseudounits')
+STAGES = ('correction', 'graph', 'mapping', 'scaffolds', 'pseudounits', 'polishing')
 
 
 def parse_args(argv=None):
-    parser = argparse.ArgumentParser(description="The cen6 pipeline from the String Decomposer report to the pseudounits and the reads that cover them")
+    parser = argparse.ArgumentParser(description="The cen6 pipeline from the String Decomposer report to the polished scaffolds")
     parser.add_argument('--sd-report', help='the String Decomposer report (decomposition.tsv)', required=True)
     parser.add_argument('--monomers', help='FASTA of the monomers the report was made with', required=True)
-    parser.add_argument('--centromeric-reads', help='the centromeric reads (read by the polishing stage only: accepted, unused)', required=True)
+    parser.add_argument('--centromeric-reads', help='the centromeric reads, FASTA or FASTQ, plain or gzip (read by the polishing stage only)', required=True)
     parser.add_argument('--outdir', help='directory the files are written to', required=True)
     parser.add_argument('--min-k', help='smallest k of the iterative graph', type=int, default=100)
     parser.add_argument('--max-k', help='largest k of the iterative graph', type=int, default=400)
     parser.add_argument('--min-mult', help='windows a mono-k-mer needs to count as frequent', type=int, default=5)
-    parser.add_argument('--polish-n-iter', help='polishing rounds (accepted, unused)', type=int, default=2)
-    parser.add_argument('--polish-n-threads', help='polishing threads (accepted, unused)', type=int, default=50)
-    parser.add_argument('--stop-after', choices=STAGES, help='Stop after this stage (required: polishing is not built)')
-    return parser.parse_args(argv)
+    parser.add_argument('--polish-n-iter', help='polishing rounds (polishing stage only)', type=int, default=2)
+    parser.add_argument('--polish-n-threads', help='threads of a Flye run (polishing stage with --polisher flye only)', type=int, default=50)
+    parser.add_argument('--polisher', choices=('flye', 'consensus'), default='flye',
+                        help="flye: one external Flye run per pseudounit, as the reference; consensus: the built-in polisher, no external program")
+    parser.add_argument('--flye-bin', help='the Flye binary (--polisher flye)', default='flye')
+    parser.add_argument('--consensus-max-divergence-permille', type=int, default=300,
+                        help='--polisher consensus: a read votes if its edit distance to the template is at most this many thousandths of the template length')
+    parser.add_argument('--uncovered-pseudounits', choices=('refuse', 'monomers'), default='refuse',
+                        help="a pseudounit no read covers: refuse, or take the concatenation of its letters' monomers, unpolished")
+    parser.add_argument('--stop-after', choices=STAGES, help="Stop after this stage (required: the reference's manual join of scaffolds behind polishing is not built)")
+    params = parser.parse_args(argv)
+    if params.consensus_max_divergence_permille < 0:
+        parser.error('--consensus-max-divergence-permille must not be negative')
+    return params
 
 
 def _write(path, lines):
@@ -104,7 +120,8 @@ def read_pseudounit_lines(read_pseudounits):
 def main(argv=None):
     params = parse_args(argv)
     if params.stop_after is None:
-        sys.exit('centroFlyeMono: polishing is not built; run with --stop-after ' + ', '.join(STAGES[:-1]) + ' or ' + STAGES[-1])
+        sys.exit("centroFlyeMono: the reference's hand-made join of scaffolds that follows polishing is not built; run with --stop-after " + ', '.join(STAGES[:-1]) +
+                 ' or ' + STAGES[-1])
     stop = STAGES.index(params.stop_after)
     os.makedirs(params.outdir, exist_ok=True)
 
@@ -149,4 +166,17 @@ def main(argv=None):
     pseudounits, read_pseudounits = extract_read_pseudounits(coverage, scaffolds, monostrings=ec_monostrings)
     _write(os.path.join(params.outdir, 'pseudounits.tsv'), pseudounit_lines(pseudounits, read_pseudounits))
     _write(os.path.join(params.outdir, 'read_pseudounits.tsv'), read_pseudounit_lines(read_pseudounits))
+    if stop == 4:
+        return 0
+
+    print('Reading centromeric reads')
+    centromeric_reads = {name.decode(): seq.decode('latin-1') for name, seq in iter_seqs(params.centromeric_reads)}
+    monomers = {name.decode(): seq.decode('latin-1') for name, seq in iter_seqs(params.monomers)}
+    print('Polishing')
+    try:
+        polish(scaffolds=scaffolds, pseudounits=pseudounits, read_pseudounits=read_pseudounits, reads=centromeric_reads, monomers=monomers,
+               outdir=os.path.join(params.outdir, 'polishing'), n_iter=params.polish_n_iter, n_threads=params.polish_n_threads, flye_bin=params.flye_bin,
+               polisher=params.polisher, permille=params.consensus_max_divergence_permille, uncovered=params.uncovered_pseudounits)
+    except PolishError as e:
+        sys.exit(f'centroFlyeMono: {e}')
     return 0

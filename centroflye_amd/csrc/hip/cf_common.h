@@ -176,6 +176,11 @@ struct cf_ctx {
     std::vector<std::vector<uint8_t>> cons_bytes;
     std::vector<std::vector<int64_t>> cons_off;
     std::vector<std::vector<int32_t>> cons_voting, cons_excluded;
+    // per iteration: the support of every output byte (cf_consensus_support; 16 bits, saturated, as the device keeps it), per read
+    // its distance or -1 and its vote flag (cf_consensus_reads)
+    std::vector<std::vector<uint16_t>> cons_agree;
+    std::vector<std::vector<int32_t>> cons_dist;
+    std::vector<std::vector<uint8_t>> cons_voted;
     cf_consensus_shape cons_last{};
 
     // results of the last cf_ualign_run (cf_ualign.hip), in host memory: the hits, the op strings as a CSR over its reads, and the

@@ -22,9 +22,14 @@
 //                         bit of its k-th byte).  Every loop is bounded by m + n, the band or the block.
 //   cf_cons_vote_kernel   one thread per (position, slot s and column s): the rows of the position's reads lie back to back, so
 //                         the threads of a wave read consecutive bytes of one row; 21 tallies in registers, no atomics; up to
-//                         5 bytes and their count per thread.
+//                         5 bytes and their count per thread, and beside every byte its support `agree` (the tally of the base
+//                         emitted, 0 for a template byte kept with no vote: the rule at cf_consensus_run) in 16 bits, saturating at 65 535:
+//                         5 x 2 contiguous bytes.  Only for cf_consensus_run_support (template argument SUPPORT): at the cenX shape the
+//                         stores and the copies of the support cost more than the spread of the parent's runs.
 //   cf_cons_compact_kernel / cf_cons_off_kernel   after the exclusive scan of cf_prims.hip over the counts: the next templates
-//                         back to back and their offsets.
+//                         back to back and their offsets; the support moves with its byte through the same scan indices.
+// With support, per read the host keeps, iteration by iteration, the vote flag and the distance as the align kernel left it (exact for a read that
+// votes; a read that does not vote never had its distance established: -1), for cf_consensus_reads.
 #include "cf_common.h"
 
 #define CF_CONS_MAX_LEN 8192           // bytes of a template or a read: the strings and a full band fit the LDS window
@@ -43,6 +48,9 @@
 __device__ __forceinline__ uint32_t cf_cons_code(uint32_t b) { return cf_is_acgt(b) ? cf_base2(b) : 5u; }
 
 __device__ __forceinline__ uint8_t cf_cons_letter(int code) { return (uint8_t)(0x54474341u >> (8 * code)); }      // 0 .. 3 -> A, C, G, T
+
+// a tally as the support is stored: 16 bits, saturating
+__device__ __forceinline__ uint16_t cf_cons_sat16(int32_t v) { return (uint16_t)(v < 65535 ? v : 65535); }
 
 struct cf_cons_pairs {
     const uint8_t* t;            // the templates of this iteration, back to back
@@ -193,10 +201,12 @@ __device__ __forceinline__ int64_t cf_cons_pos_of(const int64_t* __restrict__ t_
     return lo;
 }
 
+template <bool SUPPORT>      // SUPPORT: cf_consensus_run_support asked for the support; without it the kernel stores what it always stored
 __global__ void __launch_bounds__(CF_CONS_VOTE_THREADS)
 cf_cons_vote_kernel(const uint8_t* __restrict__ t, const int64_t* __restrict__ t_off, int64_t n_pos, const int64_t* __restrict__ pos_ptr,
                     const uint8_t* __restrict__ vote, const uint8_t* __restrict__ col, const uint16_t* __restrict__ slot,
-                    const int64_t* __restrict__ col_off, const int64_t* __restrict__ slot_off, uint8_t* __restrict__ emit, uint32_t* __restrict__ cnt) {
+                    const int64_t* __restrict__ col_off, const int64_t* __restrict__ slot_off, uint8_t* __restrict__ emit, uint16_t* __restrict__ agree,
+                    uint32_t* __restrict__ cnt) {
     const int64_t G = t_off[n_pos] - t_off[0] + n_pos;
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
         const int64_t p = cf_cons_pos_of(t_off, n_pos, g + t_off[0]);
@@ -219,6 +229,7 @@ cf_cons_vote_kernel(const uint8_t* __restrict__ t, const int64_t* __restrict__ t
             }
         }
         uint8_t* out = emit + g * (CF_CONS_K_INS + 1);
+        uint16_t* sup = SUPPORT ? agree + g * (CF_CONS_K_INS + 1) : nullptr;      // (without SUPPORT there is no such array)
         uint32_t n_out = 0;
         bool open = true;
 #pragma unroll
@@ -229,6 +240,7 @@ cf_cons_vote_kernel(const uint8_t* __restrict__ t, const int64_t* __restrict__ t
                 int best = 0;
 #pragma unroll
                 for (int b = 1; b < 4; ++b) best = ins[k][b] > ins[k][best] ? b : best;
+                if (SUPPORT) sup[n_out] = cf_cons_sat16(ins[k][best]);
                 out[n_out++] = cf_cons_letter(best);
             }
         }
@@ -237,24 +249,28 @@ cf_cons_vote_kernel(const uint8_t* __restrict__ t, const int64_t* __restrict__ t
             int best = 0;
 #pragma unroll
             for (int b = 1; b < 5; ++b) best = cv[b] > cv[best] ? b : best;
-            if (cv[best] == 0) out[n_out++] = (uint8_t)tb;
+            if (cv[best] == 0) { if (SUPPORT) sup[n_out] = 0; out[n_out++] = (uint8_t)tb; }      // the template byte kept with no vote
             else {
                 const uint32_t tc = cf_cons_code(tb);
                 if (tc < 4u && cv[tc] == cv[best]) best = (int)tc;
-                if (best < 4) out[n_out++] = cf_cons_letter(best);
+                if (best < 4) { if (SUPPORT) sup[n_out] = cf_cons_sat16(cv[best]); out[n_out++] = cf_cons_letter(best); }
             }
         }
         cnt[g] = n_out;
     }
 }
 
+template <bool SUPPORT>
 __global__ void __launch_bounds__(CF_CONS_VOTE_THREADS)
-cf_cons_compact_kernel(const uint8_t* __restrict__ emit, const uint32_t* __restrict__ cnt, const int64_t* __restrict__ idx, int64_t G,
-                       uint8_t* __restrict__ out) {
+cf_cons_compact_kernel(const uint8_t* __restrict__ emit, const uint16_t* __restrict__ agree, const uint32_t* __restrict__ cnt,
+                       const int64_t* __restrict__ idx, int64_t G, uint8_t* __restrict__ out, uint16_t* __restrict__ out_agree) {
     for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < G; g += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t c = cnt[g] <= CF_CONS_K_INS + 1 ? cnt[g] : CF_CONS_K_INS + 1;
         const int64_t o = idx[g];
-        for (uint32_t q = 0; q < c; ++q) out[o + q] = emit[g * (CF_CONS_K_INS + 1) + q];
+        for (uint32_t q = 0; q < c; ++q) {
+            out[o + q] = emit[g * (CF_CONS_K_INS + 1) + q];
+            if (SUPPORT) out_agree[o + q] = agree[g * (CF_CONS_K_INS + 1) + q];
+        }
     }
 }
 
@@ -294,8 +310,33 @@ int cf_consensus_get(cf_ctx* ctx, int32_t iter, uint8_t* out_bytes, int64_t* out
     return 0;
 }
 
+int cf_consensus_support(cf_ctx* ctx, int32_t iter, int32_t* agree) {
+    if (!ctx) return -22;
+    if (iter < 1 || (size_t)iter > ctx->cons_agree.size())
+        return cf_fail(ctx, -22, "cf_consensus_support: iteration " + std::to_string(iter) + " is not one of the " + std::to_string(ctx->cons_agree.size()) + " of the last run with support (cf_consensus_run_support)");
+    const std::vector<uint16_t>& a = ctx->cons_agree[(size_t)iter - 1];
+    if (agree) std::copy(a.begin(), a.end(), agree);
+    return 0;
+}
+
+int cf_consensus_reads(cf_ctx* ctx, int32_t iter, int32_t* dist, uint8_t* voted) {
+    if (!ctx) return -22;
+    if (iter < 1 || (size_t)iter > ctx->cons_dist.size())
+        return cf_fail(ctx, -22, "cf_consensus_reads: iteration " + std::to_string(iter) + " is not one of the " + std::to_string(ctx->cons_dist.size()) + " of the last run with support (cf_consensus_run_support)");
+    const size_t i = (size_t)iter - 1;
+    if (dist && !ctx->cons_dist[i].empty()) std::memcpy(dist, ctx->cons_dist[i].data(), ctx->cons_dist[i].size() * 4);
+    if (voted && !ctx->cons_voted[i].empty()) std::memcpy(voted, ctx->cons_voted[i].data(), ctx->cons_voted[i].size());
+    return 0;
+}
+
 int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off, const uint8_t* reads, const int64_t* r_off,
                      const int64_t* pos_ptr, int64_t n_pos, int32_t n_iters, int32_t permille, int64_t* total_bytes_out, float* ms_out) {
+    return cf_consensus_run_support(ctx, templates, t_off, reads, r_off, pos_ptr, n_pos, n_iters, permille, 0, total_bytes_out, ms_out);
+}
+
+int cf_consensus_run_support(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off, const uint8_t* reads, const int64_t* r_off,
+                             const int64_t* pos_ptr, int64_t n_pos, int32_t n_iters, int32_t permille, int32_t with_support,
+                             int64_t* total_bytes_out, float* ms_out) {
     if (!ctx) return -22;
     if (ms_out) *ms_out = 0.f;
     if (n_pos < 0) return cf_fail(ctx, -22, "cf_consensus_run: negative number of positions");
@@ -325,7 +366,10 @@ int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off
     // the results of this call, handed to the context only when everything worked
     std::vector<std::vector<uint8_t>> res_bytes((size_t)n_iters);
     std::vector<std::vector<int64_t>> res_off((size_t)n_iters);
-    std::vector<std::vector<int32_t>> res_voting((size_t)n_iters), res_excluded((size_t)n_iters);
+    std::vector<std::vector<int32_t>> res_voting((size_t)n_iters), res_excluded((size_t)n_iters), res_dist(with_support ? (size_t)n_iters : 0);
+    const bool support = with_support != 0;
+    std::vector<std::vector<uint16_t>> res_agree(support ? (size_t)n_iters : 0);
+    std::vector<std::vector<uint8_t>> res_voted(support ? (size_t)n_iters : 0);
     cf_consensus_shape shape{};
     shape.n_pos = n_pos;
     shape.n_reads = n_reads;
@@ -431,6 +475,7 @@ int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off
         CF_HIP(hipEventRecord(e0, ctx->stream));
         cf_scratch iter_tmp(ctx);
         uint32_t *d_area = nullptr, *d_cnt = nullptr;
+        uint16_t *d_agree = nullptr, *d_next_agree = nullptr;
         uint8_t *d_col = nullptr, *d_emit = nullptr, *d_next = nullptr;
         uint16_t* d_slot = nullptr;
         int64_t *d_idx = nullptr, *d_next_off = nullptr;
@@ -438,6 +483,7 @@ int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off
         CF_TRY(iter_tmp.get(&d_col, (size_t)col_total + 16, "consensus column rows"));
         CF_TRY(iter_tmp.get(&d_slot, (size_t)slot_total + 16, "consensus slot rows"));
         CF_TRY(iter_tmp.get(&d_emit, (size_t)G * (CF_CONS_K_INS + 1) + 16, "consensus emitted bytes"));
+        if (support) CF_TRY(iter_tmp.get(&d_agree, (size_t)G * (CF_CONS_K_INS + 1) + 8, "consensus support"));
         CF_TRY(iter_tmp.get(&d_cnt, (size_t)G + 1, "consensus counts"));
         CF_TRY(iter_tmp.get(&d_idx, (size_t)G + 1, "consensus offsets"));
         CF_TRY(iter_tmp.get(&d_next_off, (size_t)n_pos + 1, "consensus template offsets"));
@@ -469,16 +515,17 @@ int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off
         int64_t total_out = 0;
         if (G > 0) {
             const int vgrid = cf_grid_for(G, CF_CONS_VOTE_THREADS, std::max(1, ctx->n_cu) * 16);
-            hipLaunchKernelGGL(cf_cons_vote_kernel, dim3((unsigned)vgrid), dim3(CF_CONS_VOTE_THREADS), 0, ctx->stream, (const uint8_t*)d_t,
+            hipLaunchKernelGGL(support ? cf_cons_vote_kernel<true> : cf_cons_vote_kernel<false>, dim3((unsigned)vgrid), dim3(CF_CONS_VOTE_THREADS), 0, ctx->stream, (const uint8_t*)d_t,
                                (const int64_t*)d_t_off, n_pos, (const int64_t*)d_pos_ptr, (const uint8_t*)d_vote, (const uint8_t*)d_col,
-                               (const uint16_t*)d_slot, (const int64_t*)d_col_off, (const int64_t*)d_slot_off, d_emit, d_cnt);
+                               (const uint16_t*)d_slot, (const int64_t*)d_col_off, (const int64_t*)d_slot_off, d_emit, d_agree, d_cnt);
             CF_KERNEL_CHECK("cf_cons_vote_kernel");
             CF_HIP(hipEventRecord(e3, ctx->stream));
             CF_TRY(cf_scan_exclusive_u32_to_i64(ctx, d_cnt, d_idx, G, &total_out));
             CF_TRY(iter_tmp.get(&d_next, (size_t)total_out + 16, "consensus templates"));
+            if (support) CF_TRY(iter_tmp.get(&d_next_agree, (size_t)total_out + 8, "consensus support"));
             const int pgrid = cf_grid_for(n_pos + 1, CF_CONS_VOTE_THREADS, std::max(1, ctx->n_cu) * 16);
-            hipLaunchKernelGGL(cf_cons_compact_kernel, dim3((unsigned)vgrid), dim3(CF_CONS_VOTE_THREADS), 0, ctx->stream, (const uint8_t*)d_emit,
-                               (const uint32_t*)d_cnt, (const int64_t*)d_idx, G, d_next);
+            hipLaunchKernelGGL(support ? cf_cons_compact_kernel<true> : cf_cons_compact_kernel<false>, dim3((unsigned)vgrid), dim3(CF_CONS_VOTE_THREADS), 0, ctx->stream, (const uint8_t*)d_emit,
+                               (const uint16_t*)d_agree, (const uint32_t*)d_cnt, (const int64_t*)d_idx, G, d_next, d_next_agree);
             hipLaunchKernelGGL(cf_cons_off_kernel, dim3((unsigned)pgrid), dim3(CF_CONS_VOTE_THREADS), 0, ctx->stream, (const int64_t*)d_t_off, n_pos,
                                (const int64_t*)d_idx, total_out, d_next_off);
             CF_KERNEL_CHECK("the cf_cons_compact kernels");
@@ -505,6 +552,17 @@ int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off
         if (total_out > 0) CF_TRY(cf_copy_d2h(ctx, res_bytes[(size_t)it].data(), d_next, (size_t)total_out));
         CF_TRY(cf_copy_d2h(ctx, res_off[(size_t)it].data(), d_next_off, ((size_t)n_pos + 1) * 8));
         if (n_reads > 0) CF_TRY(cf_copy_d2h(ctx, h_vote.data(), d_vote, (size_t)n_reads));
+        if (support) {
+            res_agree[(size_t)it].resize((size_t)total_out);
+            if (total_out > 0) CF_TRY(cf_copy_d2h(ctx, res_agree[(size_t)it].data(), d_next_agree, (size_t)total_out * 2));
+            // per read: the distance is exact where the read votes; elsewhere the band stopped at the limit (or the lengths alone
+            // excluded the read) and d_dprev holds the next pass's first half-width, not a distance
+            res_dist[(size_t)it].resize((size_t)n_reads);
+            if (n_reads > 0) CF_TRY(cf_copy_d2h(ctx, res_dist[(size_t)it].data(), d_dprev, (size_t)n_reads * 4));
+            for (int64_t q = 0; q < n_reads; ++q)
+                if (!h_vote[(size_t)q]) res_dist[(size_t)it][(size_t)q] = -1;
+            res_voted[(size_t)it] = h_vote;
+        }
         res_voting[(size_t)it].assign((size_t)n_pos, 0);
         res_excluded[(size_t)it].assign((size_t)n_pos, 0);
         for (int64_t q = 0; q < n_reads; ++q) ++(h_vote[(size_t)q] ? res_voting : res_excluded)[(size_t)it][(size_t)h_pair_pos[(size_t)q]];
@@ -536,6 +594,9 @@ int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off
     ctx->cons_off.swap(res_off);
     ctx->cons_voting.swap(res_voting);
     ctx->cons_excluded.swap(res_excluded);
+    ctx->cons_agree.swap(res_agree);
+    ctx->cons_dist.swap(res_dist);
+    ctx->cons_voted.swap(res_voted);
     ctx->cons_last = shape;
     return 0;
 }

@@ -1,5 +1,5 @@
 """The de Bruijn graph on monostrings, the reads mapped to it, scaffolds and pseudounits: the drop-in for the reference's
-``scripts/debruijn_graph.py`` as far as ``centroFlyeMono.py`` runs it before polishing (``polish`` is not here).  The hits of the reads on
+``scripts/debruijn_graph.py`` as far as ``centroFlyeMono.py`` runs it, ``polish`` included (at the end of the file).  The hits of the reads on
 the edges come from the device too (``Engine.monomap``, cf_monomap.hip); scaffolding and what follows it work on edge paths of a few
 dozen elements and are host Python.
 
@@ -556,3 +556,220 @@ def extract_read_pseudounits(scaf_read_coverage, scaffold_seqs, monostrings, min
             per_unit.append(spans)
         read_pseudounits.append(per_unit)
     return pseudounits, read_pseudounits
+
+
+# ---------------------------------------------------------------- polishing
+class PolishError(RuntimeError):
+    """polish refuses: nothing it wrote is left behind"""
+
+
+_RC = str.maketrans('ATGCatgc-', 'TACGtacg-')
+
+
+def RC(s):
+    """the reference's reverse complement: ATGCatgc- swapped, every other byte as it is"""
+    return s.translate(_RC)[::-1]
+
+
+def _read_id(key):
+    """the read a monostring key belongs to: a cut read is keyed (id, part)"""
+    return key[0] if isinstance(key, tuple) else key
+
+
+def _first_record(fn):
+    """the sequence of the first FASTA record, its lines joined"""
+    with open(fn) as f:
+        blocks = f.read().split('>')[1:]
+    if not blocks:
+        raise PolishError(f'{fn} holds no record')
+    return ''.join(blocks[0].split('\n')[1:]).replace('\r', '')
+
+
+class _Tree:
+    """the directories and files of one polish call: every file through .tmp and a rename, all of it gone again after rollback()"""
+
+    def __init__(self):
+        self.dirs, self.files = [], []
+
+    def makedirs(self, path):
+        missing = []
+        while path and not os.path.isdir(path):
+            missing.append(path)
+            path = os.path.dirname(path)
+        for d in reversed(missing):
+            os.mkdir(d)
+            self.dirs.append(d)
+
+    def write(self, path, text):
+        self.files.append(path)
+        with open(path + '.tmp', 'w') as f:
+            f.write(text)
+        os.replace(path + '.tmp', path)
+
+    def rollback(self):
+        import shutil
+        for fn in self.files:
+            for p in (fn, fn + '.tmp'):
+                if os.path.exists(p):
+                    os.remove(p)
+        for d in reversed(self.dirs):
+            shutil.rmtree(d, ignore_errors=True)
+
+
+def _fasta(records):
+    return ''.join(f'>{name}\n{seq}\n' for name, seq in records.items())
+
+
+def _monomer_template(scaffold, st, en, monomers, where):
+    """the letters st .. en of the scaffold as nucleotides: the k-th monomer of the file is the k-th upper-case letter (SD_Report's
+    monomer_names_map), a lower-case letter its reverse complement"""
+    from string import ascii_lowercase, ascii_uppercase
+    names = [name for name in monomers if not name.endswith("'")]
+    upper = {c: monomers[name] for name, c in zip(names, ascii_uppercase)}
+    lower = {c: RC(monomers[name]) for name, c in zip(names, ascii_lowercase)}
+    out = []
+    for c in scaffold[st:en + 1]:
+        if c not in upper and c not in lower:
+            raise PolishError(f'{where} has the letter {c!r}, which is no monomer')
+        out.append(upper[c] if c in upper else lower[c])
+    return ''.join(out)
+
+
+def polish(scaffolds, pseudounits, read_pseudounits, reads, monomers, outdir, n_iter, n_threads, flye_bin='flye', *,
+           polisher='flye', permille=300, uncovered='refuse', engine=None):
+    """Every pseudounit polished with the stretches of the reads that cover it, and the polished pseudounits of a scaffold joined
+    (the reference's ``polish``).  The export is the reference's, byte for byte: OUTDIR/scaffold_i/pseudounit_j/reads.fasta holds
+    reads[read id][st:en + 1] of every covering read under the id s_{i}_t_{j}_{read id}_{st}_{en + 1}, reverse-complemented on strand
+    '-', in the dict's order (a repeated id overwrites); template.fasta the first id in sorted order whose length is
+    statistics.median_high of the lengths.  The read id of a key is key[0] for an (id, part) key and the key itself for a plain
+    string (the reference takes r_id[0] either way: the first character of a plain id).
+
+    polisher='flye' runs the reference's command per pseudounit (`flye_bin --nano-raw reads.fasta --polish-target template.fasta -i
+    n_iter -t n_threads -o dir`, printed as the reference prints it) and reads polished_{n_iter}.fasta; a missing binary raises
+    before anything is written, a missing polished file raises (the reference's fallback names an undefined variable).
+    polisher='consensus' runs the built-in polisher once over all pseudounits of all scaffolds (``Engine.consensus_run``, n_iter
+    passes, letters a .. z upper-cased for the run only), writes pseudounit_j/polished_k.fasta (>consensus_s_{i}_t_{j}_iter_{k}) for
+    k = 1 .. n_iter, and files of this project: OUTDIR/consensus_report.tsv, OUTDIR/read_votes.tsv and
+    scaffold_i/scaffold_i.support.tsv (formats: INTEGRATION.md).  Both write scaffold_i/scaffold_i.fasta (>scaffold_{i}_niter_{n_iter}).
+
+    A pseudounit no read covers: uncovered='refuse' raises and names it (the reference dies in median_high([])); 'monomers' takes
+    the concatenation of its letters' monomers as its sequence, unpolished.  Wherever the function raises — an uncovered
+    pseudounit, a read id that `reads` lacks, a string beyond the consensus polisher's limit, a polisher that fails — nothing it
+    wrote is left."""
+    import shutil
+    import statistics
+    import subprocess
+    if polisher not in ('flye', 'consensus'):
+        raise ValueError("polisher is 'flye' or 'consensus'")
+    if uncovered not in ('refuse', 'monomers'):
+        raise ValueError("uncovered is 'refuse' or 'monomers'")
+    if int(n_iter) < 1:
+        raise PolishError('n_iter must be at least 1')
+    if int(permille) < 0:
+        raise PolishError('permille must not be negative')
+    if polisher == 'flye' and shutil.which(str(flye_bin)) is None:
+        raise PolishError(f"the Flye binary '{flye_bin}' was not found (flye_bin; or polisher='consensus', which needs none)")
+
+    # the export, in memory: (i, j, {segment id: segment}, template id, template, covered)
+    units = []
+    for i, (scaffold, scaf_pseudounits) in enumerate(zip(scaffolds, pseudounits)):
+        for j, (s_st, s_en) in enumerate(scaf_pseudounits):
+            covering = read_pseudounits[i][j] if j < len(read_pseudounits[i]) else {}
+            segments = {}
+            for key, (r_st, r_en, strand) in covering.items():
+                r_id = _read_id(key)
+                if r_id not in reads:
+                    raise PolishError(f'pseudounit {j} of scaffold {i}: the read {r_id!r} is not among the reads')
+                segment = reads[r_id][r_st:r_en + 1]
+                segments[f's_{i}_t_{j}_{r_id}_{r_st}_{r_en + 1}'] = RC(segment) if strand == '-' else segment
+            if not segments:
+                if uncovered == 'refuse':
+                    raise PolishError(f"pseudounit {j} of scaffold {i} (letters {s_st} .. {s_en}) is covered by no read (uncovered='monomers' fills it from the monomers)")
+                units.append((i, j, segments, f's_{i}_t_{j}_monomers', _monomer_template(scaffold, s_st, s_en, monomers, f'pseudounit {j} of scaffold {i}'), False))
+                continue
+            med_len = statistics.median_high([len(s) for s in segments.values()])
+            template_id = next(s_id for s_id in sorted(segments) if len(segments[s_id]) == med_len)
+            units.append((i, j, segments, template_id, segments[template_id], True))
+
+    e = None
+    if polisher == 'consensus':
+        if engine is None:
+            from . import session
+            engine = session.engine()
+        e = engine
+        max_len = e.consensus_info()['max_len']
+        for i, j, segments, _, template, _ in units:
+            longest = max([len(template)] + [len(s) for s in segments.values()])
+            if longest > max_len:
+                raise PolishError(f"pseudounit {j} of scaffold {i} has a sequence of {longest} bases, more than the {max_len} polisher='consensus' takes")
+
+    tree = _Tree()
+    try:
+        tree.makedirs(outdir)
+        dirs = {}
+        n_scaffolds = min(len(scaffolds), len(pseudounits))
+        for i in range(n_scaffolds):
+            tree.makedirs(os.path.join(outdir, f'scaffold_{i}'))
+        polished = {}      # (i, j) -> the polished sequence
+        for i, j, segments, template_id, template, covered in units:
+            d = dirs[i, j] = os.path.join(outdir, f'scaffold_{i}', f'pseudounit_{j}')
+            tree.makedirs(d)
+            tree.write(os.path.join(d, 'reads.fasta'), _fasta(segments))
+            tree.write(os.path.join(d, 'template.fasta'), _fasta({template_id: template}))
+            if polisher == 'flye':
+                if not covered:
+                    polished[i, j] = template
+                    continue
+                cmd = [str(x) for x in (flye_bin, '--nano-raw', os.path.join(d, 'reads.fasta'), '--polish-target', os.path.join(d, 'template.fasta'),
+                                        '-i', n_iter, '-t', n_threads, '-o', d)]
+                print(' '.join(cmd))
+                subprocess.check_call(cmd)
+                fn = os.path.join(d, f'polished_{n_iter}.fasta')
+                if not os.path.isfile(fn):
+                    raise PolishError(f'pseudounit {j} of scaffold {i}: Flye left no {fn}')
+                polished[i, j] = _first_record(fn)
+        if polisher == 'consensus':
+            _polish_consensus(tree, e, units, dirs, outdir, int(n_iter), int(permille), polished)
+        for i in range(n_scaffolds):
+            seq = ''.join(polished[i, j] for j in range(len(pseudounits[i])))
+            tree.write(os.path.join(outdir, f'scaffold_{i}', f'scaffold_{i}.fasta'), _fasta({f'scaffold_{i}_niter_{n_iter}': seq}))
+    except BaseException:
+        tree.rollback()
+        raise
+
+
+def _polish_consensus(tree, e, units, dirs, outdir, n_iter, permille, polished):
+    """one consensus_run over every pseudounit; polished_k.fasta, consensus_report.tsv, read_votes.tsv, scaffold_i.support.tsv"""
+    up = lambda s: s.encode('latin-1').upper()      # noqa: E731  (bytes.upper touches a .. z only)
+    templates = [up(t) for _, _, _, _, t, _ in units]
+    flat = [up(s) for _, _, segments, _, _, _ in units for s in segments.values()]
+    seg_ids = [s_id for _, _, segments, _, _, _ in units for s_id in segments]
+    t_off = np.zeros(len(units) + 1, np.int64)
+    np.cumsum([len(t) for t in templates], out=t_off[1:])
+    pos_ptr = np.zeros(len(units) + 1, np.int64)
+    np.cumsum([len(u[2]) for u in units], out=pos_ptr[1:])
+    r_off = np.zeros(len(flat) + 1, np.int64)
+    np.cumsum([len(r) for r in flat], out=r_off[1:])
+    res = e.consensus_run(b''.join(templates), t_off, b''.join(flat), r_off, pos_ptr, n_iter, permille, support=True)
+    per_read = [e.consensus_reads(k) for k in range(1, n_iter + 1)]
+    agree = e.consensus_support(n_iter)
+    report = ['scaffold\tunit\treads\ttemplate\ttemplate_length' + ''.join(f'\tlength_{k}\tvoting_{k}\texcluded_{k}' for k in range(1, n_iter + 1)) + '\tuncovered\n']
+    votes, support = [], {}
+    for x, (i, j, segments, template_id, template, covered) in enumerate(units):
+        row = f'{i}\t{j}\t{len(segments)}\t{template_id}\t{len(template)}'
+        for k, (b, off, n_voting, n_excluded) in enumerate(res, 1):
+            text = b[off[x]:off[x + 1]].tobytes().decode('latin-1')
+            tree.write(os.path.join(dirs[i, j], f'polished_{k}.fasta'), f'>consensus_s_{i}_t_{j}_iter_{k}\n{text}\n')
+            row += f'\t{len(text)}\t{int(n_voting[x])}\t{int(n_excluded[x])}'
+        polished[i, j] = text
+        report.append(row + f'\t{int(not covered)}\n')
+        for q in range(int(pos_ptr[x]), int(pos_ptr[x + 1])):
+            votes.append(f'{i}\t{j}\t{seg_ids[q]}' + ''.join(f'\t{int(dist[q])}\t{int(voted[q])}' for dist, voted in per_read) + '\n')
+        off, n_voting = res[-1][1], res[-1][2]
+        lines = support.setdefault(i, [])
+        for a in agree[off[x]:off[x + 1]].tolist():
+            lines.append(f'{len(lines)}\t{j}\t{a}\t{int(n_voting[x])}\n')
+    tree.write(os.path.join(outdir, 'consensus_report.tsv'), ''.join(report))
+    tree.write(os.path.join(outdir, 'read_votes.tsv'), ''.join(votes))
+    for i, lines in support.items():
+        tree.write(os.path.join(outdir, f'scaffold_{i}', f'scaffold_{i}.support.tsv'), ''.join(lines))

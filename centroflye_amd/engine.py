@@ -531,11 +531,12 @@ class Engine:
         return d
 
     # ------------------------------------------------------------------ the built-in consensus polisher (cf_consensus.hip)
-    def consensus_run(self, templates, t_off, reads, r_off, pos_ptr, n_iters=4, permille=300):
+    def consensus_run(self, templates, t_off, reads, r_off, pos_ptr, n_iters=4, permille=300, support=False):
         """Every position's reads aligned to its template, a vote per column and insertion slot, n_iters passes, all positions in
         one call (the rule: include/cfhip.h at cf_consensus_run).  templates[t_off[p]:t_off[p + 1]] is the template of position p,
         reads[r_off[q]:r_off[q + 1]] read q, pos_ptr a CSR over the reads.  Returns [(bytes uint8, off int64[n_pos + 1], n_voting
-        int32[n_pos], n_excluded int32[n_pos]) for iteration 1 .. n_iters]; consensus_info() has the device times."""
+        int32[n_pos], n_excluded int32[n_pos]) for iteration 1 .. n_iters]; consensus_info() has the device times.  support=True
+        (cf_consensus_run_support) gives the same and keeps what consensus_support() and consensus_reads() hand out."""
         as_u8 = lambda x: np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray, memoryview)) else np.ascontiguousarray(x, np.uint8)
         templates, reads = as_u8(templates), as_u8(reads)
         t_off = np.ascontiguousarray(t_off, np.int64).reshape(-1)
@@ -550,8 +551,12 @@ class Engine:
         n_pos, n_iters = t_off.size - 1, int(n_iters)
         totals = np.zeros(max(n_iters, 1), np.int64)
         ms = C.c_float()
-        self._check(self._lib.cf_consensus_run(self._ctx, _ptr(templates) if templates.size else None, _ptr(t_off), _ptr(reads) if reads.size else None,
-                                               _ptr(r_off), _ptr(pos_ptr), n_pos, n_iters, int(permille), _ptr(totals), C.byref(ms)), "cf_consensus_run")
+        if support:
+            self._check(self._lib.cf_consensus_run_support(self._ctx, _ptr(templates) if templates.size else None, _ptr(t_off), _ptr(reads) if reads.size else None,
+                                                           _ptr(r_off), _ptr(pos_ptr), n_pos, n_iters, int(permille), 1, _ptr(totals), C.byref(ms)), "cf_consensus_run_support")
+        else:
+            self._check(self._lib.cf_consensus_run(self._ctx, _ptr(templates) if templates.size else None, _ptr(t_off), _ptr(reads) if reads.size else None,
+                                                   _ptr(r_off), _ptr(pos_ptr), n_pos, n_iters, int(permille), _ptr(totals), C.byref(ms)), "cf_consensus_run")
         out = []
         for i in range(n_iters):
             b, off = np.zeros(max(int(totals[i]), 1), np.uint8), np.zeros(n_pos + 1, np.int64)
@@ -559,6 +564,28 @@ class Engine:
             self._check(self._lib.cf_consensus_get(self._ctx, i + 1, _ptr(b), _ptr(off), _ptr(nv), _ptr(ne)), "cf_consensus_get")
             out.append((b[:int(totals[i])], off, nv[:n_pos], ne[:n_pos]))
         return out
+
+    def consensus_support(self, iter):
+        """int32[total bytes of iteration iter]: beside every byte iteration iter (1 .. n_iters) of the last consensus_run(support=True) emitted,
+        the tally of the base emitted (0 for a template byte kept with no vote; the rule: include/cfhip.h at cf_consensus_run).  The
+        off array of that iteration cuts it per position like the bytes."""
+        s = _lib.ConsensusShape()
+        self._check(self._lib.cf_consensus_info(self._ctx, C.byref(s)), "cf_consensus_info")
+        off = np.zeros(int(s.n_pos) + 1, np.int64)
+        self._check(self._lib.cf_consensus_get(self._ctx, int(iter), None, _ptr(off), None, None), "cf_consensus_support")
+        agree = np.zeros(max(int(off[-1]), 1), np.int32)
+        self._check(self._lib.cf_consensus_support(self._ctx, int(iter), _ptr(agree)), "cf_consensus_support")
+        return agree[:int(off[-1])]
+
+    def consensus_reads(self, iter):
+        """(dist int32[n_reads], voted bool[n_reads]) of iteration iter (1 .. n_iters) of the last consensus_run(support=True): whether the read
+        voted, and its distance to that iteration's template — exact where it voted, -1 where it did not (never established)."""
+        s = _lib.ConsensusShape()
+        self._check(self._lib.cf_consensus_info(self._ctx, C.byref(s)), "cf_consensus_info")
+        n = int(s.n_reads)
+        dist, voted = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.uint8)
+        self._check(self._lib.cf_consensus_reads(self._ctx, int(iter), _ptr(dist), _ptr(voted)), "cf_consensus_reads")
+        return dist[:n], voted[:n].astype(bool)
 
     def consensus_info(self):
         """The shape of cf_consensus.hip (max_len, block_small / block_big / big_from, launch_cap, batch_bytes, k_ins), the figures

@@ -332,7 +332,26 @@ int cf_tandem_info(cf_ctx* ctx, cf_tandem_shape* out);
  * out_off[n_pos + 1], n_voting[n_pos] and n_excluded[n_pos] (the reads of that pass that voted / did not); any may be NULL.
  * cf_consensus_info: the shape the tests straddle and the last run's figures.  phase_ms: copies to and from the device,
  * alignment (bands, moves, walks), vote and emission, scan and compaction, the whole call; by HIP events, summed over the
- * iterations of the last run. */
+ * iterations of the last run.
+ * Support (tests/supportcheck.py restates it).  cf_consensus_run_support is cf_consensus_run with one more argument:
+ * with_support == 0 is cf_consensus_run itself (which calls it so), the same kernels storing the same bytes; with_support != 0
+ * gives the same outputs bit for bit and keeps beside them what the vote otherwise discards (on request only: at the cenX shape
+ * the extra stores and copies cost more than the spread between runs).  Every byte a pass emits carries one
+ * number, `agree`:
+ *   - an inserted base at (slot s, k): the largest of its four tallies, which is the tally of the base emitted;
+ *   - a column base: 0 if all five tallies are 0 (the template byte kept with no vote; c_v == 0 is such a case), otherwise the
+ *     tally of the base emitted, which after the tie rule of step 4 equals the top tally;
+ *   - a column resolved as "deleted" emits nothing and has no entry;
+ *   - the device keeps the number in 16 bits, saturating: a tally above 65 535 (a position with more voting reads than that)
+ *     is reported as 65 535.  The bytes are decided on the full tallies.
+ * So 0 <= agree <= n_voting[p] for every byte of position p, and an iteration has exactly total_bytes_out[iter - 1] entries, in
+ * the order of its bytes (out_off of cf_consensus_get cuts both).  Per read q and iteration the context keeps voted[q] (1 / 0)
+ * and dist[q]: the read's distance d to that iteration's template where it voted (exact), -1 where it did not — the band
+ * stopped at the permille limit, or the lengths alone put the read beyond it, so d was never established.
+ * cf_consensus_support: agree (int32, room for total_bytes_out[iter - 1] entries) of iteration iter (1 .. n_iters) of the last run.
+ * cf_consensus_reads: dist[n_reads] and voted[n_reads] of that iteration.  Both refuse another iter with -22 like
+ * cf_consensus_get — after a run without support every iter is another one —; either output pointer may be NULL; both read
+ * host memory only. */
 typedef struct cf_consensus_shape {
     int64_t max_len;                      /* bytes of the longest template or read taken                              */
     int64_t block_small, block_big, big_from; /* threads per workgroup; batches with a band of more than big_from diagonals take block_big */
@@ -346,6 +365,11 @@ int cf_consensus_run(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off
                      const int64_t* pos_ptr, int64_t n_pos, int32_t n_iters, int32_t permille, int64_t* total_bytes_out, float* ms_out);
 int cf_consensus_get(cf_ctx* ctx, int32_t iter, uint8_t* out_bytes, int64_t* out_off, int32_t* n_voting, int32_t* n_excluded);
 int cf_consensus_info(cf_ctx* ctx, cf_consensus_shape* out);
+int cf_consensus_run_support(cf_ctx* ctx, const uint8_t* templates, const int64_t* t_off, const uint8_t* reads, const int64_t* r_off,
+                             const int64_t* pos_ptr, int64_t n_pos, int32_t n_iters, int32_t permille, int32_t with_support,
+                             int64_t* total_bytes_out, float* ms_out);
+int cf_consensus_support(cf_ctx* ctx, int32_t iter, int32_t* agree);
+int cf_consensus_reads(cf_ctx* ctx, int32_t iter, int32_t* dist, uint8_t* voted);
 
 /* The built-in tandem aligner (cf_ualign.hip): every read against the unit read cyclically, the best stretch per read.  It stands
  * in for the external NCRF binary the reference starts per chunk of reads (scripts/run_ncrf_parallel.py:49-62) and has NO

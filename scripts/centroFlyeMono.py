@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Entry point of the cen6 pipeline up to the pseudounits (--stop-after correction | graph | mapping | scaffolds | pseudounits).  Implementation: centroflye_amd/centroflye_mono.py."""
+"""Entry point of the cen6 pipeline up to the polished scaffolds (--stop-after correction | graph | mapping | scaffolds | pseudounits | polishing).  Implementation: centroflye_amd/centroflye_mono.py."""
 import os
 import sys
 
